@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decoded target tokens/sec of the streaming-ST hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -48,10 +48,6 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-# more hardware queues for the HIP runtime: with the default (4) at most 2 kernels from different streams
-# execute concurrently on this stack (tools/microbench_streams.hip); 8 lets 3-4 independent decode chains overlap.
-# Must be set before the runtime initialises; a process-level runtime knob, not a machine setting.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from bench_model import (B_PER_GPU, CROSS_ATTN_TRAFFIC_FILES, ENCODER_TRAFFIC_FILES, HBM_PEAK_GBS, L2_PEAK_GBS, MFMA_PEAK_TFLOPS,  # noqa: E402,F401
                          N_STEPS_DECODE, PMC_TRAFFIC_FILE, T_FRAMES, WAITK, algorithmic_work, class_roofline, class_work,
                          decode_path_options, log, model_param_bytes, path_bytes_per_token, roofline_entry)
@@ -105,6 +101,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run-gloo", action="store_true",
                     help="CPU rehearsal of the multi-rank plumbing (launcher, rendezvous, sharding, barriers, MAX over "
                          "ranks, hypothesis gather) on the gloo backend with a stand-in for the decode; measures nothing")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed passes, write what the last one returned (the hypotheses of every decoded utterance, "
+                         "token ids as float32) to DIR/hypotheses.npy and their row indices to DIR/hypotheses_rows.npy; above "
+                         f"{DUMP_LIMIT >> 20} MB a fixed seeded sample of rows.  The inputs are the same in every run")
     return ap.parse_args(argv)
 
 
@@ -151,6 +151,28 @@ def run_cpu_baseline(cfg, weights_f32, sample_B, n_steps, cores):
             "kind": "port",
             "sample": f"{sample_B} utterances x {T_FRAMES} frames, {n_steps} forced greedy steps "
                       f"({toks.numel()} tokens) in {dt:.1f} s, torch fp32, {cores} thread{'s' if cores > 1 else ''}"}, toks, fb
+
+
+DUMP_LIMIT = 64 << 20               # bytes --dump-outputs may write
+
+
+def dump_outputs(hyp, out_dir, limit=DUMP_LIMIT):
+    """--dump-outputs: the hypotheses [utterances, decode steps] of the last timed pass as float32 (token ids < 2**24 are exact)
+    plus the index of each stored row (float64); when all rows would exceed `limit` bytes, a sorted sample drawn with a fixed
+    seed.  Returns {file name: shape}."""
+    import numpy as np
+    import torch
+    h = hyp.detach().cpu()
+    n, u = h.size(0), (h.size(1) if h.dim() > 1 else 1)
+    keep = min(n, limit // (4 * u + 8))
+    rows = torch.arange(n)
+    if keep < n:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"hypotheses": h[rows].to(torch.float32).numpy(), "hypotheses_rows": rows.to(torch.float64).numpy()}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name + ".npy": list(a.shape) for name, a in out.items()}
 
 
 LEGS_FILE = "bench_legs.json"        # everything the line leaves out (per-row tables, per-utterance latency, census, notes)
@@ -478,6 +500,8 @@ def main(argv=None):
     value = tokens_per_step * args.steps / elapsed
     assert hyp_timed.shape[0] == B * args.steps * world, "the timed region did not decode every batch"
     log(f"timed passes of {args.steps} steps: {[round(x * 1e3, 2) for x in pass_s]} ms -> median {value:.0f} tokens/s")
+    if args.dump_outputs and rank == 0:
+        log(f"outputs of the last timed pass: {dump_outputs(hyp_timed, args.dump_outputs)} in {args.dump_outputs}")
 
     roofline, cpu_base = None, None
     if args.timed_only:

@@ -5,17 +5,17 @@ CPU:
     architectures and --simul-attn-type names land in ITS registries, under the reference's names;
   * `task.build_model(args)` -> `load_state_dict` -> `eval` -> `share_memory` -> `cuda` is the protocol the agent uses
     (agents/default_agent.py:205-224); the deferred build is checked up to the point where device memory is needed;
-  * where /root/reference is present (this container; not the GPU box): the reference's OWN agent methods
-    (`policy`, `predict`, `update_model_encoder`, `update_states_read`, `initialize_states`, `units_to_segment`),
-    imported by file path over stub `simuleval` / `fairseq` modules, and this package's agent drive the same recording
-    model through the same event script; the two call traces (method, keyword names, tensor shapes / values, dict
-    keys), actions and predictions must be identical.
+  * the reference's OWN agent methods (`policy`, `predict`, `update_model_encoder`, `update_states_read`,
+    `initialize_states`, `units_to_segment`) and this package's agent drive the same recording model through the same event
+    script; the two call traces (method, keyword names, tensor shapes / values, dict keys), actions and predictions must be
+    identical.  The reference's side is recorded in tests/golden/g22_agent_surface.json by
+    tests/golden/gen_golden_agent_surface.py (its methods imported by file path over stub `simuleval` / `fairseq` modules).
 GPU:
   * the SimulEval-facing agent on the real HIP model equals the frame-granular agent (which tests/test_hip_streaming.py
     pins to the oracle): READ/WRITE sequence and tokens, wait-k / MMA-hard / MMA-IL, incl. force_finish.
 """
 import argparse
-import importlib.util
+import json
 import os
 import subprocess
 import sys
@@ -26,7 +26,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_AGENT = "/root/reference/codebase/agents/default_agent.py"
+G22 = os.path.join(ROOT, "tests", "golden", "g22_agent_surface.json")
 
 
 # ----------------------------------------------------------------------------------------------------- registries
@@ -193,37 +193,6 @@ class RecordingModel:
         return 1024
 
 
-def _load_reference_agent():
-    """agents/default_agent.py by file path over stub simuleval / fairseq modules (nothing is copied)."""
-    def mod(name, **attrs):
-        m = types.ModuleType(name)
-        m.__dict__.update(attrs)
-        sys.modules[name] = m
-        return m
-
-    from simulst_amd import simuleval_agent as mine
-    saved = {k: sys.modules.get(k) for k in ("simuleval", "simuleval.agents", "simuleval.states", "fairseq",
-                                             "fairseq.data", "fairseq.data.audio", "fairseq.data.audio.audio_utils")}
-    mod("simuleval", READ_ACTION=mine.READ_ACTION, WRITE_ACTION=mine.WRITE_ACTION, DEFAULT_EOS=mine.DEFAULT_EOS)
-    mod("simuleval.agents", SpeechAgent=mine.SpeechAgent)
-    mod("simuleval.states", ListEntry=mine.ListEntry, SpeechStates=mine.SpeechStates)
-    mod("fairseq", utils=None, checkpoint_utils=None, tasks=None)
-    mod("fairseq.data")
-    mod("fairseq.data.audio")
-    mod("fairseq.data.audio.audio_utils", _get_kaldi_fbank=None, _get_torchaudio_fbank=None)
-    try:
-        spec = importlib.util.spec_from_file_location("_ref_default_agent", REF_AGENT)
-        m = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(m)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-    return m
-
-
 def _drive(agent, model, frames_per_read, force_finish_eos=False):
     """A SimulEval episode at unit granularity: READ -> new frames appended -> update_states_read; WRITE -> predict ->
     target unit appended (None included) -> units_to_segment on a queue.  Returns what the driver saw."""
@@ -256,56 +225,26 @@ def _drive(agent, model, frames_per_read, force_finish_eos=False):
     return seen
 
 
-@pytest.mark.skipif(not os.path.exists(REF_AGENT), reason="the reference tree is only present in the build container")
-@pytest.mark.parametrize("force_finish", [False, True])
-def test_same_calls_as_the_reference_agent(force_finish):
+SYMBOLS = ["<s>", "<pad>", "</s>", "<unk>"] + ["▁a", "b", "▁c", "d", "e", "▁f", "g", "▁h"]
+FEED = [(24, False), (16, False), (16, False), (7, True)]
+
+
+def call_script(force_finish, eos=2):
+    """READ/WRITE answers of the decoder: (action, argmax id).  With force_finish an early EOS is discarded."""
+    return [(0, 4), (1, 4), (1, 5), (0, 6), (1, 6), (1, eos if force_finish else 7), (1, 7), (0, 8), (1, 9), (1, 10),
+            (1, 11), (1, eos)]
+
+
+def merger_steps(make_segment):
+    """Random unit streams, incl. force-finish Nones and EOS, pushed one unit at a time through a units_to_segment form:
+    make_segment(tgt) -> segment(queue, states, target, max_len).  Returns, per case, the units, the max_len and every
+    (segment, queue after the call) the driver saw."""
     from simulst_amd import simuleval_agent as mine
     from simulst_amd.harness import Dictionary
-    ref_mod = _load_reference_agent()
-    symbols = ["<s>", "<pad>", "</s>", "<unk>"] + ["▁a", "b", "▁c", "d", "e", "▁f", "g", "▁h"]
-    tgt = Dictionary(symbols, 2)
-    eos = 2
-    # READ/WRITE answers of the decoder: (action, argmax id).  With force_finish an early EOS is discarded.
-    script = [(0, 4), (1, 4), (1, 5), (0, 6), (1, 6), (1, eos if force_finish else 7), (1, 7), (0, 8), (1, 9), (1, 10),
-              (1, 11), (1, eos)]
-    feed = [(24, False), (16, False), (16, False), (7, True)]
-    traces = []
-    for which in ("reference", "mine"):
-        model = RecordingModel(script)
-        if which == "reference":
-            agent = object.__new__(ref_mod.FairseqSimulSTAgent)            # its __init__ needs fairseq + a checkpoint
-            agent.model, agent.gpu, agent.dict, agent.pre_tokenizer = model, False, {"tgt": tgt}, None
-            agent.pre_decision_ratio = getattr(model.decoder.layers[0].encoder_attn, "pre_decision_ratio", 1)
-            agent.full_sentence, agent.force_finish = False, force_finish
-            agent.stride_ms = model.encoder.conv_layer_stride() * 10
-            agent.right_context, agent.segment_length = model.encoder.right_context, model.encoder.segment_length
-            agent.max_len = lambda x: min(1 * x + 0, model.max_decoder_positions())
-            agent.feature_extractor = types.SimpleNamespace(clear_cache=lambda: None)
-        else:
-            args = argparse.Namespace(force_finish=force_finish, max_len_a=1, max_len_b=0)
-            agent = mine.FairseqSimulSTAgent(args, model=model, tgt_dict=tgt)
-        seen = _drive(agent, model, feed)
-        traces.append((seen, model.trace))
-    (seen_ref, trace_ref), (seen_mine, trace_mine) = traces
-    assert len(trace_ref) > 15 and any(t[0] == "decoder.clear_cache" for t in trace_ref) == force_finish
-    assert trace_mine == trace_ref
-    assert seen_mine == seen_ref
-
-
-def test_word_merger_equals_reference_method_on_random_queues():
-    """Beyond the g15 fixture: random unit streams, incl. force-finish Nones and EOS, replayed through the reference's
-    units_to_segment (when present) and the table-driven WordMerger."""
-    if not os.path.exists(REF_AGENT):
-        pytest.skip("the reference tree is only present in the build container")
-    from simulst_amd import simuleval_agent as mine
-    from simulst_amd.harness import Dictionary, WordMerger
-    ref_mod = _load_reference_agent()
     g = torch.Generator().manual_seed(3)
     pieces = [("▁" if torch.rand(1, generator=g).item() < 0.4 else "") + f"p{i}" for i in range(40)]
-    tgt = Dictionary(["<s>", "<pad>", "</s>", "<unk>"] + pieces, 2)
-    ref = object.__new__(ref_mod.FairseqSimulSTAgent)
-    ref.dict, ref.pre_tokenizer = {"tgt": tgt}, None
-    merger = WordMerger(tgt)
+    segment = make_segment(Dictionary(["<s>", "<pad>", "</s>", "<unk>"] + pieces, 2))
+    cases = []
     for case in range(60):
         n = int(torch.randint(3, 25, (1,), generator=g))
         toks = [int(t) for t in torch.randint(4, 44, (n,), generator=g)]
@@ -313,21 +252,62 @@ def test_word_merger_equals_reference_method_on_random_queues():
             toks.insert(int(torch.randint(1, n, (1,), generator=g)), None)
         toks.append(2)
         max_len = 1000 if case % 5 else n // 2
-        ref.max_len = lambda x, m=max_len: m
-        qa, qb, target = mine.ListEntry(), mine.ListEntry(), []
+        q, target, steps = mine.ListEntry(), [], []
         states = types.SimpleNamespace(units=types.SimpleNamespace(source=[0], target=target))
         for t in toks:
-            qa.append(t); qb.append(t); target.append(t)
+            q.append(t)
+            target.append(t)
             while True:
-                if len(qa) == 0:
+                if len(q) == 0:
                     break
-                a = ref.units_to_segment(qa, states)
-                b = merger(qb, len(target), max_len)
-                assert a == b and qa.value == qb.value, (case, toks, a, b)
+                a = segment(q, states, target, max_len)
+                steps.append([a, list(q.value)])
                 if a is None or isinstance(a, str) or mine.DEFAULT_EOS in a:
                     break
-            if len(qa) and (qa[0] == 2 or (a is not None and mine.DEFAULT_EOS in a)):
+            if len(q) and (q[0] == 2 or (a is not None and mine.DEFAULT_EOS in a)):
                 break
+        cases.append({"units": toks, "max_len": max_len, "steps": steps})
+    return cases
+
+
+def _g22():
+    """the reference agent's side of the two tests below, recorded by tests/golden/gen_golden_agent_surface.py"""
+    with open(G22) as f:
+        return json.load(f)
+
+
+def _jsonable(x):
+    return json.loads(json.dumps(x))
+
+
+@pytest.mark.parametrize("force_finish", [False, True])
+def test_same_calls_as_the_reference_agent(force_finish):
+    from simulst_amd import simuleval_agent as mine
+    from simulst_amd.harness import Dictionary
+    ref = _g22()["calls"][str(force_finish)]
+    model = RecordingModel(call_script(force_finish))
+    args = argparse.Namespace(force_finish=force_finish, max_len_a=1, max_len_b=0)
+    agent = mine.FairseqSimulSTAgent(args, model=model, tgt_dict=Dictionary(SYMBOLS, 2))
+    seen_mine = _drive(agent, model, FEED)
+    seen_ref, trace_ref = ref["seen"], ref["trace"]
+    assert len(trace_ref) > 15 and any(t[0] == "decoder.clear_cache" for t in trace_ref) == force_finish
+    assert _jsonable(model.trace) == trace_ref
+    assert _jsonable(seen_mine) == seen_ref
+
+
+def test_word_merger_equals_reference_method_on_random_queues():
+    """Beyond the g15 fixture: random unit streams, incl. force-finish Nones and EOS, replayed through the table-driven
+    WordMerger and compared, call by call, with what the reference's units_to_segment returned on the same streams."""
+    from simulst_amd.harness import WordMerger
+
+    def make_segment(tgt):
+        merger = WordMerger(tgt)
+        return lambda q, states, target, max_len: merger(q, len(target), max_len)
+    ref = _g22()["word_merger"]
+    got = _jsonable(merger_steps(make_segment))
+    assert len(got) == len(ref) == 60
+    for c_got, c_ref in zip(got, ref):
+        assert c_got == c_ref, (c_got, c_ref)
 
 
 # ----------------------------------------------------------------------------------------------------------- GPU

@@ -85,3 +85,24 @@ def test_class_model_follows_the_launches_that_run():
     assert bench.class_work("dec_vocab_chain", cfg, Bs, dims, fl, "bf16", opts={"chains": True, "vsplit": 0, "embed_qkv": True}) is None
     # every modelled class is positive and the encoder class is the flop sum
     assert bench.class_work("linear", cfg, Bs, dims, fl, "bf16", opts=on) == ("mfma", fl["conv"] + fl["enc_linear"] + fl["dec_cross_kv"], None)
+
+
+def test_dump_outputs_writes_float_arrays_under_the_limit(tmp_path):
+    """--dump-outputs: every hypothesis row as float32 while it fits, a fixed seeded sample of rows (same in every run) when not."""
+    import numpy as np
+    import torch
+    hyp = torch.randint(0, 8000, (640, 110), generator=torch.Generator().manual_seed(1))
+    shapes = bench.dump_outputs(hyp, str(tmp_path / "all"))
+    assert shapes == {"hypotheses.npy": [640, 110], "hypotheses_rows.npy": [640]}
+    h = np.load(tmp_path / "all" / "hypotheses.npy")
+    assert h.dtype == np.float32 and np.array_equal(h, hyp.numpy().astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "all" / "hypotheses_rows.npy"), np.arange(640, dtype=np.float64))
+    limit = 100 * (4 * 110 + 8)
+    for d in ("a", "b"):
+        bench.dump_outputs(hyp, str(tmp_path / d), limit=limit)
+    rows = [np.load(tmp_path / d / "hypotheses_rows.npy") for d in ("a", "b")]
+    h = np.load(tmp_path / "a" / "hypotheses.npy")
+    assert rows[0].dtype == np.float64 and np.array_equal(rows[0], rows[1]) and len(rows[0]) == 100
+    assert np.all(np.diff(rows[0]) > 0)
+    assert np.array_equal(h, hyp.numpy()[rows[0].astype(np.int64)].astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= limit + 256

@@ -24,7 +24,6 @@ from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 KERNELS = (("dec_qkv_chain", r"dec_qkv_chain_kernel"), ("dec_embed_qkv_chain", r"dec_embed_qkv_chain_kernel"),
            ("dec_proj_chain", r"dec_proj_chain_kernel"), ("dec_ffn_chain", r"dec_ffn_chain_kernel"),

@@ -20,7 +20,6 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # as bench.py: lets 3 streams overlap
 import torch  # noqa: E402
 
 
