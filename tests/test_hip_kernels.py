@@ -245,6 +245,17 @@ def test_encoder_forward_full_size_vs_oracle(ops, dtype):
     for b in range(3):
         n = int(out["encoder_lengths"][b])
         close(y[:n, b], ref[:n, b], **tol)
+    if dtype == torch.bfloat16:
+        # the small-row path the agents take, to the bars of tests/test_hip_encoder_oracle.py: fp64 oracle, and an emulation
+        # of this path's bf16 stores (500 rows: two-launch feed-forward, fc2 adds its residual before the one rounding)
+        from test_hip_encoder_oracle import assert_bars, bar_stats, oracle_forward
+        ref64, pad = oracle_forward(w, ecfg, fb, L)
+        emu, _ = oracle_forward(w, ecfg, fb, L, emulate=False)
+        enc_len = (~pad).sum(1)
+        assert torch.equal(out["encoder_padding_mask"][0].cpu(), pad)
+        assert torch.equal(out["encoder_lengths"].cpu(), enc_len)
+        assert_bars(bar_stats(out["encoder_out_btd"], ref64, enc_len), bar_stats(emu, ref64, enc_len),
+                    "offline 3 utterances, 3 layers")
 
 
 # ------------------------------------------------------------------ scans
