@@ -602,6 +602,24 @@ typedef struct {
 int simulst_mma_decode(simulst_handle* h, const simulst_decoder_desc* d, const simulst_dec_layer* layers,
                        int64_t* tokens_io, int64_t* out_tokens, int32_t n_steps, int32_t mask_eos);
 
+/* Offline decode with hypotheses finalised at EOS (fairseq's SequenceGenerator, beam 1: a finished hypothesis leaves the
+ * batch): run between two chunks of simulst_mma_decode over the first `rows` slots of a lockstep batch of B rows.
+ * Slot i holds original row slot_row[i] (-1: dead), whose step cap is row_cap[i].  In order on the handle's stream:
+ *  1. every live slot's tokens of the chunk (chunk_tokens [n_steps][rows], simulst_mma_decode's out_tokens) go to
+ *     hyp[slot_row[i]][n_prev[i] - n_steps + s] ([B][U] int64, by original row) up to the row's first EOS (kept; eos_idx < 0:
+ *     never) or its cap; padding_idx behind that, and the finished slot leaves slot_row (-1);
+ *  2. a stable partition of the live slots of [0, rows): the k-th dead slot in front of the live count n_live takes the state
+ *     of the k-th live slot behind it -- self K/V [0, n_prev), cross K/V and soft keys [0, enc_len), pooled keys of complete
+ *     windows, head_step, head_read, n_prev, enc_len, enc_len_bh (may be NULL; [B][H]), slot_row, row_cap and
+ *     last_tokens ([B] int64: the tokens_io of the next chunk);
+ *  3. result ([4 + 2 B] int32 device scratch): [0] n_live, [1] rows_next = n_live rounded up to 16 rows, clamped into the
+ *     kernel class the decode loop runs a batch of B rows in (0 when no row is live), [2] pairs moved.
+ * The next chunk runs simulst_mma_decode with d->B = rows_next; the slots behind n_live ride along dead. */
+int simulst_mma_retire_rows(simulst_handle* h, const simulst_decoder_desc* d, const simulst_dec_layer* layers,
+                            const int64_t* chunk_tokens, int32_t n_steps, int32_t rows, int32_t B, int32_t* slot_row,
+                            int32_t* row_cap, int64_t* last_tokens, int64_t* hyp, int32_t U, int32_t* enc_len_bh,
+                            int32_t* result);
+
 /* BATCHED STREAMING decode steps (no counterpart in the reference, which asserts B == 1 when streaming,
  * models/s2t_emformer.py:200): n_iter policy()/predict() rounds for every row of a batch whose rows decide
  * READ / WRITE independently.  Per row and round: the layers run until one wants more source while the row is

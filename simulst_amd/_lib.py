@@ -149,6 +149,8 @@ SIGNATURES = {
     "simulst_greedy_argmax": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32],
     "simulst_mma_decode": [_vp, C.POINTER(DecoderDesc), C.POINTER(DecLayer), _vp, _vp, _i32, _i32],
     "simulst_mma_stream_steps": [_vp, C.POINTER(DecoderDesc), C.POINTER(DecLayer), _vp, C.POINTER(StreamCtl), _i32],
+    "simulst_mma_retire_rows": [_vp, C.POINTER(DecoderDesc), C.POINTER(DecLayer), _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32,
+                                _vp, _vp],
     "simulst_step_p_choose_padded": [_vp, _vp, _vp, _f32, _vp, _vp] + [_i32] * 8 + [_f32, _i32],
     "simulst_pool_keys": [_vp, _vp, _vp, _vp] + [_i32] * 9,
     "simulst_policy_cross_attention": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
@@ -267,6 +269,7 @@ class Handle:
                                    "(no CPU fallback)")
             stream_ptr = torch.cuda.current_stream().cuda_stream
         self._h = _vp()
+        self.stream_ptr = stream_ptr         # the stream every launch of this handle goes to (host read-backs wait on it alone)
         rc = self.lib.simulst_create(C.byref(self._h), _vp(stream_ptr))
         if rc != 0:
             raise RuntimeError(f"simulst_create failed: {rc}")
@@ -277,6 +280,7 @@ class Handle:
 
     def set_stream(self, stream_ptr):
         self.check(self.lib.simulst_set_stream(self._h, _vp(stream_ptr)), "simulst_set_stream")
+        self.stream_ptr = stream_ptr
 
     def check(self, rc, what):
         if rc != 0:

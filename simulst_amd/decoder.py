@@ -540,19 +540,7 @@ class MMADecoder:
         # the state (and with it every buffer address) is reused across batches of the same shape, so a
         # cached hipGraph of the step loop can be replayed; only the small per-batch fields are reset
         # s_cap / cap: round the state's capacities up so ragged workloads reuse a few cached states
-        key = (B, max(cap or 0, n_steps + 2), max(s_cap or 0, S, 1))
-        if not hasattr(self, "_offline_states"):
-            self._offline_states = {}
-        st = self._offline_states.get(key)
-        if st is None:
-            st = self._offline_states[key] = self.new_state(B, cap=key[1], S_cap=key[2])
-            st.tok_buf = torch.empty(B, device=self.device, dtype=torch.int64)
-        else:
-            for hs in st.head_step:
-                hs.zero_()
-            st.n_prev.zero_()
-            st.n_prev_host, st.enc_rows = 0, 0
-        st.online = False
+        st = self._offline_state(B, n_steps, S, s_cap, cap)
         self.append_encoder_out(st, enc_btd, enc_len)
         toks = st.tok_buf.fill_(cfg.eos)
         if fused:
@@ -565,6 +553,83 @@ class MMADecoder:
                                          mask_eos=mask_eos or s == 0, out=out[s])
                 self.commit(st)
         return out.t().contiguous(), st
+
+    def generate_offline(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, steps_per_row, *, stop_at_eos: bool = True,
+                         chunk: int = 8, s_cap: Optional[int] = None, cap: Optional[int] = None):
+        """Greedy offline decode with fairseq's SequenceGenerator semantics at beam 1 (eval/generate.py:187-209): a hypothesis is
+        final at its first EOS (kept) or at its own cap steps_per_row[b], and its row leaves the batch.  Rows need not be sorted.
+        The loop runs `chunk` steps of simulst_mma_decode over the first `rows` slots, then simulst_mma_retire_rows writes the
+        chunk's tokens into the hypotheses, moves the state of the live slots behind the live count into the holes the finished
+        ones left in front of it, and picks the next row count (whole 16-row tiles, inside the kernel class the full batch
+        started in); the two counts are read back on this handle's stream alone.  It ends when no row is live or the longest
+        cap is reached.  stop_at_eos=False: rows leave at their cap only (the tokens of greedy_offline_ragged).
+        Returns (tokens [B, U] int64 with padding_idx behind each row's end, lengths [B] int64 on the device,
+        stats {"steps": steps launched, "row_steps": rows x steps launched, "calls": decode calls, "rows": rows per call})."""
+        cfg = self.cfg
+        B, S, D = enc_btd.shape
+        caps = [int(x) for x in steps_per_row]
+        assert len(caps) == B and min(caps) >= 1, "one cap >= 1 per row"
+        U = max(caps)
+        st = self._offline_state(B, U, S, s_cap, cap)
+        self.append_encoder_out(st, enc_btd, enc_len)
+        st.enc_len = st.enc_len.clone()                      # the compaction permutes it: never the caller's tensor
+        toks = st.tok_buf.fill_(cfg.eos)
+        dev = self.device
+        if getattr(st, "slot_row", None) is None:
+            st.slot_row = torch.empty(B, device=dev, dtype=torch.int32)
+            st.row_cap = torch.empty(B, device=dev, dtype=torch.int32)
+            st.retire_result = torch.zeros(4 + 2 * B, device=dev, dtype=torch.int32)
+            st.retire_host = torch.zeros(4, dtype=torch.int32, pin_memory=True)
+            st.retire_event = torch.cuda.Event()
+        # the slot maps of this call: slot i holds row i; a previous call's compaction left its own permutation behind
+        st.slot_row.copy_(torch.arange(B, dtype=torch.int32), non_blocking=True)
+        st.row_cap.copy_(torch.tensor(caps, dtype=torch.int32), non_blocking=True)
+        hyp = torch.full((B, U), cfg.padding_idx, device=dev, dtype=torch.int64)
+        import ctypes as C
+        h = self.ops.h
+        sp = getattr(h, "stream_ptr", None)
+        stream = torch.cuda.ExternalStream(sp, device=dev) if sp else torch.cuda.default_stream(dev)
+        rows, s, calls, row_steps, rows_log = B, 0, 0, 0, []
+        while s < U and rows > 0:
+            e = min(U, s + chunk)
+            if U - e < chunk // 2:                           # no tiny last call (the schedule of greedy_offline_ragged)
+                e = U
+            o = self.decode_steps(st, toks, e - s, False, rows=rows)
+            calls, row_steps = calls + 1, row_steps + rows * (e - s)
+            rows_log.append(rows)
+            d = self._decoder_desc(st, st.n_prev_host)
+            if not stop_at_eos:
+                d.eos_idx = -1
+            h.check(self.ops.lib.simulst_mma_retire_rows(h.ptr, C.byref(d), st.layer_structs, o.data_ptr(), e - s, rows, B,
+                                                         st.slot_row.data_ptr(), st.row_cap.data_ptr(), toks.data_ptr(),
+                                                         hyp.data_ptr(), U, st.enc_len_bh.data_ptr(), st.retire_result.data_ptr()),
+                    "simulst_mma_retire_rows")
+            with torch.cuda.stream(stream):
+                st.retire_host.copy_(st.retire_result[:4], non_blocking=True)
+                st.retire_event.record(stream)
+            st.retire_event.synchronize()
+            rows = int(st.retire_host[1])
+            s = e
+        lengths = (hyp != cfg.padding_idx).sum(1)
+        return hyp, lengths, {"steps": s, "row_steps": row_steps, "calls": calls, "rows": rows_log}
+
+    def _offline_state(self, B: int, U: int, S: int, s_cap: Optional[int], cap: Optional[int]) -> DecoderState:
+        """the cached offline state of this shape (every buffer address is reused, so a cached hipGraph of the step loop can be
+        replayed), its per-batch fields reset"""
+        key = (B, max(cap or 0, U + 2), max(s_cap or 0, S, 1))
+        if not hasattr(self, "_offline_states"):
+            self._offline_states = {}
+        st = self._offline_states.get(key)
+        if st is None:
+            st = self._offline_states[key] = self.new_state(B, cap=key[1], S_cap=key[2])
+            st.tok_buf = torch.empty(B, device=self.device, dtype=torch.int64)
+        else:
+            for hs in st.head_step:
+                hs.zero_()
+            st.n_prev.zero_()
+            st.n_prev_host, st.enc_rows = 0, 0
+        st.online = False
+        return st
 
     def greedy_offline_ragged(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, steps_per_row, mask_eos: bool = False,
                               s_cap: Optional[int] = None, cap: Optional[int] = None, chunk: int = 8):
@@ -580,19 +645,7 @@ class MMADecoder:
         steps = [int(x) for x in steps_per_row]
         assert len(steps) == B and all(steps[i] >= steps[i + 1] for i in range(B - 1)), "rows must come longest first"
         U = steps[0]
-        key = (B, max(cap or 0, U + 2), max(s_cap or 0, S, 1))
-        if not hasattr(self, "_offline_states"):
-            self._offline_states = {}
-        st = self._offline_states.get(key)
-        if st is None:
-            st = self._offline_states[key] = self.new_state(B, cap=key[1], S_cap=key[2])
-            st.tok_buf = torch.empty(B, device=self.device, dtype=torch.int64)
-        else:
-            for hs in st.head_step:
-                hs.zero_()
-            st.n_prev.zero_()
-            st.n_prev_host, st.enc_rows = 0, 0
-        st.online = False
+        st = self._offline_state(B, U, S, s_cap, cap)
         self.append_encoder_out(st, enc_btd, enc_len)
         toks = st.tok_buf.fill_(cfg.eos)
         out = torch.full((B, U), cfg.padding_idx, device=self.device, dtype=torch.int64)

@@ -123,13 +123,19 @@ def make_batch(idx: Sequence[int], lengths: Sequence[int], device, dtype, fbank_
     return fb.to(device=device, dtype=dtype), L.to(device), L, max_steps(Tmax), Tpad
 
 
-def decode_batch(model, batch, retire=True):
+def decode_batch(model, batch, retire=True, stop_at_eos=False):
     """One ragged launch sequence (rows longest first).  retire: rows leave the step loop at their OWN cap int(0.1 T + 10)
     (decoder.greedy_offline_ragged; the reference's generator shrinks its batch the same way, eval/generate.py:187-209); False: every
-    row rides to the cap of the longest member (rounds 2-5).  The hypotheses after trim_hypotheses are the same either way."""
+    row rides to the cap of the longest member (rounds 2-5).  The hypotheses after trim_hypotheses are the same either way.
+    stop_at_eos: rows also leave at their first EOS (decoder.generate_offline: finished rows are compacted out of the batch on the
+    device); the tokens are then padding_idx behind each hypothesis' end, its first EOS included."""
     fb, Ld, L, steps, Tpad = batch
     enc = model.encoder.forward(fb, Ld)
     kw = dict(s_cap=Tpad // 4 + 1, cap=(steps + 2 + 31) // 32 * 32)
+    if stop_at_eos:
+        per_row = [max_steps(int(t)) for t in L.tolist()]
+        toks, _, _ = model.decoder.generate_offline(enc["encoder_out_btd"], enc["encoder_lengths"], per_row, **kw)
+        return toks
     if retire and not os.environ.get("SIMULST_NO_RETIRE"):             # (the switch: A/B measurements of tools/eval_sharded.py)
         per_row = [max_steps(int(t)) for t in L.tolist()]
         if all(per_row[i] >= per_row[i + 1] for i in range(len(per_row) - 1)) and per_row[-1] < per_row[0]:

@@ -63,6 +63,9 @@ def main(argv=None, collect=None):
                     help="--plan work: cut the sequences by the cost of RETIRING rows (floor x steps of the longest + the rows' own steps + the "
                          "encoder's padding).  Measured on the rank shard: 6 sequences of up to 1024 rows instead of 7, best pass 0.362 s "
                          "against 0.365 s, but half of the passes 10-20 %% slower (profiles/r06_config5_shard_*): off by default")
+    ap.add_argument("--stop-at-eos", dest="stop_at_eos", action="store_true",
+                    help="offline: a row also leaves its launch sequence at its first EOS (offline_eval.decode_batch(stop_at_eos=True): "
+                         "finished rows are compacted out of the batch on the device every 8 steps); off by default")
     ap.add_argument("--warmup-passes", type=int, default=0,
                     help="whole untimed passes over the shard before the timed ones (allocator pools of every launch-sequence shape, like "
                          "bench.py's warm-up steps); the default warm-up is one sequence per stream")
@@ -133,7 +136,7 @@ def main(argv=None, collect=None):
     outs = [None] * len(batches)
 
     def decode(m, b):
-        return decode_batch(m, b[1:])
+        return decode_batch(m, b[1:], stop_at_eos=args.stop_at_eos)
 
     import threading
     qlock = threading.Lock()
