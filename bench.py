@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decoded target tokens/sec of the streaming-ST hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,7 +21,9 @@ actually executed is what config.schedule reports.  The warm-up runs the launch 
 timed plan (same shapes), at least W steps of them.  Utterance batches shard across ranks with no
 data-path collective (weak scaling); the only RCCL traffic is the all_gather of hypotheses.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the headline (value, ms_per_step, timed_passes, config) and nothing else.  With --full, after the
+timed region, rank 0 also measures and checks the rest and the line carries these extra objects (full tables in bench_legs.json):
   roofline       -- the dominant kernel class by device time in an instrumented replay of the largest launch
                     sequence of the executed plan (HIP events on the handle's stream around every launch of each
                     class), with the other big class (HBM-bound attention / MFMA-bound encoder GEMMs) beside it
@@ -90,6 +92,10 @@ def parse_args(argv=None):
     ap.add_argument("--partition-phase-a", type=int, default=0, help="--partition: launch sequences encoded in the first, whole-chip phase (0: half)")
     ap.add_argument("--passes", type=int, default=3,
                     help="timed passes of the K-step plan; value = the MEDIAN pass, all of them are reported")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check everything beside the headline (roofline replays, CPU "
+                         "baseline and parity, the other configs' legs); off: the headline alone.  --no-cpu-baseline, --no-extra-configs, "
+                         "--extra-rows, --no-teacher-forced and --cpu-sample* only act with it")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the configs[1] streaming / configs[2] / configs[3] legs")
     ap.add_argument("--extra-rows", type=int, default=448, help="rows of the batched streaming runs of the extra legs")
     ap.add_argument("--no-teacher-forced", action="store_true", help="skip the teacher-forced bf16 audits of the configs[2] / configs[3] legs")
@@ -223,6 +229,7 @@ def _leg_summary(leg):
 
 def compact_line(full, legs_path=LEGS_FILE):
     """The ONE stdout line of the contract from the full result: headline, `roofline`, `cpu_baseline` and one small object per leg.
+    A plain run's result has none of these: its line is the headline alone, and with legs_path None it names no side file.
     Pure function of `full` (tests/test_bench_line.py drives it on a canned result)."""
     head = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "ranks_seen", "per_rank_pass_ms_min_max")
@@ -250,7 +257,7 @@ def compact_line(full, legs_path=LEGS_FILE):
         if "class_ms_per_sequence" in r:
             ro["class_ms_per_sequence"] = r["class_ms_per_sequence"]
         out["roofline"] = ro
-    else:
+    elif "roofline" in full:
         out["roofline"] = None
     c = full.get("cpu_baseline")
     if isinstance(c, dict):
@@ -265,7 +272,7 @@ def compact_line(full, legs_path=LEGS_FILE):
         if "teacher_forced" in c:
             co["teacher_forced"] = c["teacher_forced"]
         out["cpu_baseline"] = co
-    else:
+    elif "cpu_baseline" in full:
         out["cpu_baseline"] = None
     legs = {}
     if "configs1_one_batch_of_64_alone" in full:
@@ -297,7 +304,8 @@ def compact_line(full, legs_path=LEGS_FILE):
         out["legs"] = legs
     if "average_lagging" in full:
         out["average_lagging"] = full["average_lagging"]
-    out["details"] = legs_path
+    if legs_path:
+        out["details"] = legs_path
     return out
 
 
@@ -506,10 +514,38 @@ def main(argv=None):
     roofline, cpu_base = None, None
     if args.timed_only:
         return
-    if rank == 0:
+    Bs = B * g_max                              # rows of the largest launch sequence (the instrumented one with --full)
+    sched = (f"{sum(plan)} batches of {B} as {len(plan)} launch sequence(s) of {sorted(set(plan), reverse=True)} stacked "
+             f"batches on {streams_used} HIP stream(s)" +
+             ("" if args.concurrency > 1 or args.no_pipeline else ", encoder(i+1) overlapped with decode(i)"))
+    out = {
+        "metric": "decoded tgt tokens/sec (Emformer encoder + wait-k=5 greedy decode, MuST-C en-de shape)",
+        "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+        "data": "synthetic N(0,1) fbank, one distinct utterance per decoded row (first batch: CPU generator seed 999 + utt_id, "
+                "the rest one device-generator draw seed 999 + rank); random-init weights seed 999",
+        "ranks_seen": (dist.get_world_size() if dist is not None else 1),
+        "per_rank_pass_ms_min_max": [[round(a * 1e3, 3), round(b * 1e3, 3)] for a, b in rank_spread] or None,
+        "timed_passes": {"n": len(pass_s), "ms": [round(x * 1e3, 3) for x in pass_s],
+                         "tokens_per_s_min_median_max": [round(tokens_per_step * args.steps / max(pass_s), 1), round(value, 1),
+                                                         round(tokens_per_step * args.steps / min(pass_s), 1)],
+                         "value_is": "the median pass; each pass = exactly K steps between barrier + synchronize"},
+        "config": {"workload": "configs[1]: Emformer enc (12L) + wait-k=5 dec (6L), 80x1000 fbank, "
+                               "batch 64/GPU, 110 forced greedy steps",
+                   "batch_per_gpu": B, "frames": T_FRAMES, "decode_steps": N_STEPS_DECODE,
+                   "input_dtype": (f"{args.dtype} fbank resident in HBM (the fp32 -> {args.dtype} cast of the synthetic draw is untimed; "
+                                   "SURVEY 8(d)'s fp32 fbank would add 0.16 MB of reads per utterance)") if args.dtype != "f32" else "f32",
+                   "tokens_per_step": tokens_per_step, "sharding": f"utterance-sharded x{world}",
+                   "plan_batches_per_sequence": plan, "co_scheduled_batches": g_max, "streams": streams_used,
+                   "rows_per_sequence": Bs, "warmup_steps_executed": warm_done,
+                   "warmup_note": "the warm-up repeats the timed plan's own launch sequences until W steps AND "
+                                  f"{args.min_warmup_seconds} s have passed (a cold MI355X ramps its clocks for ~0.5 s)",
+                   "schedule": sched},
+    }
+    if rank == 0 and args.full:
         # ---- instrumented replay of the LARGEST launch sequence of the executed plan: HIP events around every launch
         h = model.ops.h
-        Bs = B * g_max                          # rows of the instrumented launch sequence
         fb_seq, L_seq = fb_all[:Bs], L_all[:Bs]
         torch.cuda.synchronize()
         serial_s = float("inf")
@@ -747,33 +783,7 @@ def main(argv=None):
                     log(f"teacher-forced wait-k audit: {cpu_base['teacher_forced']}")
                 except Exception as e:
                     cpu_base["teacher_forced"] = {"error": repr(e)[:160]}
-        sched = (f"{sum(plan)} batches of {B} as {len(plan)} launch sequence(s) of {sorted(set(plan), reverse=True)} stacked "
-                 f"batches on {streams_used} HIP stream(s)" +
-                 ("" if args.concurrency > 1 or args.no_pipeline else ", encoder(i+1) overlapped with decode(i)"))
-        out = {
-            "metric": "decoded tgt tokens/sec (Emformer encoder + wait-k=5 greedy decode, MuST-C en-de shape)",
-            "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-            "data": "synthetic N(0,1) fbank, one distinct utterance per decoded row (first batch: CPU generator seed 999 + utt_id, "
-                    "the rest one device-generator draw seed 999 + rank); random-init weights seed 999",
-            "ranks_seen": (dist.get_world_size() if dist is not None else 1),
-            "per_rank_pass_ms_min_max": [[round(a * 1e3, 3), round(b * 1e3, 3)] for a, b in rank_spread] or None,
-            "timed_passes": {"n": len(pass_s), "ms": [round(x * 1e3, 3) for x in pass_s],
-                             "tokens_per_s_min_median_max": [round(tokens_per_step * args.steps / max(pass_s), 1), round(value, 1),
-                                                             round(tokens_per_step * args.steps / min(pass_s), 1)],
-                             "value_is": "the median pass; each pass = exactly K steps between barrier + synchronize"},
-            "config": {"workload": "configs[1]: Emformer enc (12L) + wait-k=5 dec (6L), 80x1000 fbank, "
-                                   "batch 64/GPU, 110 forced greedy steps",
-                       "batch_per_gpu": B, "frames": T_FRAMES, "decode_steps": N_STEPS_DECODE,
-                       "input_dtype": (f"{args.dtype} fbank resident in HBM (the fp32 -> {args.dtype} cast of the synthetic draw is untimed; "
-                                       "SURVEY 8(d)'s fp32 fbank would add 0.16 MB of reads per utterance)") if args.dtype != "f32" else "f32",
-                       "tokens_per_step": tokens_per_step, "sharding": f"utterance-sharded x{world}",
-                       "plan_batches_per_sequence": plan, "co_scheduled_batches": g_max, "streams": streams_used,
-                       "rows_per_sequence": Bs, "warmup_steps_executed": warm_done,
-                       "warmup_note": "the warm-up repeats the timed plan's own launch sequences until W steps AND "
-                                      f"{args.min_warmup_seconds} s have passed (a cold MI355X ramps its clocks for ~0.5 s)",
-                       "schedule": sched},
+        out.update({
             "configs1_one_batch_of_64_alone": {"tokens_per_s": round(B * N_STEPS_DECODE / serial_s, 1),
                                                "ms_per_batch": round(serial_s * 1e3, 3),
                                                "frac_of_path_hbm_roofline":
@@ -781,7 +791,7 @@ def main(argv=None):
             "one_sequence_alone": {"rows": Bs, "tokens_per_s": round(Bs * N_STEPS_DECODE / group_s, 1),
                                    "ms_per_sequence": round(group_s * 1e3, 3)},
             "roofline": roofline, "cpu_baseline": cpu_base,
-        }
+        })
         out.update(extra)
         # the other half of BASELINE.json's metric ("decoded tgt tokens/sec + Average Lagging"): AL of the streamed runs of the
         # legs and whether READ / WRITE strings, tokens, delays and AL of the fp32 sample equal the CPU oracle's
@@ -797,6 +807,8 @@ def main(argv=None):
         if al:
             out["average_lagging"] = al
         print(emit(out), flush=True)
+    elif rank == 0:                             # a plain run: the headline is the whole result, no side file
+        print(json.dumps(compact_line(out, legs_path=None), separators=(",", ":")), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -106,3 +106,23 @@ def test_dump_outputs_writes_float_arrays_under_the_limit(tmp_path):
     assert np.all(np.diff(rows[0]) > 0)
     assert np.array_equal(h, hyp.numpy()[rows[0].astype(np.int64)].astype(np.float32))
     assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= limit + 256
+
+
+def test_plain_line_is_the_headline_alone():
+    """A run without --full measures the headline only: its line keeps the headline, the timed passes and the config, and
+    carries no roofline, CPU baseline, legs or pointer to a side file it did not write."""
+    full = json.load(open(os.path.join(ROOT, "profiles", "r04_d_bench_k20.json")))
+    head = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                 "vs_baseline", "dtype", "data", "ranks_seen", "per_rank_pass_ms_min_max", "timed_passes", "config")
+            if k in full}
+    out = json.loads(json.dumps(bench.compact_line(head, legs_path=None), separators=(",", ":")))
+    assert {k: out[k] for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")} == \
+        {k: full[k] for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")}
+    assert out["timed_passes"]["n"] == full["timed_passes"]["n"] and out["config"]["plan_batches_per_sequence"]
+    for k in ("roofline", "cpu_baseline", "legs", "average_lagging", "details"):
+        assert k not in out, k
+
+
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(["--full"]).full is True

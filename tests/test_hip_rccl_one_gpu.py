@@ -44,7 +44,7 @@ def _json_line(r):
 
 
 def test_bench_under_torchrun_with_the_rccl_branch_forced_equals_the_plain_run():
-    args = ["--gpus", "1", "--steps", "6", "--warmup", "6", "--no-extra-configs", "--no-cpu-baseline"]
+    args = ["--gpus", "1", "--steps", "6", "--warmup", "6", "--full", "--no-extra-configs", "--no-cpu-baseline"]
     bench = os.path.join(ROOT, "bench.py")
     plain = _json_line(subprocess.run([sys.executable, bench] + args, env=_env(False), capture_output=True, text=True, timeout=900))
     dist = _json_line(subprocess.run(_torchrun(bench, args), env=_env(True), capture_output=True, text=True, timeout=900))

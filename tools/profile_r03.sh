@@ -8,10 +8,10 @@ TAG=${1:-r03_b}
 R=$PWD
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err; echo "bench k20 rc=$?"
-timeout 900 python bench.py --no-extra-configs > $O/bench_default.json 2> $O/bench_default.err; echo "bench default rc=$?"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err; echo "bench k20 rc=$?"
+timeout 900 python bench.py --full --no-extra-configs > $O/bench_default.json 2> $O/bench_default.err; echo "bench default rc=$?"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_k20 -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra-configs > $O/bench_k20_under_rocprofv3.json 2> $O/trace_k20.err; echo "trace rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_k20 -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra-configs > $O/bench_k20_under_rocprofv3.json 2> $O/trace_k20.err; echo "trace rc=$?"
 for c in 2 3; do
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_stream_c$c -- python3 $R/tools/profile_streaming.py --config $c --rows 448 --repeats 2 > $O/stream_c$c.log 2>&1; echo "stream c$c rc=$?"
 done

@@ -19,7 +19,7 @@ call, and what the device computed is read back and compared number by number:
 
 Rows are `copies` copies of each utterance so that the batch is in the layer chains' domain (> 128 rows) and copies sit in
 different row tiles (they must agree bit for bit).  Everything is a function: tests/test_hip_teacher_forced.py asserts the bounds,
-bench.py reports one-number summaries, `python tools/teacher_forced_audit.py --out f.json` writes the full record.
+bench.py --full reports one-number summaries, `python tools/teacher_forced_audit.py --out f.json` writes the full record.
 """
 import argparse
 import json
