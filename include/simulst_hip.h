@@ -620,6 +620,51 @@ int simulst_mma_retire_rows(simulst_handle* h, const simulst_decoder_desc* d, co
                             int32_t* row_cap, int64_t* last_tokens, int64_t* hyp, int32_t U, int32_t* enc_len_bh,
                             int32_t* result);
 
+/* Beam search over offline MMA / wait-k decoding (csrc/beam.hip): fairseq's SequenceGenerator with search.BeamSearch at the
+ * reference's defaults (normalize_scores, min_len 1, no unk penalty, temperature 1, no prefix tokens or constraints).  Bs sentences
+ * of `beam` rows each (row r = s * beam + j, R = Bs * beam), K = 2 beam candidates per row.  Limits: 1 <= beam <= 16,
+ * 1 <= nbest <= beam, 2 beam <= V - 1.  Candidate order: descending score, equal scores to the lower flat index j * V + token.
+ * Every launch goes on the handle's stream, with no allocation and no synchronisation (capturable).
+ *
+ * simulst_beam_topk: per row of logits [R][V] fp32, lp = log_softmax(row) with lp[pad] = -inf, lp[eos] = -inf at step 0 and every
+ * entry but EOS -inf from step max_len[s] on; its top K (lp, token) pairs in candidate order -> cand_lp / cand_tok [R][K].  Rows of
+ * finished sentences (finished [Bs] int32, may be NULL) and, at step 0, rows j > 0 are skipped. */
+int simulst_beam_topk(simulst_handle* h, const float* logits, int32_t R, int32_t V, int32_t beam, int32_t step,
+                      const int32_t* max_len, const int32_t* finished, int32_t pad_idx, int32_t eos_idx, float* cand_lp,
+                      int32_t* cand_tok);
+
+/* simulst_beam_select: one wave per unfinished sentence.  The top K of cum[r] + cand_lp over the sentence's rows (step 0: row j = 0
+ * with cum 0).  Among the first beam, EOS candidates with a finite score are finalised while the sentence holds fewer than beam:
+ * slot fin_count[s] of the tables fin_step / fin_row (the parent row) / fin_raw (the score) / fin_score (score / (step + 1)^lenpen),
+ * [Bs][beam].  The sentence is finished (finished[s] = 1) when it holds beam of them or step == max_len[s].  Otherwise the first beam
+ * candidates that are not finalised EOS become rows j = 0 .. beam - 1: reorder[r] (parent row), next_tok[r] (int64, the next step's
+ * input), cum[r], and the back-pointers bp_parent / bp_token / bp_cum [L][R] at row `step`.  result [2] int32 (device scratch):
+ * [0] sentences unfinished after this step (cleared here), [1] += sentences short of beam finite non-EOS next rows (never under
+ * the masks above; fairseq's cands_to_ignore is not implemented). */
+int simulst_beam_select(simulst_handle* h, const float* cand_lp, const int32_t* cand_tok, int32_t Bs, int32_t beam, int32_t V,
+                        int32_t step, const int32_t* max_len, int32_t L, double lenpen, int32_t eos_idx, float* cum,
+                        int64_t* next_tok, int32_t* reorder, int32_t* bp_parent, int32_t* bp_token, float* bp_cum,
+                        int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_raw, int32_t* fin_count,
+                        int32_t* finished, int32_t* result);
+
+/* simulst_beam_reorder: row r of the second buffer set `dst` takes row reorder[r] of `src`, per layer: the self-attention K/V
+ * positions [0, n_prev) (k_cache / v_cache [R][H][cap][d]), head_step [R H] and head_read [R H] (when both sets carry it).  d gives
+ * R = d->B, H, D, n_layers, cap and dtype; only those fields of the simulst_dec_layer entries are read.  Rows of finished sentences
+ * (finished [Bs], may be NULL) keep their own head_step and copy no K/V.  The cross-attention buffers are the same for every row of
+ * a sentence and are not touched.  A reorder that leaves its sentence's block of beam rows is not performed (the row keeps its own
+ * state) and added to result [1] int32 (device scratch, cleared by the caller). */
+int simulst_beam_reorder(simulst_handle* h, const simulst_decoder_desc* d, const simulst_dec_layer* src, const simulst_dec_layer* dst,
+                         const int32_t* reorder, const int32_t* finished, int32_t beam, int32_t n_prev, int32_t* result);
+
+/* simulst_beam_backtrack: once, after the last step.  Per sentence its finalised hypotheses by descending fin_score (equal scores
+ * in finalisation order), the first nbest, walked back through the back-pointers: tokens [Bs][nbest][L] int64 (EOS included,
+ * pad_idx behind), lengths [Bs][nbest] int32, scores [Bs][nbest] fp32 and positional scores [Bs][nbest][L] fp32 (the differences
+ * of the cumulative scores along the path, 0 behind).  Slots no hypothesis reached: length 0, score -inf. */
+int simulst_beam_backtrack(simulst_handle* h, int32_t Bs, int32_t beam, int32_t nbest, int32_t L, const int32_t* bp_parent,
+                           const int32_t* bp_token, const float* bp_cum, const int32_t* fin_step, const int32_t* fin_row,
+                           const float* fin_score, const float* fin_raw, const int32_t* fin_count, int32_t pad_idx,
+                           int32_t eos_idx, int64_t* tokens, int32_t* lengths, float* scores, float* pos_scores);
+
 /* BATCHED STREAMING decode steps (no counterpart in the reference, which asserts B == 1 when streaming,
  * models/s2t_emformer.py:200): n_iter policy()/predict() rounds for every row of a batch whose rows decide
  * READ / WRITE independently.  Per row and round: the layers run until one wants more source while the row is

@@ -151,6 +151,10 @@ SIGNATURES = {
     "simulst_mma_stream_steps": [_vp, C.POINTER(DecoderDesc), C.POINTER(DecLayer), _vp, C.POINTER(StreamCtl), _i32],
     "simulst_mma_retire_rows": [_vp, C.POINTER(DecoderDesc), C.POINTER(DecLayer), _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32,
                                 _vp, _vp],
+    "simulst_beam_topk": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp],
+    "simulst_beam_select": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, C.c_double, _i32] + [_vp] * 13,
+    "simulst_beam_reorder": [_vp, C.POINTER(DecoderDesc), C.POINTER(DecLayer), C.POINTER(DecLayer), _vp, _vp, _i32, _i32, _vp],
+    "simulst_beam_backtrack": [_vp, _i32, _i32, _i32, _i32] + [_vp] * 8 + [_i32, _i32] + [_vp] * 4,
     "simulst_step_p_choose_padded": [_vp, _vp, _vp, _f32, _vp, _vp] + [_i32] * 8 + [_f32, _i32],
     "simulst_pool_keys": [_vp, _vp, _vp, _vp] + [_i32] * 9,
     "simulst_policy_cross_attention": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,

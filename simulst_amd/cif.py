@@ -422,6 +422,12 @@ class CIFTransformerModel(FairseqModelSurface):
                                            fused=fused)
         return toks, {"encoder": enc}
 
+    def generate(self, src_tokens, src_lengths, *, beam=5, lenpen=1.0, nbest=1, max_len_a=0.1, max_len_b=10):
+        """SimulSTModel.generate's surface.  Beam search over the position-synchronous CIF decoder is not implemented, so this raises
+        at every beam; generate_offline is the greedy decode of this model."""
+        raise NotImplementedError(f"beam search (beam {beam}) over the CIF decoder is not implemented; "
+                                  "generate_offline decodes it greedily")
+
 
 class CIFAgent:
     """agents/cif_agent.py: READ while cif_lengths <= len(hyp) and the source has not ended (:385-389),

@@ -613,15 +613,72 @@ class MMADecoder:
         lengths = (hyp != cfg.padding_idx).sum(1)
         return hyp, lengths, {"steps": s, "row_steps": row_steps, "calls": calls, "rows": rows_log}
 
-    def _offline_state(self, B: int, U: int, S: int, s_cap: Optional[int], cap: Optional[int]) -> DecoderState:
+    def beam_offline(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, max_len, *, beam: int, lenpen: float = 1.0, nbest: int = 1,
+                     chunk: int = 8, s_cap: Optional[int] = None):
+        """Beam search with fairseq's SequenceGenerator semantics (search.BeamSearch, normalize_scores; simulst_amd/beam.py) over
+        Bs sentences: enc_btd [Bs, S, D], enc_len [Bs], max_len an int or one cap per sentence (steps 0 .. max_len[s]: at most
+        max_len[s] tokens and EOS).  The decoder step is the per-op step() over Bs * beam lockstep rows (row s * beam + j) of an offline
+        state whose encoder output is repeated beam times; behind every selection the step is committed and simulst_beam_reorder
+        gathers each row's self-attention prefix and monotonic step from its parent row into the state's second buffer set, and the
+        two sets swap.  Returns (tokens [Bs, nbest, L] int64 with padding_idx behind each hypothesis, lengths [Bs, nbest] int32 (EOS
+        included), scores [Bs, nbest] fp32, positional scores [Bs, nbest, L] fp32, stats {"steps"}), on the device; L = max(max_len) + 1."""
+        from .beam import BeamSearch, check_args
+        cfg = self.cfg
+        Bs, S, D = enc_btd.shape
+        caps = [int(max_len)] * Bs if isinstance(max_len, int) else [int(x) for x in max_len]
+        assert len(caps) == Bs, "one cap per sentence"
+        check_args(beam, nbest, cfg.vocab)
+        R = Bs * beam
+        bs = BeamSearch(self.ops, caps, beam=beam, V=cfg.vocab, eos=cfg.eos, pad=cfg.padding_idx, lenpen=lenpen, nbest=nbest,
+                        device=self.device)
+        st = self._offline_state(R, bs.L, S, s_cap, None, cache="_beam_states")
+        if getattr(st, "alt", None) is None:
+            # the second buffer set of the reorder: self-attention K/V and head_step; the cross-attention buffers are per sentence
+            st.alt = {"k": [torch.zeros_like(t) for t in st.k_cache], "v": [torch.zeros_like(t) for t in st.v_cache],
+                      "hs": [torch.zeros_like(t) for t in st.head_step]}
+        for hs in st.alt["hs"]:
+            hs.zero_()
+        self.append_encoder_out(st, enc_btd.repeat_interleave(beam, 0), enc_len.to(self.device).repeat_interleave(beam))
+        cap0 = st.cap
+        desc = _lib.DecoderDesc()
+        desc.B, desc.D, desc.H, desc.n_layers, desc.cap = R, cfg.embed_dim, cfg.num_heads, cfg.decoder_layers, st.cap
+        desc.dtype = _lib.F32 if self.dtype == torch.float32 else _lib.BF16
+
+        def layer_structs(k, v, hs):
+            arr = (_lib.DecLayer * cfg.decoder_layers)()
+            for l in range(cfg.decoder_layers):
+                arr[l].k_cache, arr[l].v_cache, arr[l].head_step = k[l].data_ptr(), v[l].data_ptr(), hs[l].data_ptr()
+            return arr
+
+        sets = [layer_structs(st.k_cache, st.v_cache, st.head_step), layer_structs(st.alt["k"], st.alt["v"], st.alt["hs"])]
+
+        def logits_fn(t, toks):
+            logits, _ = self.step(st, toks)
+            return logits
+
+        def after_select(t):
+            self.commit(st)
+            assert st.cap == cap0, "beam state outgrew its capacity"
+            self.ops.beam_reorder(desc, sets[0], sets[1], bs.reorder, bs.finished, bs.result[2:3], beam=beam, n_prev=st.n_prev_host)
+            st.k_cache, st.alt["k"] = st.alt["k"], st.k_cache
+            st.v_cache, st.alt["v"] = st.alt["v"], st.v_cache
+            st.head_step, st.alt["hs"] = st.alt["hs"], st.head_step
+            sets.reverse()
+
+        tokens, lengths, scores, pos = bs.run(logits_fn, after_select, chunk=chunk)
+        return tokens, lengths, scores, pos, {"steps": bs.steps}
+
+    def _offline_state(self, B: int, U: int, S: int, s_cap: Optional[int], cap: Optional[int],
+                       cache: str = "_offline_states") -> DecoderState:
         """the cached offline state of this shape (every buffer address is reused, so a cached hipGraph of the step loop can be
-        replayed), its per-batch fields reset"""
+        replayed), its per-batch fields reset.  Beam search keeps its states apart (cache="_beam_states"): it swaps their
+        self-attention buffers, which the device decode loop's cached layer descriptors would not follow."""
         key = (B, max(cap or 0, U + 2), max(s_cap or 0, S, 1))
-        if not hasattr(self, "_offline_states"):
-            self._offline_states = {}
-        st = self._offline_states.get(key)
+        if not hasattr(self, cache):
+            setattr(self, cache, {})
+        st = getattr(self, cache).get(key)
         if st is None:
-            st = self._offline_states[key] = self.new_state(B, cap=key[1], S_cap=key[2])
+            st = getattr(self, cache)[key] = self.new_state(B, cap=key[1], S_cap=key[2])
             st.tok_buf = torch.empty(B, device=self.device, dtype=torch.int64)
         else:
             for hs in st.head_step:

@@ -134,6 +134,19 @@ class SimulSTModel(FairseqModelSurface):
                                                fused=fused)
         return toks, {"encoder": enc, "state": st}
 
+    def generate(self, src_tokens, src_lengths, *, beam=5, lenpen=1.0, nbest=1, max_len_a=0.1, max_len_b=10):
+        """task.inference_step as eval/generate.py:200-275 calls it with --beam / --lenpen / --nbest: fairseq's SequenceGenerator
+        with search.BeamSearch (simulst_amd/beam.py).  Sentence s decodes at most max_len[s] = min(int(max_len_a T_s + max_len_b),
+        max_target_positions - 1) tokens and EOS, T_s its own frame count.  Returns per sentence a list of at most nbest
+        {"tokens" (EOS included), "score", "positional_scores", "alignment": None, "attention": None}, best first."""
+        from .beam import hypotheses
+        enc = self.encoder.forward(src_tokens, src_lengths)
+        lens = [int(t) for t in torch.as_tensor(src_lengths).tolist()]
+        max_len = [min(int(max_len_a * t + max_len_b), self.cfg.max_target_positions - 1) for t in lens]
+        toks, lengths, scores, pos, _ = self.decoder.beam_offline(enc["encoder_out_btd"], enc["encoder_lengths"], max_len, beam=beam,
+                                                                  lenpen=lenpen, nbest=nbest)
+        return hypotheses(toks, lengths, scores, pos)
+
 
 @register_model("mma_model")
 class MMAModel(SimulSTModel):

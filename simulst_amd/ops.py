@@ -445,3 +445,31 @@ class Ops:
         self.h.check(self.lib.simulst_greedy_argmax(self.h.ptr, _p(logits), _p(eos_bias), _p(out), B, V, pad_idx,
                                                     eos_idx, int(mask_eos)), "simulst_greedy_argmax")
         return out
+
+    # ------------------------------------------------------------------ beam search (csrc/beam.hip)
+    def beam_topk(self, logits, max_len, finished, cand_lp, cand_tok, *, beam, step, pad_idx, eos_idx):
+        _chk_contig(logits, max_len, finished, cand_lp, cand_tok)
+        R, V = logits.shape
+        self.h.check(self.lib.simulst_beam_topk(self.h.ptr, _p(logits), R, V, beam, step, _p(max_len), _p(finished), pad_idx, eos_idx,
+                                                _p(cand_lp), _p(cand_tok)), "simulst_beam_topk")
+
+    def beam_select(self, cand_lp, cand_tok, max_len, *, beam, V, step, lenpen, eos_idx, cum, next_tok, reorder, bp_parent, bp_token,
+                    bp_cum, fin_step, fin_row, fin_score, fin_raw, fin_count, finished, result):
+        Bs, L = max_len.numel(), bp_parent.shape[0]
+        self.h.check(self.lib.simulst_beam_select(self.h.ptr, _p(cand_lp), _p(cand_tok), Bs, beam, V, step, _p(max_len), L, float(lenpen),
+                                                  eos_idx, _p(cum), _p(next_tok), _p(reorder), _p(bp_parent), _p(bp_token), _p(bp_cum),
+                                                  _p(fin_step), _p(fin_row), _p(fin_score), _p(fin_raw), _p(fin_count), _p(finished),
+                                                  _p(result)), "simulst_beam_select")
+
+    def beam_reorder(self, desc, src_layers, dst_layers, reorder, finished, result, *, beam, n_prev):
+        """desc: a _lib.DecoderDesc with B (rows), D, H, n_layers, cap and dtype set; src_layers / dst_layers: _lib.DecLayer arrays
+        whose k_cache, v_cache, head_step (and head_read) point at the two buffer sets"""
+        self.h.check(self.lib.simulst_beam_reorder(self.h.ptr, C.byref(desc), src_layers, dst_layers, _p(reorder), _p(finished), beam,
+                                                   n_prev, _p(result)), "simulst_beam_reorder")
+
+    def beam_backtrack(self, *, beam, nbest, bp_parent, bp_token, bp_cum, fin_step, fin_row, fin_score, fin_raw, fin_count, pad_idx,
+                       eos_idx, tokens, lengths, scores, pos_scores):
+        Bs, L = fin_count.numel(), bp_parent.shape[0]
+        self.h.check(self.lib.simulst_beam_backtrack(self.h.ptr, Bs, beam, nbest, L, _p(bp_parent), _p(bp_token), _p(bp_cum), _p(fin_step),
+                                                     _p(fin_row), _p(fin_score), _p(fin_raw), _p(fin_count), pad_idx, eos_idx,
+                                                     _p(tokens), _p(lengths), _p(scores), _p(pos_scores)), "simulst_beam_backtrack")

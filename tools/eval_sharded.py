@@ -66,6 +66,10 @@ def main(argv=None, collect=None):
     ap.add_argument("--stop-at-eos", dest="stop_at_eos", action="store_true",
                     help="offline: a row also leaves its launch sequence at its first EOS (offline_eval.decode_batch(stop_at_eos=True): "
                          "finished rows are compacted out of the batch on the device every 8 steps); off by default")
+    ap.add_argument("--beam", type=int, default=1,
+                    help="offline: beam search of this width (offline_eval.decode_batch(beam=N), fairseq's --beam; the best hypothesis "
+                         "is kept, EOS included); 1: the greedy paths")
+    ap.add_argument("--lenpen", type=float, default=1.0, help="offline beam search: length penalty (fairseq's --lenpen)")
     ap.add_argument("--warmup-passes", type=int, default=0,
                     help="whole untimed passes over the shard before the timed ones (allocator pools of every launch-sequence shape, like "
                          "bench.py's warm-up steps); the default warm-up is one sequence per stream")
@@ -115,7 +119,7 @@ def main(argv=None, collect=None):
         for l in range(cfg.decoder_layers):
             weights[f"decoder.layers.{l}.encoder_attn.q_proj.weight"] *= 8
     model = SimulSTModel(cfg, weights, device=dev, dtype=dtype)
-    width = int(0.1 * 3000 + 10)
+    width = int(0.1 * 3000 + 10) + (1 if args.beam > 1 and not args.streaming else 0)    # beam: the cap's tokens and EOS
     # ---- this rank's launch sequences: neighbours in length, sizes balanced over the streams; the synthetic fbank is
     #      resident in HBM before the clock starts (as in bench.py)
     from simulst_amd.model import ConcurrentOffline
@@ -136,7 +140,7 @@ def main(argv=None, collect=None):
     outs = [None] * len(batches)
 
     def decode(m, b):
-        return decode_batch(m, b[1:], stop_at_eos=args.stop_at_eos)
+        return decode_batch(m, b[1:], stop_at_eos=args.stop_at_eos, beam=args.beam, lenpen=args.lenpen)
 
     import threading
     qlock = threading.Lock()
@@ -180,9 +184,9 @@ def main(argv=None, collect=None):
         n_tokens = 0
         for (idx, fb, Ld, L, steps, Tpad), toks in zip(batches, outs):     # hypotheses: first EOS or the length cap
             toks = toks.cpu()
-            n_b = trim_hypotheses(toks, L, cfg.eos)
+            n_b = (toks != cfg.padding_idx).sum(1) if args.beam > 1 else trim_hypotheses(toks, L, cfg.eos)
             pad = torch.full((len(idx), width), cfg.padding_idx, dtype=torch.int64)
-            pad[:, :steps] = toks
+            pad[:, :toks.size(1)] = toks
             ids += idx
             ntok.append(n_b)
             toks_all.append(pad)
