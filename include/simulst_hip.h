@@ -58,9 +58,11 @@ enum {
 };
 
 /* monotonic attention flavours (modules/__init__.py:11-16 registry names minus the
- * _fixed_pre_decision suffix, which is the `ratio` argument) */
+ * _fixed_pre_decision suffix, which is the `ratio` argument), and FULL: the plain encoder-decoder attention of
+ * fairseq's TransformerDecoder (the s2t_emformer model, models/s2t_emformer.py:297-379): softmax over every valid
+ * key, no policy, no step search.  FULL is not a simultaneous policy: the streaming and p_choose entry points refuse it. */
 enum { SIMULST_ATTN_HARD = 0, SIMULST_ATTN_INFINITE_LOOKBACK = 1, SIMULST_ATTN_WAITK = 2,
-       SIMULST_ATTN_CHUNKWISE = 3 };
+       SIMULST_ATTN_CHUNKWISE = 3, SIMULST_ATTN_FULL = 4 };
 
 /* kernel classes for simulst_timer_* (roofline accounting in bench.py) */
 enum { SIMULST_K_LINEAR = 0, SIMULST_K_LAYERNORM = 1, SIMULST_K_EMF_ATTN = 2, SIMULST_K_CONV_POS = 3,
@@ -495,6 +497,8 @@ int simulst_decoder_self_attention(simulst_handle* h, const void* qkv, void* k_c
  *   HARD : ctx = Vc[clamp(step)] (zero if !mass_preservation && step == len)
  *   soft : ctx = softmax_{s <= step}(q.Kc[s]) Vc, zero if step == 0  (CHUNKWISE == INFINITE_LOOKBACK at
  *          inference: the reference's inference softmax ignores the chunk size, :278-293)
+ *   FULL : ctx = softmax_{s < key_len[b]}(q.Kc[s]) Vc (a 1-row source attends to its one key); `step` is not read
+ *          and may be NULL, beta (if given) holds the softmax weights
  * Replaces modules/monotonic_multihead_attention.py:278-297,401-409. */
 int simulst_decoder_cross_attention(simulst_handle* h, const void* q, const void* Kc, const void* Vc,
                                     const int64_t* step, const int32_t* key_len, void* ctx, float* beta,
@@ -538,7 +542,10 @@ int simulst_ctc_best_alignment(simulst_handle* h, const float* log_probs, int64_
  * eval/generate.py:187-209 ('online' unset => never READs, models/mma_model.py:191-193); with
  * n_steps == 1 it is one policy()/predict() pair of agents/default_agent.py:378-424 after which the
  * caller inspects head_read.  Pointers per layer in simulst_dec_layer, shared ones in
- * simulst_decoder_desc; all device memory is caller-owned. */
+ * simulst_decoder_desc; all device memory is caller-owned.
+ * attn_type SIMULST_ATTN_FULL (offline encoder-decoder attention): the policy is skipped, every layer attends over
+ * all enc_len[b] rows; head_step / head_read are neither read nor written (they must still be valid buffers: the
+ * retire and beam-reorder calls move them), c_wq_soft is unused and Kmono / Ksoft may be the same K buffer. */
 typedef struct {
   const void* wqkv; const float* bqkv;           /* self-attention [3D][D] (q|k|v) */
   const void* wo; const float* bo;
@@ -877,7 +884,8 @@ int simulst_pool_keys(simulst_handle* h, const void* Kmono, float* Kpool, const 
 
 /* policy + cross-attention of one layer for one step in ONE launch (simulst_step_p_choose +
  * simulst_mma_step_search + simulst_decoder_cross_attention, same results). qm/qs: monotonic / soft
- * queries [B][D] (qm unused for WAITK, qs unused for HARD). */
+ * queries [B][D] (qm unused for WAITK and FULL, qs unused for HARD).  FULL: no policy, ctx = softmax over
+ * the key_len[b] keys of Ksoft; tgt_idx and Kmono may be NULL, head_step / head_read are not touched (may be NULL). */
 int simulst_policy_cross_attention(simulst_handle* h, const void* qm, const void* qs, const void* Kmono,
                                    const void* Ksoft, const void* Vc, float energy_bias, const int32_t* key_len,
                                    const int32_t* tgt_idx, int64_t* head_step, uint8_t* head_read, void* ctx,

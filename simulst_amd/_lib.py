@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("SIMULST_LIB_PATH") or os.path.join(_HERE, "libsimulst
 
 F32, BF16 = 0, 1
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_GLU, EPI_EMF_OUT, EPI_BIAS_F32OUT, EPI_BIAS_RES_GELU = range(7)
-ATTN_HARD, ATTN_INFINITE_LOOKBACK, ATTN_WAITK, ATTN_CHUNKWISE = range(4)
+ATTN_HARD, ATTN_INFINITE_LOOKBACK, ATTN_WAITK, ATTN_CHUNKWISE, ATTN_FULL = range(5)
 (K_LINEAR, K_LAYERNORM, K_EMF_ATTN, K_CONV_POS, K_DEC_SELF_ATTN, K_DEC_CROSS_ATTN, K_SCAN, K_ARGMAX,
  K_MISC, K_LINEAR_SKINNY, K_LINEAR_TILE64, K_DEC_QKV_CHAIN, K_DEC_PROJ_CHAIN, K_DEC_FFN_CHAIN, K_DEC_ATTN_CHAIN,
  K_DEC_VOCAB_CHAIN, K_COUNT) = range(17)
@@ -26,7 +26,7 @@ KERNEL_CLASS_NAMES = ["linear", "layernorm", "emformer_attention", "conv_pos", "
                       "dec_qkv_chain", "dec_proj_chain", "dec_ffn_chain", "dec_attn_proj_chain", "dec_vocab_chain"]
 
 ATTN_ENUM = {"hard_aligned": ATTN_HARD, "infinite_lookback": ATTN_INFINITE_LOOKBACK,
-             "waitk": ATTN_WAITK, "chunkwise": ATTN_CHUNKWISE}
+             "waitk": ATTN_WAITK, "chunkwise": ATTN_CHUNKWISE, "full": ATTN_FULL}
 
 
 class LinearDesc(C.Structure):

@@ -50,6 +50,8 @@ class States:
 
 class FairseqSimulSTAgent:
     def __init__(self, model, max_len_a: float = 1, max_len_b: int = 0, force_finish: bool = False):
+        from .model import refuse_offline_model
+        refuse_offline_model(model, type(self).__name__)
         self.model = model
         enc = model.encoder
         # agents/default_agent.py:157-175

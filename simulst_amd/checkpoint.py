@@ -23,7 +23,7 @@ from typing import Dict, Iterable, List, Mapping, Optional
 
 import torch
 
-from .config import ModelConfig, cif_transformer_s, mma_model_s
+from .config import ModelConfig, cif_transformer_s, mma_model_s, s2t_emformer_s
 from .weights import init_model
 
 
@@ -32,7 +32,7 @@ def config_from_args(args: Mapping) -> ModelConfig:
     defaults of s2t_emformer_s / mma_model_s / cif_transformer_s filling what is absent."""
     g = args.get
     arch = g("arch", "mma_model_s")
-    base = cif_transformer_s() if arch.startswith("cif") else mma_model_s()
+    base = cif_transformer_s() if arch.startswith("cif") else s2t_emformer_s() if arch.startswith("s2t_emformer") else mma_model_s()
     kw = {}
     names = {"conv_channels": "conv_channels", "encoder_embed_dim": "embed_dim", "encoder_ffn_embed_dim": "ffn_dim",
              "encoder_attention_heads": "num_heads", "encoder_layers": "encoder_layers",
@@ -56,7 +56,10 @@ def config_from_args(args: Mapping) -> ModelConfig:
         kw["conv_kernel_sizes"] = tuple(int(k) for k in str(g("conv_kernel_sizes")).split(","))
     if arch.startswith("mma") and g("mass_preservation") is None:
         kw["mass_preservation"] = False          # the arch's own default (models/mma_model.py:265), not exp/2-mma.sh's
-    if g("waitk_testtime") is not None:          # inference lagging overrides the training one (:504-506)
+    if base.model == "s2t_emformer":             # a plain TransformerDecoder: no policy flags apply
+        for k in ("simul_attn_type", "waitk_lagging", "mass_preservation", "energy_bias"):
+            kw.pop(k, None)
+    if g("waitk_testtime") is not None and base.model != "s2t_emformer":          # inference lagging overrides the training one (:504-506)
         kw["waitk_lagging"] = g("waitk_testtime")
     from dataclasses import replace
     return replace(base, **kw)
@@ -97,6 +100,10 @@ def upgrade_state_dict(state: Mapping[str, torch.Tensor], cfg: ModelConfig, voca
             missing.remove(k)
     if missing and strict:
         raise KeyError(f"checkpoint is missing {len(missing)} tensors, e.g. {missing[:4]}")
+    if strict and cfg.model == "s2t_emformer":    # a plain TransformerDecoder holds no policy parameters
+        policy = [k for k in sd if re.search(r"encoder_attn\.(energy_bias|[qk]_proj_soft\.)", k)]
+        if policy:
+            raise KeyError(f"s2t_emformer checkpoint holds {len(policy)} monotonic-attention tensors, e.g. {policy[:4]}")
     for k, v in ref.items():
         if k in sd and tuple(sd[k].shape) != tuple(v.shape):
             raise ValueError(f"shape mismatch for {k}: checkpoint {tuple(sd[k].shape)} vs model {tuple(v.shape)}")

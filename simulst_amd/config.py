@@ -37,7 +37,7 @@ class ModelConfig:
     max_memory_size: int = 5
     tanh_on_mem: bool = True
     ctc_layer: bool = False
-    # --simul-attn-type
+    # --simul-attn-type ("full": the plain encoder-decoder attention of the s2t_emformer model, no policy)
     simul_attn_type: str = "waitk_fixed_pre_decision"
     waitk_lagging: int = 3
     fixed_pre_decision_ratio: int = 8
@@ -90,6 +90,12 @@ class ModelConfig:
 def mma_model_s(**kw) -> ModelConfig:
     """arch mma_model_s (models/mma_model.py:258-268) as launched by exp/2-mma.sh:55-57."""
     return replace(ModelConfig(model="mma_model"), **kw)
+
+
+def s2t_emformer_s(**kw) -> ModelConfig:
+    """arch s2t_emformer_s (models/s2t_emformer.py:398-413): the offline CTC + attention ASR model whose decoder is fairseq's
+    plain TransformerDecoder -- cross-attention over every valid encoder row, no read/write policy (ctc_layer defaults off)."""
+    return replace(ModelConfig(model="s2t_emformer", simul_attn_type="full", ctc_layer=False, mass_preservation=False), **kw)
 
 
 def cif_transformer_s(**kw) -> ModelConfig:

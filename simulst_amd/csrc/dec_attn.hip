@@ -169,7 +169,8 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const T* __restrict__ q
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int D = H * d;
   const int len = key_len ? key_len[b] : S_cap;
-  const long st = step[(long)b * H + h];
+  const bool full = attn_type == SIMULST_ATTN_FULL;     // softmax over [0, len), no step
+  const long st = full ? (long)len - 1 : step[(long)b * H + h];
   const T* Kh = Kc + ((long)b * H + h) * S_cap * d;     // head-major [B][H][S_cap][d]
   const T* Vh = Vc + ((long)b * H + h) * S_cap * d;
   float* bt = beta ? beta + ((long)b * H + h) * S_cap : nullptr;
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const T* __restrict__ q
   } else {
     // softmax over keys <= step, zeroed if the head has not moved (:278-293)
     const int n = (int)(st < len - 1 ? st : len - 1) + 1;
-    if (st > 0 && n > 0) {
+    if ((st > 0 || full) && n > 0) {
       if (NP > 0 && n <= 256) {
         if constexpr (NP > 0) {
           attn::Regs2<T, NP> r;
@@ -260,10 +261,11 @@ extern "C" int simulst_decoder_cross_attention(simulst_handle* h, const void* q,
                                                int32_t B, int32_t H, int32_t d, int32_t S_cap, int32_t attn_type,
                                                int32_t mass_preservation, int32_t dtype) {
   if (!h) return SIMULST_E_NULL;
-  SL_CHECK_NULL(h, Vc); SL_CHECK_NULL(h, step); SL_CHECK_NULL(h, ctx);
+  SL_CHECK_NULL(h, Vc); SL_CHECK_NULL(h, ctx);
+  if (attn_type != SIMULST_ATTN_FULL) SL_CHECK_NULL(h, step);      // FULL: no step (may be NULL)
   if (attn_type != SIMULST_ATTN_HARD) { SL_CHECK_NULL(h, q); SL_CHECK_NULL(h, Kc); }
   SL_REQUIRE(h, dtype == SIMULST_F32 || dtype == SIMULST_BF16, SIMULST_E_DTYPE, "simulst_decoder_cross_attention: dtype");
-  SL_REQUIRE(h, attn_type >= SIMULST_ATTN_HARD && attn_type <= SIMULST_ATTN_CHUNKWISE, SIMULST_E_ARG,
+  SL_REQUIRE(h, attn_type >= SIMULST_ATTN_HARD && attn_type <= SIMULST_ATTN_FULL, SIMULST_E_ARG,
              "simulst_decoder_cross_attention: attn_type");
   SL_REQUIRE(h, H > 0 && d >= 8 && d <= 64 && d % 8 == 0 && S_cap > 0, SIMULST_E_SHAPE,
              "simulst_decoder_cross_attention: head_dim must be a multiple of 8, <= 64");

@@ -63,6 +63,8 @@ struct HeadSplit {
 //  2. wave 0: mask the past, force the stop, first index with p >= 0.5
 //     (modules/monotonic_multihead_attention.py:196-257) -> head_step, head_read
 //  3. hard gather / softmax over keys <= step (:261-297), PV
+// SIMULST_ATTN_FULL (plain encoder-decoder attention, no policy): phases 1 and 2 are skipped, phase 3 is the softmax over all
+// len keys, head_step / head_read are neither read nor written
 // FQ = the fused-query instantiation (LN2 + q-projection inside the launch, <= 128 rows); the plain one drops that code
 // and its registers and runs 4 workgroups per CU
 #ifndef SL_POLICY_WGS
@@ -125,9 +127,11 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
   attn::Regs2<T, NP> rg2;
   // n_hint: upper bound on the keys this step can attend to: host-known (wait-k in lockstep), derived from
   // the device-side target index (n_hint < 0, wait-k: target t sees at most (t + k) * ratio frames), else S_cap
+  const bool full = attn_type == SIMULST_ATTN_FULL;
   const int tg = tgt_idx ? tgt_idx[b] : 0;    // scalar inputs of the policy: issued with the prefetch
-  const long hs = head_step[r];
+  const long hs = full ? 0 : head_step[r];
   if (n_hint < 0) n_hint = attn_type == SIMULST_ATTN_WAITK ? (tg + waitk_k) * ratio : S_cap;
+  if (full) n_hint = len;                     // every valid key, none beyond
 #ifdef SL_ABLATE_CROSS      // timing ablation (results invalid): 8 key / value rows instead of the visible source
   n_hint = 8;
 #endif
@@ -218,7 +222,9 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
   //           pooled position wk (fixed_pre_decision.py:133-167); the search then is a minimum over <= 3 candidates.
   //           Every thread computes it; thread 0 publishes.  Other attention types: pooled energies + search below.
   long st;
-  if (attn_type == SIMULST_ATTN_WAITK) {
+  if (full) {
+    st = len - 1;                                       // the last key: phase 3 attends over [0, len)
+  } else if (attn_type == SIMULST_ATTN_WAITK) {
     int wk = tg + waitk_k - 1;
     if (!online) wk = min(wk, P - 1);
     int s1 = -1, s2 = -1;                               // frames with p = 1
@@ -325,7 +331,7 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
     if (!dead && tid < d) o = to_f32(Vh[scl * d + tid]);
   } else {
     const int n = (int)(st < len - 1 ? st : len - 1) + 1;
-    if (st > 0 && n > 0) {
+    if ((st > 0 || full) && n > 0) {                    // FULL has no "zero while the head has not moved" rule
       const float* qfused = fusedq ? (Wqs ? qsoft_s : q_s) : nullptr;
       if (fast) {
         if constexpr (NP > 0) o = attn::finish3<T, NP>(rg2, n, n_pref, rsqrtf((float)d), red, nullptr, qfused);
@@ -349,13 +355,14 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
 // replaces moved 3.7 TB/s of K / V at 1024 rows x 384-750 keys where the single-latency form moves 6.1-6.4 (tools/kernel_bench.py
 // cross_attn --keys).  The closed-form wait-k policy is computed by every block workgroup (it reads head_step and block 0 writes
 // it: a workgroup that reads the NEW value finds the same step again, the minimum over candidates >= head_step is idempotent).
+// full != 0 (SIMULST_ATTN_FULL): no policy -- every block below len is live, head_step / head_read / tgt_idx are not touched.
 constexpr int KB_KEYS = 256;
 template <typename T, int NP>
 __global__ __launch_bounds__(256, NP >= 16 ? 2 : 4) void waitk_cross_attn_block_kernel(
     const T* __restrict__ qs, const T* __restrict__ Ks, const T* __restrict__ Vc, const int* __restrict__ key_len,
     const int* __restrict__ tgt_idx, long* __restrict__ head_step, unsigned char* __restrict__ head_read,
     float* __restrict__ part, int H, int d, int S_cap, int ratio, int waitk_k, int online, int mass_pres, int n_hint,
-    StreamCtl ctl) {
+    StreamCtl ctl, int full) {
   if (ctl.active) {
     const unsigned char rf = ctl.read_flag[blockIdx.y];
     if (!ctl.active[blockIdx.y] || (rf && rf != ctl.layer)) return;
@@ -370,14 +377,17 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : 4) void waitk_cross_attn_block_
   ratio = ratio < 0 ? -ratio : ratio;
   const int P = pooled_count(len, ratio, true, pool_last);
   const long hb = ((long)b * H + h) * S_cap * d;
-  const int tg = tgt_idx[b];
-  const long hs = head_step[r];
+  const int tg = full ? 0 : tgt_idx[b];
+  const long hs = full ? 0 : head_step[r];
   if (n_hint < 0) n_hint = (tg + waitk_k) * ratio;
+  if (full) n_hint = len;
   const int j0 = kb * KB_KEYS;
   const int n_pref = max(0, min(min(S_cap, n_hint) - j0, KB_KEYS));
   attn::Regs2<T, NP> rg2;
   if (n_pref > 0)
     attn::prefetch2<T, NP>(rg2, qs + (long)b * D + h * d, Ks + hb + (long)j0 * d, d, Vc + hb + (long)j0 * d, d, n_pref, -1, nullptr, nullptr);
+  long st = len - 1;                                   // FULL: keys [0, len)
+  if (!full) {
   // the closed-form wait-k policy of policy_cross_attn_kernel
   int wk = tg + waitk_k - 1;
   if (!online) wk = min(wk, P - 1);
@@ -400,9 +410,10 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : 4) void waitk_cross_attn_block_
     head_read[r] = hr ? 1 : 0;
     if (ctl.read_flag && hr && online) ctl.read_flag[b] = (unsigned char)ctl.layer;
   }
-  const long st = found;
+  st = found;
+  }
   const int n = (int)(st < len - 1 ? st : len - 1) + 1;                  // keys [0, n) take part
-  const int nb = (st > 0 && n > 0) ? max(0, min(n - j0, KB_KEYS)) : 0;   // ... of them in this block (uniform over the workgroup)
+  const int nb = ((st > 0 || full) && n > 0) ? max(0, min(n - j0, KB_KEYS)) : 0;   // ... of them in this block (uniform over the workgroup)
   float* pw = part + ((long)r * nblk + kb) * (d + 2);
   if (nb <= 0 || n_pref <= 0) {
     if (tid == 0) { pw[0] = -INFINITY; pw[1] = 0.f; }
@@ -634,8 +645,10 @@ int launch_policy_cross(simulst_handle* h, const void* qm, const void* qs, const
   if ((size_t)h->policy_lds_bytes > lds && B >= h->dec_chain_min_rows) lds = (size_t)h->policy_lds_bytes;
   KTimer t(h, SIMULST_K_DEC_CROSS_ATTN);
   const int np = attn::lanes_per_row<T>(d);
-  if (attn_type == SIMULST_ATTN_WAITK && S_cap > KB_KEYS && !xres && qs && Ks && np > 0 && !h->force_unfused_decode) {
-    // long sources: key blocks of 256 on their own workgroups + a merge (waitk_cross_attn_block_kernel)
+  if ((attn_type == SIMULST_ATTN_WAITK || attn_type == SIMULST_ATTN_FULL) && S_cap > KB_KEYS && !xres && qs && Ks && np > 0 &&
+      !h->force_unfused_decode) {
+    // long sources: key blocks of 256 on their own workgroups + a merge (waitk_cross_attn_block_kernel; FULL: every block below
+    // the row's length is live)
     const int nblk = (S_cap + KB_KEYS - 1) / KB_KEYS;
     const size_t need = (size_t)B * H * nblk * (d + 2) * sizeof(float);
     if (h->ws_bytes < need) {
@@ -651,7 +664,7 @@ int launch_policy_cross(simulst_handle* h, const void* qm, const void* qs, const
 #define KB_LAUNCH(NP)                                                                                                  \
     hipLaunchKernelGGL((waitk_cross_attn_block_kernel<T, NP>), dim3(H, B, nblk), dim3(256), 0, h->stream, (const T*)qs,     \
                        (const T*)Ks, (const T*)Vc, key_len, tgt_idx, (long*)head_step, head_read, part, H, d, S_cap, ratio,  \
-                       waitk_k, online, mass_pres, n_hint, ctl)
+                       waitk_k, online, mass_pres, n_hint, ctl, attn_type == SIMULST_ATTN_FULL ? 1 : 0)
     switch (np) { case 2: KB_LAUNCH(2); break; case 4: KB_LAUNCH(4); break; case 8: KB_LAUNCH(8); break; default: KB_LAUNCH(16); break; }
 #undef KB_LAUNCH
     int rc = sl_launch_status(h, "simulst_policy_cross_attention(blocks)");
@@ -710,12 +723,13 @@ static int policy_cross(simulst_handle* h, const void* qm, const void* qs, const
     SL_REQUIRE(h, (xres || (!hs.po && !hs.w_packed)) && (!hs.po || hs.x_mid) && (!hs.w_packed || d % 16 == 0), SIMULST_E_ARG,
                "simulst_policy_cross_attention: head-split projections need the fused query path");
   }
-  SL_CHECK_NULL(h, Vc); SL_CHECK_NULL(h, head_step); SL_CHECK_NULL(h, head_read); SL_CHECK_NULL(h, ctx);
+  SL_CHECK_NULL(h, Vc); SL_CHECK_NULL(h, ctx);
   SL_REQUIRE(h, dtype == SIMULST_F32 || dtype == SIMULST_BF16, SIMULST_E_DTYPE, "simulst_policy_cross_attention: dtype");
-  SL_REQUIRE(h, attn_type >= SIMULST_ATTN_HARD && attn_type <= SIMULST_ATTN_CHUNKWISE, SIMULST_E_ARG,
+  SL_REQUIRE(h, attn_type >= SIMULST_ATTN_HARD && attn_type <= SIMULST_ATTN_FULL, SIMULST_E_ARG,
              "simulst_policy_cross_attention: attn_type");
+  if (attn_type != SIMULST_ATTN_FULL) { SL_CHECK_NULL(h, head_step); SL_CHECK_NULL(h, head_read); }
   if (attn_type == SIMULST_ATTN_WAITK) { SL_CHECK_NULL(h, tgt_idx); SL_REQUIRE(h, waitk_k > 0, SIMULST_E_ARG, "simulst_policy_cross_attention: lagging"); }
-  else { if (!xres) SL_CHECK_NULL(h, qm); SL_CHECK_NULL(h, Kmono); }
+  else if (attn_type != SIMULST_ATTN_FULL) { if (!xres) SL_CHECK_NULL(h, qm); SL_CHECK_NULL(h, Kmono); }
   if (attn_type != SIMULST_ATTN_HARD) { if (!xres) SL_CHECK_NULL(h, qs); SL_CHECK_NULL(h, Ksoft); }
   if (xres) { SL_CHECK_NULL(h, ln_g); SL_CHECK_NULL(h, ln_b); SL_CHECK_NULL(h, Wqm);
               SL_REQUIRE(h, (H * d) % 32 == 0, SIMULST_E_SHAPE, "simulst_policy_cross_attention: D % 32 for the fused projection"); }
@@ -861,17 +875,19 @@ static int run_decode(simulst_handle* h, const simulst_decoder_desc* dd, const s
   const int pk = dd->weights_fragment_major;
   SL_REQUIRE(h, !pk || (D % 64 == 0 && F % 64 == 0 && V % 16 == 0 && d % 16 == 0), SIMULST_E_SHAPE,
              "simulst_mma_decode: fragment-major weights need D, F multiples of 64, V and head_dim of 16");
+  // FULL over more than 256 keys: the blocked kernel reads a separate query, so the <= 128-row class runs LN2 + q-proj as a GEMM
+  const bool full_blocked = dd->attn_type == SIMULST_ATTN_FULL && dd->S_cap > KB_KEYS && !h->force_unfused_decode;
   // head-split self-attention block (decode_fused.hip): 5 launches per layer instead of 7 when the host supplied the
   // partial buffer, the weights are fragment-major and the shapes fit (cached target positions <= 256)
 #ifdef SL_EXPERIMENTS
-  const bool split = pk && dd->x_mid && dd->partial_self && !h->force_unfused_decode &&
+  const bool split = !full_blocked && pk && dd->x_mid && dd->partial_self && !h->force_unfused_decode &&
                      sl_self_attention_fused_ok(H, d, dd->cap) && B <= 128 && (dt == SIMULST_BF16 ? D <= 512 : D <= 256);
 #else
   const bool split = false;          // decode_fused.hip: measured slower, EXPERIMENTS builds only
 #endif
   // LN2 + query projection inside the policy/cross-attention launch (few rows: one launch less on the dependent
   // chain) or as its own GEMM (many rows: no per-workgroup re-read of the projection weights)
-  const bool fuse_q = split || B <= h->fuse_q_max_rows;
+  const bool fuse_q = (split || B <= h->fuse_q_max_rows) && !full_blocked;
   // row-local chains (dec_chain.hip) for co-scheduled batches: { out-proj + residual, LN + q-proj(s) } in one launch,
   // { cross out-proj + residual, LN + fc1 + GELU, fc2 + residual } in another -- 5 launches per layer instead of 8-9
   // (the feed-forward chain is always launched in its hand-off-free form here -- x_mid given, slabs added by the next layer's
@@ -1041,6 +1057,8 @@ static int run_decode(simulst_handle* h, const simulst_decoder_desc* dd, const s
 extern "C" int simulst_mma_stream_steps(simulst_handle* h, const simulst_decoder_desc* dd, const simulst_dec_layer* layers,
                                         int64_t* tokens_io, const simulst_stream_ctl* c, int32_t n_iter) {
   if (!h) return SIMULST_E_NULL;
+  SL_REQUIRE(h, !dd || dd->attn_type != SIMULST_ATTN_FULL, SIMULST_E_ARG,
+             "simulst_mma_stream_steps: full attention is not a simultaneous policy (offline decoding only)");
   SL_CHECK_NULL(h, c); SL_CHECK_NULL(h, c->active); SL_CHECK_NULL(h, c->read_flag); SL_CHECK_NULL(h, c->online);
   SL_CHECK_NULL(h, c->done); SL_CHECK_NULL(h, c->hyp);
   SL_REQUIRE(h, c->cap > 0 && n_iter >= 0, SIMULST_E_SHAPE, "simulst_mma_stream_steps: cap / n_iter");

@@ -790,6 +790,7 @@ extern "C" int simulst_step_p_choose(simulst_handle* h, const void* q, const voi
   if (!h) return SIMULST_E_NULL;
   SL_CHECK_NULL(h, p);
   SL_REQUIRE(h, dtype == SIMULST_F32 || dtype == SIMULST_BF16, SIMULST_E_DTYPE, "simulst_step_p_choose: dtype");
+  SL_REQUIRE(h, attn_type != SIMULST_ATTN_FULL, SIMULST_E_ARG, "simulst_step_p_choose: full attention has no step probabilities");
   SL_REQUIRE(h, attn_type >= SIMULST_ATTN_HARD && attn_type <= SIMULST_ATTN_CHUNKWISE, SIMULST_E_ARG,
              "simulst_step_p_choose: attn_type");
   if (attn_type == SIMULST_ATTN_WAITK) { SL_CHECK_NULL(h, tgt_idx); SL_REQUIRE(h, waitk_k > 0, SIMULST_E_ARG, "simulst_step_p_choose: waitk lagging"); }

@@ -78,7 +78,7 @@ class DecoderWeights:
                 if cfg.attn_type in ("infinite_lookback", "chunkwise"):
                     L["c_wq_soft"], L["c_bq_soft"] = W(f"{ea}.q_proj_soft.weight"), Bv(f"{ea}.q_proj_soft.bias")
                     L["c_wk_soft"], L["c_bk_soft"] = W(f"{ea}.k_proj_soft.weight"), Bv(f"{ea}.k_proj_soft.bias")
-                L["energy_bias"] = float(w[f"{ea}.energy_bias"][0]) if cfg.energy_bias else 0.0
+                L["energy_bias"] = float(w[f"{ea}.energy_bias"][0]) if cfg.energy_bias and cfg.attn_type != "full" else 0.0
             L["fc1"], L["b1"] = W(f"{lp}.fc1.weight"), Bv(f"{lp}.fc1.bias")
             L["fc2"], L["b2"] = W(f"{lp}.fc2.weight"), Bv(f"{lp}.fc2.bias")
             self.layers.append(L)
@@ -195,7 +195,9 @@ class _Dictionary:
 
 
 class MMADecoder:
-    """Mirror of models/mma_model.py:MMADecoder (inference, incremental)."""
+    """Mirror of models/mma_model.py:MMADecoder (inference, incremental).  attn_type "full" (the s2t_emformer model): fairseq's plain
+    TransformerDecoder, whose cross-attention is the softmax over every valid encoder row -- no p_choose, no step search, never a
+    READ; the same state, loops and kernels run with SIMULST_ATTN_FULL."""
 
     def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], device="cuda", dtype=torch.float32,
                  ops: Optional[Ops] = None, prefix="decoder", shared_weights: Optional[DecoderWeights] = None):
@@ -217,6 +219,7 @@ class MMADecoder:
         # K and V projections of every layer over new encoder rows as ONE contraction (tall bf16 batches; SIMULST_FUSE_KV=0: one
         # launch per projection as in round 2)
         self.fuse_kv_projections = os.environ.get("SIMULST_FUSE_KV", "1") == "1"
+        self.full = cfg.attn_type == "full"
         self.soft = cfg.attn_type != "hard_aligned"
         self.separate_soft = cfg.attn_type in ("infinite_lookback", "chunkwise")
         self.embed_scale = 1.0 if cfg.no_scale_embedding else math.sqrt(cfg.embed_dim)
@@ -320,8 +323,17 @@ class MMADecoder:
             ctx = ops.decoder_self_attention(qkv, st.k_cache[l], st.v_cache[l], st.n_prev)
             x = ops.linear(ctx, L["wo"], L["bo"], epilogue=EPI_BIAS_RES, residual=x)
             y = ops.layernorm(x, L["ln2_g"], L["ln2_b"])
-            p = torch.empty(B * H, st.S_cap, device=self.device, dtype=torch.float32)
             q = None
+            if self.full:              # plain encoder-decoder attention: softmax over [0, enc_len), no policy
+                q = ops.linear(y, L["c_wq"], L["c_bq"])
+                ctx, _ = ops.decoder_cross_attention(q, st.Kmono[l], st.V[l], None, H=H, attn_type=self.attn_enum,
+                                                     mass_preservation=False, key_len=st.enc_len)
+                x = ops.linear(ctx, L["c_wo"], L["c_bo"], epilogue=EPI_BIAS_RES, residual=x)
+                y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
+                hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
+                x = ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+                continue
+            p = torch.empty(B * H, st.S_cap, device=self.device, dtype=torch.float32)
             if cfg.attn_type == "waitk":
                 ops.step_p_choose(None, None, p, B=B, S_cap=st.S_cap, H=H, d=d, ratio=self.ratio_arg,
                                   incremental=incremental, attn_type=_lib.ATTN_WAITK, key_len=st.enc_len,

@@ -155,7 +155,23 @@ class MMAModel(SimulSTModel):
 
 @register_model("s2t_emformer")
 class S2TEmformerModel(SimulSTModel):
-    pass
+    """models/s2t_emformer.py:297-379: the Emformer encoder and fairseq's plain TransformerDecoder (cross-attention over every valid
+    encoder row, SIMULST_ATTN_FULL).  An offline model: generate (beam search, eval/eval_asr.sh's call) and generate_offline
+    (greedy); the simultaneous agents refuse it."""
+
+    def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], device="cuda", dtype=torch.float32,
+                 ops: Optional[Ops] = None, share_with: Optional["SimulSTModel"] = None):
+        if cfg.attn_type != "full":
+            raise ValueError(f"S2TEmformerModel decodes with full attention (config.s2t_emformer_s), not {cfg.simul_attn_type!r}")
+        super().__init__(cfg, weights, device, dtype, ops, share_with)
+
+
+def refuse_offline_model(model, who: str):
+    """The simultaneous agents need a read/write policy; a model with full encoder-decoder attention has none."""
+    cfg = getattr(model, "cfg", None)
+    if cfg is not None and (cfg.model == "s2t_emformer" or cfg.attn_type == "full"):
+        raise ValueError(f"{who}: the {cfg.model} model attends to the whole source (full attention, no read/write policy) and "
+                         f"cannot be decoded simultaneously; use model.generate / model.generate_offline")
 
 
 def _default(args, name, value):

@@ -133,6 +133,8 @@ class FairseqSimulSTAgent(SpeechAgent):
             self.load_model_vocab(args)
         else:
             self.model, self.dict, self.pre_tokenizer = model, {"tgt": tgt_dict or model.decoder.dictionary}, None
+        from .model import refuse_offline_model
+        refuse_offline_model(self.model, type(self).__name__)
         dec, enc = self.model.decoder, self.model.encoder
         self.pre_decision_ratio = getattr(dec.layers[0].encoder_attn, "pre_decision_ratio", 1)
         self.full_sentence = getattr(args, "full_sentence", False)

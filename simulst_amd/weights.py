@@ -112,7 +112,9 @@ def init_model(cfg: ModelConfig, seed: int = 999, ln_jitter: float = 0.02) -> Di
             w[f"{p}.encoder_attn.out_proj.weight"] = _xavier(gen, D, D)
             w[f"{p}.encoder_attn.out_proj.bias"] = torch.zeros(D)
             at = cfg.attn_type
-            if at in ("infinite_lookback", "chunkwise"):
+            if cfg.model == "s2t_emformer":
+                pass        # fairseq's plain MultiheadAttention: {q,k,v,out}_proj only
+            elif at in ("infinite_lookback", "chunkwise"):
                 for n in ("q_proj_soft", "k_proj_soft"):
                     w[f"{p}.encoder_attn.{n}.weight"] = _xavier(gen, D, D, s2)
                     w[f"{p}.encoder_attn.{n}.bias"] = _uniform_bias(gen, D, D)
@@ -122,7 +124,7 @@ def init_model(cfg: ModelConfig, seed: int = 999, ln_jitter: float = 0.02) -> Di
                 for n in ("q_proj", "k_proj"):
                     for m in ("weight", "bias"):
                         w[f"{p}.encoder_attn.{n}_soft.{m}"] = w[f"{p}.encoder_attn.{n}.{m}"]
-            if cfg.energy_bias:
+            if cfg.energy_bias and cfg.model != "s2t_emformer":
                 w[f"{p}.encoder_attn.energy_bias"] = cfg.energy_bias_init * torch.ones(1)
         _ln(w, p + ".encoder_attn_layer_norm", D, gen, ln_jitter)
         w[p + ".fc1.weight"] = _xavier(gen, F, D)

@@ -50,6 +50,8 @@ def main(argv=None, collect=None):
                     help="most utterances per launch sequence (neighbours in length)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--waitk", type=int, default=3)
+    ap.add_argument("--model", default="mma_model", choices=["mma_model", "s2t_emformer"],
+                    help="s2t_emformer: the offline ASR model (full encoder-decoder attention, models/s2t_emformer.py); offline only")
     ap.add_argument("--streams", type=int, default=3, help="launch sequences in flight per GPU (HIP streams)")
     ap.add_argument("--streaming", action="store_true",
                     help="streaming evaluation instead of offline decoding: every utterance through the simultaneous policy with its "
@@ -96,7 +98,7 @@ def main(argv=None, collect=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    from simulst_amd.config import mma_model_s
+    from simulst_amd.config import mma_model_s, s2t_emformer_s
     from simulst_amd.model import SimulSTModel
     from simulst_amd.sharding import gather_records
     from simulst_amd.weights import init_model
@@ -104,7 +106,11 @@ def main(argv=None, collect=None):
     from simulst_amd.offline_eval import (decode_batch, make_batch, plan_shard, plan_shard_by_work, sequence_cost,
                                           synthetic_lengths, trim_hypotheses)
     lengths = synthetic_lengths(args.utterances)
-    if args.streaming and args.policy == "hard":
+    if args.model == "s2t_emformer":
+        if args.streaming:
+            raise SystemExit("--model s2t_emformer: an offline model (full attention), no --streaming")
+        cfg = s2t_emformer_s()
+    elif args.streaming and args.policy == "hard":
         cfg = mma_model_s(simul_attn_type="hard_aligned_fixed_pre_decision", fixed_pre_decision_ratio=8, mass_preservation=True)
     else:
         cfg = mma_model_s(simul_attn_type="waitk_fixed_pre_decision", waitk_lagging=args.waitk)
@@ -229,10 +235,11 @@ def main(argv=None, collect=None):
               "passes_s_this_rank": [round(x, 3) for x in pass_s],
               "tokens_per_s": round(total_tokens / total_s, 1),
               "utterances_per_s": round(n_done / total_s, 1), "dtype": args.dtype,
-              "utterances_per_sequence": args.batch, "streams": args.streams, "plan": args.plan,
+              "utterances_per_sequence": args.batch, "streams": args.streams, "plan": args.plan, "model": args.model,
               "rows_per_sequence": [len(b[0]) for b in batches],
               "properties": {"one_hypothesis_per_utterance": bool(one_each), "every_length_within_its_cap": bool(caps_ok)},
-              "path_hbm_model": path_model(cfg, lengths, [b[0] for b in batches], dtype, args.waitk, "waitk", False,
+              "path_hbm_model": path_model(cfg, lengths, [b[0] for b in batches], dtype,
+                                           10 ** 6 if args.model == "s2t_emformer" else args.waitk, "waitk", False,
                                            total_tokens / total_s, world),
               "timed": "decode of every launch sequence + D2H + hypothesis trimming" +
                        ("" if args.warmup else " (cold: first launches and allocator growth included)")})
