@@ -620,7 +620,8 @@ int simulst_mma_decode(simulst_handle* h, const simulst_decoder_desc* d, const s
  *     windows, head_step, head_read, n_prev, enc_len, enc_len_bh (may be NULL; [B][H]), slot_row, row_cap and
  *     last_tokens ([B] int64: the tokens_io of the next chunk);
  *  3. result ([4 + 2 B] int32 device scratch): [0] n_live, [1] rows_next = n_live rounded up to 16 rows, clamped into the
- *     kernel class the decode loop runs a batch of B rows in (0 when no row is live), [2] pairs moved.
+ *     kernel class the decode loop runs a batch of B rows in (csrc/decode_plan.cpp sl_retire_floor_rows, beside the launch
+ *     plan whose row switch points it keeps; 0 when no row is live), [2] pairs moved.
  * The next chunk runs simulst_mma_decode with d->B = rows_next; the slots behind n_live ride along dead. */
 int simulst_mma_retire_rows(simulst_handle* h, const simulst_decoder_desc* d, const simulst_dec_layer* layers,
                             const int64_t* chunk_tokens, int32_t n_steps, int32_t rows, int32_t B, int32_t* slot_row,
@@ -817,7 +818,8 @@ int simulst_cif_stream_append(simulst_handle* h, const void* out, const int32_t*
                               int32_t D, float beta, int32_t finish, int32_t dtype);
 
 /* Row-local chains of the decoder layer for co-scheduled batches (bf16, D == 256, fragment-major weights); the decode
- * loop uses them from 129 rows on when simulst_decoder_desc.ffn_partial / ffn_sem are given.  Same rounding points as the
+ * loops use them where their launch plan says so (csrc/decode_plan.cpp sl_plan_decode: by default from 129 rows on when
+ * simulst_decoder_desc.ffn_partial / x_mid are given).  Same rounding points as the
  * launches they replace (bf16 after bias + residual, after LayerNorm, after GELU).
  *   proj chain:  x <- bf16(x + Wo ctx + bo);  q <- Wq LN(x) + bq;  q2 <- Wq2 LN(x) + bq2 (wq2_fm may be NULL)
  *                = the self-attention output projection + residual of fairseq's TransformerDecoderLayer followed by

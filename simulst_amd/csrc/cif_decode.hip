@@ -13,6 +13,7 @@
 // Launches per layer: co-scheduled bf16 batches (the row-local chains of dec_chain.hip) 4 -- {slab sum + LN1 + QKV}, self-attention,
 // {out-proj + residual + LN2 + q-proj + kk + GELU}, {out-proj + residual + LN3 + fc1 + GELU + fc2 slabs} -- otherwise 7.
 #include "attn_core.h"
+#include "decode_plan.h"
 
 namespace {
 
@@ -197,18 +198,6 @@ __global__ __launch_bounds__(256) void cif_append_kernel(const T* __restrict__ o
   if (tid == 0) acc_len[b] = base + keep < n_cap ? base + keep : n_cap;
 }
 
-int lin(simulst_handle* h, int dtype, int B, int N, int K, const void* A, const void* W, const float* bias, const void* R,
-        void* C, int epi, const float* ln_g, const float* ln_b, int w_packed) {
-  simulst_linear_desc d;
-  d.M_batches = 1; d.rows_per_batch = B; d.N = N; d.K = K;
-  d.a_batch_stride = 0; d.a_row_stride = K; d.a_lead = 0;
-  d.c_batch_stride = 0; d.c_row_stride = N;
-  d.r_batch_stride = 0; d.r_row_stride = N;
-  d.epilogue = epi; d.dtype = dtype; d.scale = 1.f; d.n_main = 0; d.aux_rows = 0; d.aux_batch_stride = 0;
-  d.ln_gamma = ln_g; d.ln_beta = ln_b; d.w_fragment_major = w_packed; d.c_head_dim = 0; d.c_head_stride = 0; d.c_tensor_heads = 0; d.c_tensor_stride = 0;
-  return simulst_linear(h, &d, A, W, bias, R, C, nullptr);
-}
-
 template <typename T>
 int launch_commit(simulst_handle* h, const simulst_cif_decoder_desc* dd, const KcPtrs& kc, const float* logits, int64_t* tokens,
                   int64_t* out_row, int mask_eos, const CifCtl& ctl, int n_pairs = 0) {
@@ -245,26 +234,22 @@ int run_cif(simulst_handle* h, const simulst_cif_decoder_desc* dd, const simulst
   rc = dt == SIMULST_F32 ? launch_commit<float>(h, dd, kc, nullptr, tokens_io, nullptr, mask_eos, ctl)
                          : launch_commit<bf16>(h, dd, kc, nullptr, tokens_io, nullptr, mask_eos, ctl);
   if (rc) return rc;
-  // row-local chains for co-scheduled bf16 batches (dec_chain.hip): same domain as the MMA decode loop
-  const bool chain = dd->ffn_partial && dd->x_mid && sl_dec_chain_ok(h, dt, B, D, F, pk != 0);
-  const bool chain_ffn = chain && B <= h->dec_chain_ffn_max_rows;
-  const bool attn_chain = chain && sl_dec_attn_chain_ok(h, dt, B, H, d, dd->cap);
-  // round 5: the feed-forward chain of layer l with the slab sum + LN1 + QKV of layer l + 1 in one launch (as simulst_mma_decode)
-  const bool fuse_ffn_qkv = chain_ffn && !attn_chain && sl_dec_ffn_qkv_chain_ok(h, B, F);
-  bool qkv_done = false;
+  // the launch path of every step (decode_plan.h)
+  const bool streaming = ctl.done != nullptr;
+  sl_decode_call call = {};
+  call.dtype = dt; call.B = B; call.D = D; call.H = H; call.F = F; call.V = V; call.cap = dd->cap; call.attn_type = -1;
+  call.packed = pk != 0; call.x_mid = dd->x_mid != nullptr; call.ffn_partial = dd->ffn_partial != nullptr; call.final_ln = true;
+  call.mode = streaming ? SL_CALL_STREAM : SL_CALL_OFFLINE; call.np_uniform = np_uniform; call.mask_eos = mask_eos != 0;
+  call.cif = true; call.highway = dd->highway != 0;
+  const sl_decode_plan plan = sl_plan_decode(h, call);
+  const sl_step_bufs bufs = {dt, B, D, F, pk, dd->x, dd->x_mid, dd->qkv, dd->hidden, dd->ffn_partial, nullptr};
+  const float* last_b2 = layers[dd->n_layers - 1].b2;
   for (int s = 0; s < n_steps; ++s) {
     for (int l = 0; l < dd->n_layers; ++l) {
       const simulst_cif_dec_layer& L = layers[l];
       const void* kk_l = (const char*)dd->kk + (size_t)l * B * D * (dt == SIMULST_F32 ? 4 : 2);
-      if (qkv_done) {
-        qkv_done = false;                           // (x and qkv of this layer were written by the previous layer's launch)
-      } else if (chain_ffn && l > 0) {                     // the previous layer's feed-forward slabs are added here, then LN1 + QKV
-        if ((rc = sl_dec_qkv_chain(h, dd->x_mid, dd->x, dd->ffn_partial, layers[l - 1].b2, L.ln1_g, L.ln1_b, L.wqkv, L.bqkv,
-                                   dd->qkv, B, F))) return rc;
-      } else {
-        if ((rc = lin(h, dt, B, 3 * D, D, dd->x, L.wqkv, L.bqkv, nullptr, dd->qkv, SIMULST_EPI_BIAS, L.ln1_g, L.ln1_b, pk))) return rc;
-      }
-      if (attn_chain) {
+      if ((rc = sl_step_qkv(h, plan, bufs, l, l > 0 ? layers[l - 1].b2 : nullptr, sl_qkv_of(L)))) return rc;
+      if (plan.attn_chain) {
         // self-attention; x += Wo ctx + bo;  q = gelu(Wq LN2(x) + kk): one launch
         if ((rc = sl_dec_attn_proj_chain(h, dd->qkv, L.k_cache, L.v_cache, dd->n_prev, np_uniform < 0 ? -1 : np_uniform + s, dd->cap,
                                          dd->x, L.wo, L.bo, L.ln2_g, L.ln2_b, L.c_wq, nullptr, dd->q, nullptr, nullptr, nullptr, B,
@@ -272,50 +257,30 @@ int run_cif(simulst_handle* h, const simulst_cif_decoder_desc* dd, const simulst
       } else {
         if ((rc = sl_self_attention(h, dd->qkv, L.k_cache, L.v_cache, dd->n_prev, np_uniform < 0 ? -1 : np_uniform + s, dd->ctx, B,
                                     H, d, dd->cap, dt))) return rc;
-        if (chain) {
+        if (plan.chain) {
           // x += Wo ctx + bo;  q = gelu(Wq LN2(x) + kk): one launch
           if ((rc = sl_dec_proj_chain(h, dd->ctx, dd->x, L.wo, L.bo, L.ln2_g, L.ln2_b, L.c_wq, nullptr, dd->q, nullptr, nullptr,
                                       nullptr, B, kk_l))) return rc;
         } else {
-          if ((rc = lin(h, dt, B, D, D, dd->ctx, L.wo, L.bo, dd->x, dd->x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, pk))) return rc;
-          if ((rc = lin(h, dt, B, D, D, dd->x, L.c_wq, nullptr, kk_l, dd->q, SIMULST_EPI_BIAS_RES_GELU, L.ln2_g, L.ln2_b, pk))) return rc;
+          if ((rc = sl_lin(h, dt, B, D, D, dd->ctx, L.wo, L.bo, dd->x, dd->x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, pk))) return rc;
+          if ((rc = sl_lin(h, dt, B, D, D, dd->x, L.c_wq, nullptr, kk_l, dd->q, SIMULST_EPI_BIAS_RES_GELU, L.ln2_g, L.ln2_b, pk))) return rc;
         }
       }
-      if (chain_ffn) {
-        if (fuse_ffn_qkv && l + 1 < dd->n_layers) {
-          const simulst_cif_dec_layer& Ln = layers[l + 1];
-          if ((rc = sl_dec_ffn_qkv_chain(h, dd->q, dd->x, L.c_wo, L.c_bo, L.ln3_g, L.ln3_b, L.fc1, L.b1, L.fc2, L.b2, dd->ffn_partial, B, F,
-                                         Ln.ln1_g, Ln.ln1_b, Ln.wqkv, Ln.bqkv, dd->qkv))) return rc;
-          qkv_done = true;
-          continue;
-        }
-        if ((rc = sl_dec_ffn_chain(h, dd->q, dd->x, L.c_wo, L.c_bo, L.ln3_g, L.ln3_b, L.fc1, L.b1, L.fc2, L.b2, dd->ffn_partial,
-                                   nullptr, dd->x_mid, B, F))) return rc;
-        continue;
-      }
-      if ((rc = lin(h, dt, B, D, D, dd->q, L.c_wo, L.c_bo, dd->x, dd->x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, pk))) return rc;
-      if ((rc = lin(h, dt, B, F, D, dd->x, L.fc1, L.b1, nullptr, dd->hidden, SIMULST_EPI_BIAS_GELU, L.ln3_g, L.ln3_b, pk))) return rc;
-      if ((rc = lin(h, dt, B, D, F, dd->hidden, L.fc2, L.b2, dd->x, dd->x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, pk))) return rc;
+      if ((rc = sl_step_ffn(h, plan, bufs, dd->q, dd->x, sl_ffn_of(L),
+                            l + 1 < dd->n_layers ? sl_qkv_of(layers[l + 1]) : sl_qkv_weights{}))) return rc;
     }
     // the step's closing launch (dec_chain.hip dec_vocab_chain_kernel: last layer's slab sum + final LayerNorm + output projection +
-    // eos bias + partial greedy pick) where the masks are known at launch time, as in simulst_mma_decode; not with the highway (the
-    // projection's input there is LN(x) + c)
-    const bool streaming = ctl.done != nullptr;
-    const bool masks_known = streaming || mask_eos || np_uniform >= 0;
+    // eos bias + partial greedy pick) where the plan takes it, as in simulst_mma_decode
     const bool no_eos = !streaming && (mask_eos || (np_uniform >= 0 && np_uniform + s == 0));
-    const int vsplit = (chain_ffn && masks_known && h->fused_argmax && !dd->highway)
-                           ? sl_dec_vocab_chain_split(h, dt, B, V, D, pk != 0, true) : 0;
-    if (vsplit) {
-      if ((rc = sl_dec_vocab_chain(h, dd->x_mid, dd->x, dd->ffn_partial, layers[dd->n_layers - 1].b2, dd->ln_g, dd->ln_b, dd->out_proj,
-                                   (float2*)dd->logits, B, F, V, vsplit, streaming ? -1 : dd->pad_idx, no_eos ? dd->eos_idx : -1,
+    if (plan.vsplit) {
+      if ((rc = sl_dec_vocab_chain(h, dd->x_mid, dd->x, dd->ffn_partial, last_b2, dd->ln_g, dd->ln_b, dd->out_proj,
+                                   (float2*)dd->logits, B, F, V, plan.vsplit, streaming ? -1 : dd->pad_idx, no_eos ? dd->eos_idx : -1,
                                    dd->eos_bias, dd->eos_idx))) return rc;
       int64_t* out_row_v = out_tokens ? out_tokens + (long)s * B : nullptr;
-      if ((rc = launch_commit<bf16>(h, dd, kc, dd->logits, tokens_io, out_row_v, mask_eos, ctl, vsplit))) return rc;
+      if ((rc = launch_commit<bf16>(h, dd, kc, dd->logits, tokens_io, out_row_v, mask_eos, ctl, plan.n_pairs))) return rc;
       continue;
     }
-    if (chain_ffn)                                  // the last layer's slabs
-      if ((rc = sl_dec_qkv_chain(h, dd->x_mid, dd->x, dd->ffn_partial, layers[dd->n_layers - 1].b2, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, B, F))) return rc;
+    if ((rc = sl_step_last_slabs(h, plan, bufs, last_b2))) return rc;
     if (dd->highway) {                              // logits = E^T (LN(x) + c): the final LayerNorm cannot ride as a prologue
       if ((rc = simulst_layernorm(h, dd->x, dd->ln_g, dd->ln_b, dd->ctx, B, D, D, D, dt))) return rc;
       {
@@ -325,9 +290,9 @@ int run_cif(simulst_handle* h, const simulst_cif_decoder_desc* dd, const simulst
         else hipLaunchKernelGGL(add_rows_kernel<bf16>, dim3((n + 255) / 256), dim3(256), 0, h->stream, (bf16*)dd->ctx, (const bf16*)dd->cif_t, n);
         if ((rc = sl_launch_status(h, "simulst_cif_decode(highway)"))) return rc;
       }
-      if ((rc = lin(h, dt, B, V, D, dd->ctx, dd->out_proj, nullptr, nullptr, dd->logits, SIMULST_EPI_BIAS_F32OUT, nullptr, nullptr, pk))) return rc;
+      if ((rc = sl_lin(h, dt, B, V, D, dd->ctx, dd->out_proj, nullptr, nullptr, dd->logits, SIMULST_EPI_BIAS_F32OUT, nullptr, nullptr, pk))) return rc;
     } else {
-      if ((rc = lin(h, dt, B, V, D, dd->x, dd->out_proj, nullptr, nullptr, dd->logits, SIMULST_EPI_BIAS_F32OUT, dd->ln_g, dd->ln_b, pk))) return rc;
+      if ((rc = sl_lin(h, dt, B, V, D, dd->x, dd->out_proj, nullptr, nullptr, dd->logits, SIMULST_EPI_BIAS_F32OUT, dd->ln_g, dd->ln_b, pk))) return rc;
     }
     int64_t* out_row = out_tokens ? out_tokens + (long)s * B : nullptr;
     rc = dt == SIMULST_F32 ? launch_commit<float>(h, dd, kc, dd->logits, tokens_io, out_row, mask_eos, ctl)

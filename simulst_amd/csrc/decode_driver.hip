@@ -8,6 +8,7 @@
 // LayerNorms ride as prologues of the following skinny GEMM (simulst_linear_desc.ln_gamma).
 #include "attn_core.h"
 #include "gemv_mfma.h"
+#include "decode_plan.h"
 
 namespace {
 
@@ -356,7 +357,7 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
 // cross_attn --keys).  The closed-form wait-k policy is computed by every block workgroup (it reads head_step and block 0 writes
 // it: a workgroup that reads the NEW value finds the same step again, the minimum over candidates >= head_step is idempotent).
 // full != 0 (SIMULST_ATTN_FULL): no policy -- every block below len is live, head_step / head_read / tgt_idx are not touched.
-constexpr int KB_KEYS = 256;
+constexpr int KB_KEYS = SL_CROSS_KEY_BLOCK;
 template <typename T, int NP>
 __global__ __launch_bounds__(256, NP >= 16 ? 2 : 4) void waitk_cross_attn_block_kernel(
     const T* __restrict__ qs, const T* __restrict__ Ks, const T* __restrict__ Vc, const int* __restrict__ key_len,
@@ -620,18 +621,6 @@ __global__ void embed_first_kernel(const long* __restrict__ tokens, const T* __r
     x[(long)slot * D + c] = from_f32<T>(scale * to_f32(E[tok * D + c]) + pos[pr * D + c]);
 }
 
-int lin(simulst_handle* h, int dtype, int B, int N, int K, const void* A, const void* W, const float* bias,
-        const void* R, void* C, int epi, const float* ln_g, const float* ln_b, int w_packed = 0) {
-  simulst_linear_desc d;
-  d.M_batches = 1; d.rows_per_batch = B; d.N = N; d.K = K;
-  d.a_batch_stride = 0; d.a_row_stride = K; d.a_lead = 0;
-  d.c_batch_stride = 0; d.c_row_stride = N;
-  d.r_batch_stride = 0; d.r_row_stride = N;
-  d.epilogue = epi; d.dtype = dtype; d.scale = 1.f; d.n_main = 0; d.aux_rows = 0; d.aux_batch_stride = 0;
-  d.ln_gamma = ln_g; d.ln_beta = ln_b; d.w_fragment_major = w_packed; d.c_head_dim = 0; d.c_head_stride = 0; d.c_tensor_heads = 0; d.c_tensor_stride = 0;
-  return simulst_linear(h, &d, A, W, bias, R, C, nullptr);
-}
-
 template <typename T>
 int launch_policy_cross(simulst_handle* h, const void* qm, const void* qs, const void* Km, const void* Ks,
                         const void* Vc, float energy_bias, const int32_t* key_len, const int32_t* tgt_idx,
@@ -831,6 +820,141 @@ extern "C" int simulst_mma_decode(simulst_handle* h, const simulst_decoder_desc*
   return SIMULST_OK;
 }
 
+// one call of the step loop: what the blocks of a step share
+struct DecodeCall {
+  simulst_handle* h;
+  const simulst_decoder_desc* dd;
+  const simulst_dec_layer* layers;
+  int64_t* tokens_io;
+  int64_t* out_tokens;
+  sl_decode_call in;                             // in.B: rows of every launch (under compaction: the slots)
+  sl_decode_plan plan;
+  sl_step_bufs bufs;
+  StreamCtl ctl;                                 // all null unless in.mode == SL_CALL_STREAM
+  int np_base, mask_eos;
+};
+
+// the input embeddings of the rows (row_map: of the slots) in front of a step
+static int launch_embed(const DecodeCall& c, const int* row_map) {
+  const simulst_decoder_desc* dd = c.dd;
+  if (dd->dtype == SIMULST_F32)
+    hipLaunchKernelGGL(embed_first_kernel<float>, dim3(c.in.B), dim3(256), 0, c.h->stream, (const long*)c.tokens_io, (const float*)dd->E,
+                       dd->pos_table, dd->n_prev, (float*)dd->x, dd->D, dd->pad_idx, dd->embed_scale, row_map);
+  else
+    hipLaunchKernelGGL(embed_first_kernel<bf16>, dim3(c.in.B), dim3(256), 0, c.h->stream, (const long*)c.tokens_io, (const bf16*)dd->E,
+                       dd->pos_table, dd->n_prev, (bf16*)dd->x, dd->D, dd->pad_idx, dd->embed_scale, row_map);
+  return sl_launch_status(c.h, row_map ? "simulst_mma_stream_steps(compaction + embedding)" : "simulst_mma_decode(embed)");
+}
+
+// LN1 + QKV, self-attention, out-proj + residual of layer l, as far as the plan gives them launches of their own.  Head-split block: hs
+// and xin tell the policy launch where the partials and the residual row are.
+static int self_attention_block(const DecodeCall& c, int s, int l, HeadSplit& hs, const void*& xin) {
+  simulst_handle* h = c.h;
+  const simulst_decoder_desc* dd = c.dd;
+  const simulst_dec_layer& L = c.layers[l];
+  const int B = c.in.B, D = dd->D, H = dd->H, d = D / H, dt = dd->dtype, np = c.in.np_uniform < 0 ? -1 : c.in.np_uniform + s;
+  int rc;
+  if (c.plan.split) {
+    rc = sl_self_attention_fused(h, dd->x, L.ln1_g, L.ln1_b, L.wqkv, L.bqkv, L.wo, L.k_cache, L.v_cache, dd->n_prev, np,
+                                 dd->partial_self, B, H, d, dd->cap, dt);
+    hs.po = dd->partial_self; hs.bo = L.bo; hs.x_mid = dd->x_mid;
+    xin = dd->x_mid;
+    return rc;
+  }
+  if (l == 0 && s > 0 && c.plan.fuse_commit)     // the previous step's pairs: its commit + this step's embedding ride with LN1 + QKV
+    rc = sl_dec_embed_qkv_chain(h, (const float2*)dd->logits, c.plan.n_pairs, c.tokens_io, c.out_tokens + (long)(s - 1) * B, dd->n_prev,
+                                c.in.np_uniform + s - 1, dd->E, dd->pos_table, dd->embed_scale, dd->pad_idx, dd->x, L.ln1_g, L.ln1_b,
+                                L.wqkv, L.bqkv, dd->qkv, B);
+  else
+    rc = sl_step_qkv(h, c.plan, c.bufs, l, l > 0 ? c.layers[l - 1].b2 : nullptr, sl_qkv_of(L));
+  if (rc) return rc;
+  if (!c.plan.attn_chain)
+    if ((rc = sl_self_attention(h, dd->qkv, L.k_cache, L.v_cache, dd->n_prev, np, dd->ctx, B, H, d, dd->cap, dt,
+                                c.in.compact ? c.ctl.row_map : nullptr))) return rc;
+  if (!c.plan.chain)
+    return sl_lin(h, dt, B, D, D, dd->ctx, L.wo, L.bo, dd->x, dd->x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, c.bufs.packed);
+  return SIMULST_OK;
+}
+
+// LN2 + query projection(s) + policy + cross-attention of layer l: in ONE launch (fuse_q: each (head, utterance) workgroup normalises
+// its residual row and projects its own 64 query channels), or the projection as a chain / GEMM of its own in front of the policy
+// launch (many rows: every (head, row) workgroup re-streaming its 32 KB of the query projection through L2 costs more than that)
+static int cross_attention_block(DecodeCall& c, int s, int l, const HeadSplit& hs) {
+  simulst_handle* h = c.h;
+  const simulst_decoder_desc* dd = c.dd;
+  const simulst_dec_layer& L = c.layers[l];
+  const int B = c.in.B, D = dd->D, H = dd->H, d = D / H, dt = dd->dtype, pk = c.bufs.packed;
+  const int n_hint = c.in.mode != SL_CALL_OFFLINE ? -1
+                     : (dd->attn_type == SIMULST_ATTN_WAITK && c.in.np_uniform >= 0)
+                           ? (c.in.np_uniform + s + dd->waitk_k) * (dd->ratio < 0 ? -dd->ratio : dd->ratio) : dd->S_cap;
+  const StreamCtl* ctlp = c.in.mode == SL_CALL_STREAM ? &c.ctl : nullptr;
+  const void* Ks = L.Ksoft ? L.Ksoft : L.Kmono;
+  int rc;
+  c.ctl.layer = l + 1;
+  if (c.plan.fuse_q)
+    return policy_cross(h, nullptr, nullptr, L.Kmono, Ks, L.V, L.energy_bias, dd->enc_len, dd->n_prev, L.head_step, L.head_read, dd->ctx,
+                        B, H, d, dd->S_cap, dd->ratio, dd->attn_type, dd->waitk_k, dd->online, dd->mass_preservation, dt, n_hint, dd->x,
+                        L.ln2_g, L.ln2_b, L.c_wq, L.c_bq, L.c_wq_soft, L.c_bq_soft, ctlp, &hs, L.Kpool, dd->P_cap);
+  if (c.plan.attn_chain) {                       // self-attention + out-proj + residual + LN2 + query projection(s): one launch
+    rc = sl_dec_attn_proj_chain(h, dd->qkv, L.k_cache, L.v_cache, dd->n_prev, c.in.np_uniform < 0 ? -1 : c.in.np_uniform + s, dd->cap, dd->x,
+                                L.wo, L.bo, L.ln2_g, L.ln2_b, L.c_wq, L.c_bq, dd->q, L.c_wq_soft, L.c_bq_soft, dd->q2, B);
+  } else if (c.plan.proj_cross && !L.c_wq_soft) {
+    // experiment: the chain and the wait-k cross-attention in one launch (dec_chain.hip dec_proj_cross_fused_kernel)
+    return sl_dec_proj_cross_fused(h, dd->ctx, dd->x, L.wo, L.bo, L.ln2_g, L.ln2_b, L.c_wq, L.c_bq, dd->q, Ks, L.V, dd->enc_len,
+                                   dd->n_prev, L.head_step, L.head_read, dd->ctx, B, H, dd->S_cap, dd->ratio, dd->waitk_k, dd->online,
+                                   dd->mass_preservation, n_hint);
+  } else if (c.plan.chain) {
+    rc = sl_dec_proj_chain(h, dd->ctx, dd->x, L.wo, L.bo, L.ln2_g, L.ln2_b, L.c_wq, L.c_bq, dd->q, L.c_wq_soft, L.c_bq_soft, dd->q2, B);
+  } else {
+    rc = sl_lin(h, dt, B, D, D, dd->x, L.c_wq, L.c_bq, nullptr, dd->q, SIMULST_EPI_BIAS, L.ln2_g, L.ln2_b, pk);
+    if (!rc && L.c_wq_soft)
+      rc = sl_lin(h, dt, B, D, D, dd->x, L.c_wq_soft, L.c_bq_soft, nullptr, dd->q2, SIMULST_EPI_BIAS, L.ln2_g, L.ln2_b, pk);
+  }
+  if (rc) return rc;
+  return policy_cross(h, dd->q, L.c_wq_soft ? dd->q2 : dd->q, L.Kmono, Ks, L.V, L.energy_bias, dd->enc_len, dd->n_prev, L.head_step,
+                      L.head_read, dd->ctx, B, H, d, dd->S_cap, dd->ratio, dd->attn_type, dd->waitk_k, dd->online, dd->mass_preservation,
+                      dt, n_hint, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ctlp, nullptr, L.Kpool, dd->P_cap);
+}
+
+// Vocabulary projection + greedy pick + commit of step s.  Where the plan fuses the pick into the projection, dd->logits holds
+// (value, index) pairs per row and column range instead of fp32 rows; where it fuses the commit into the next step's first launch,
+// only the last step of the call commits here.
+static int close_step(const DecodeCall& c, int s, int n_steps) {
+  simulst_handle* h = c.h;
+  const simulst_decoder_desc* dd = c.dd;
+  const int B = c.in.B, D = dd->D, V = dd->V, dt = dd->dtype;
+  const float* last_b2 = c.layers[dd->n_layers - 1].b2;
+  const bool stream = c.in.mode == SL_CALL_STREAM;
+  const int skip_pad = stream ? -1 : dd->pad_idx;
+  const bool no_eos = !stream && (c.mask_eos || (c.in.np_uniform >= 0 && c.in.np_uniform + s == 0));
+  int rc;
+  if ((rc = sl_step_last_slabs(h, c.plan, c.bufs, last_b2))) return rc;
+  if (c.plan.vsplit)
+    rc = sl_dec_vocab_chain(h, dd->x_mid, dd->x, dd->ffn_partial, last_b2, dd->ln_g, dd->ln_b, dd->out_proj, (float2*)dd->logits, B,
+                            dd->F, V, c.plan.vsplit, skip_pad, no_eos ? dd->eos_idx : -1);
+  else if (c.plan.tile_argmax)
+    rc = sl_launch_vocab_argmax(h, dd->x, dd->out_proj, dd->ln_g, dd->ln_b, (float2*)dd->logits, B, V, D, skip_pad,
+                                no_eos ? dd->eos_idx : -1);
+  else
+    rc = sl_lin(h, dt, B, V, D, dd->x, dd->out_proj, nullptr, nullptr, dd->logits, SIMULST_EPI_BIAS_F32OUT, dd->ln_g, dd->ln_b,
+                c.bufs.packed);
+  if (rc) return rc;
+  if (c.plan.fuse_commit && s + 1 < n_steps) return SIMULST_OK;      // committed by the next step's first launch
+  const float2* part = c.plan.n_pairs ? (const float2*)dd->logits : nullptr;
+  const int n_part = c.plan.vsplit ? c.plan.vsplit : V / 64;
+  long* out_row = (long*)c.out_tokens + (c.in.mode != SL_CALL_OFFLINE ? 0 : (long)s * B);
+  KTimer t(h, SIMULST_K_ARGMAX);
+  if (dt == SIMULST_F32)
+    hipLaunchKernelGGL(argmax_embed_kernel<float>, dim3(B), dim3(256), 0, h->stream, dd->logits, (long*)c.tokens_io, out_row, dd->n_prev,
+                       (const float*)dd->E, dd->pos_table, (float*)dd->x, V, D, dd->pad_idx, dd->eos_idx, c.mask_eos, dd->embed_scale, B,
+                       c.np_base, c.ctl, part, n_part);
+  else
+    hipLaunchKernelGGL(argmax_embed_kernel<bf16>, dim3(B), dim3(256), 0, h->stream, dd->logits, (long*)c.tokens_io, out_row, dd->n_prev,
+                       (const bf16*)dd->E, dd->pos_table, (bf16*)dd->x, V, D, dd->pad_idx, dd->eos_idx, c.mask_eos, dd->embed_scale, B,
+                       c.np_base, c.ctl, part, n_part);
+  return sl_launch_status(h, "simulst_mma_decode(argmax)");
+}
+
 static int run_decode(simulst_handle* h, const simulst_decoder_desc* dd, const simulst_dec_layer* layers,
                       int64_t* tokens_io, int64_t* out_tokens, int32_t n_steps, int32_t mask_eos, bool do_embed,
                       bool device_indexed, const StreamCtl* ctlp) {
@@ -861,195 +985,39 @@ static int run_decode(simulst_handle* h, const simulst_decoder_desc* dd, const s
     SL_REQUIRE(h, !ctl.p_probe && !ctl.step_probe && !ctl.step_force, SIMULST_E_ARG, "simulst_mma_stream_steps: the audit hooks index by stream");
     do_embed = false;                            // every round embeds after its own compaction
   }
-  if (do_embed) {
-    KTimer t(h, SIMULST_K_MISC);
-    if (dt == SIMULST_F32)
-      hipLaunchKernelGGL(embed_first_kernel<float>, dim3(B), dim3(256), 0, h->stream, (const long*)tokens_io,
-                         (const float*)dd->E, dd->pos_table, dd->n_prev, (float*)dd->x, D, dd->pad_idx, dd->embed_scale);
-    else
-      hipLaunchKernelGGL(embed_first_kernel<bf16>, dim3(B), dim3(256), 0, h->stream, (const long*)tokens_io,
-                         (const bf16*)dd->E, dd->pos_table, dd->n_prev, (bf16*)dd->x, D, dd->pad_idx, dd->embed_scale);
-    if ((rc = sl_launch_status(h, "simulst_mma_decode(embed)")) != 0) return rc;
-  }
   // weights of the step GEMMs / GEMVs in fragment-major order (1 KB contiguous per wave load)
   const int pk = dd->weights_fragment_major;
   SL_REQUIRE(h, !pk || (D % 64 == 0 && F % 64 == 0 && V % 16 == 0 && d % 16 == 0), SIMULST_E_SHAPE,
              "simulst_mma_decode: fragment-major weights need D, F multiples of 64, V and head_dim of 16");
-  // FULL over more than 256 keys: the blocked kernel reads a separate query, so the <= 128-row class runs LN2 + q-proj as a GEMM
-  const bool full_blocked = dd->attn_type == SIMULST_ATTN_FULL && dd->S_cap > KB_KEYS && !h->force_unfused_decode;
-  // head-split self-attention block (decode_fused.hip): 5 launches per layer instead of 7 when the host supplied the
-  // partial buffer, the weights are fragment-major and the shapes fit (cached target positions <= 256)
-#ifdef SL_EXPERIMENTS
-  const bool split = !full_blocked && pk && dd->x_mid && dd->partial_self && !h->force_unfused_decode &&
-                     sl_self_attention_fused_ok(H, d, dd->cap) && B <= 128 && (dt == SIMULST_BF16 ? D <= 512 : D <= 256);
-#else
-  const bool split = false;          // decode_fused.hip: measured slower, EXPERIMENTS builds only
-#endif
-  // LN2 + query projection inside the policy/cross-attention launch (few rows: one launch less on the dependent
-  // chain) or as its own GEMM (many rows: no per-workgroup re-read of the projection weights)
-  const bool fuse_q = (split || B <= h->fuse_q_max_rows) && !full_blocked;
-  // row-local chains (dec_chain.hip) for co-scheduled batches: { out-proj + residual, LN + q-proj(s) } in one launch,
-  // { cross out-proj + residual, LN + fc1 + GELU, fc2 + residual } in another -- 5 launches per layer instead of 8-9
-  // (the feed-forward chain is always launched in its hand-off-free form here -- x_mid given, slabs added by the next layer's
-  //  LN + QKV launch -- so the ticket array dd->ffn_sem of the in-launch hand-off is not needed and not touched)
-  const bool chain = !split && !fuse_q && !h->force_unfused_decode && dd->ffn_partial &&
-                     sl_dec_chain_ok(h, dt, B, D, F, pk != 0);
-  const bool chain_ffn = chain && B <= h->dec_chain_ffn_max_rows && dd->x_mid;
-  // round 4: the self-attention of a layer inside its projection chain (4 launches per layer)
-  const bool attn_chain = chain && sl_dec_attn_chain_ok(h, dt, B, H, d, dd->cap);
-  // round 4: a step's commit (fold of the greedy pick's pairs, token, position) + the new embedding ride in the NEXT step's first launch
-  // with layer 0's LayerNorm + QKV (dec_embed_qkv_chain_kernel) -- lockstep offline rows only; the last step of the call commits as before
-  const bool fuse_commit = chain_ffn && !ctlp && !device_indexed && np_uniform >= 0 && h->dec_embed_qkv_chain;
-  // round 5: the feed-forward chain of layer l with the slab sum + LN1 + QKV of layer l + 1 in one launch (dec_ffn_qkv_chain_kernel)
-  const bool fuse_ffn_qkv = chain_ffn && !attn_chain && sl_dec_ffn_qkv_chain_ok(h, B, F);
-  bool qkv_done = false;                         // this layer's QKV came out of the previous layer's feed-forward launch
-  int pending_pairs = 0;                         // pairs of the previous step's projection that no launch has committed yet
+  // the launch path of every step of this call (decode_plan.h)
+  sl_decode_call call = {};
+  call.dtype = dt; call.B = B; call.D = D; call.H = H; call.F = F; call.V = V; call.cap = dd->cap; call.S_cap = dd->S_cap;
+  call.attn_type = dd->attn_type; call.packed = pk != 0;
+  call.x_mid = dd->x_mid != nullptr; call.partial_self = dd->partial_self != nullptr; call.ffn_partial = dd->ffn_partial != nullptr;
+  call.final_ln = dd->ln_g != nullptr && dd->ln_b != nullptr;
+  call.mode = ctlp ? SL_CALL_STREAM : device_indexed ? SL_CALL_GRAPH_STEP : SL_CALL_OFFLINE;
+  call.np_uniform = np_uniform; call.compact = compact; call.mask_eos = mask_eos != 0; call.force_unfused = h->force_unfused_decode;
+  DecodeCall c = {h, dd, layers, tokens_io, out_tokens, call, sl_plan_decode(h, call),
+                  {dt, B, D, F, pk, dd->x, dd->x_mid, dd->qkv, dd->hidden, dd->ffn_partial, dd->ffn_sem}, ctl, np_base, mask_eos};
+  if (do_embed) {
+    KTimer t(h, SIMULST_K_MISC);
+    if ((rc = launch_embed(c, nullptr))) return rc;
+  }
   for (int s = 0; s < n_steps; ++s) {
     if (compact) {                               // this round's slots, then their input embeddings
       KTimer t(h, SIMULST_K_MISC);
       hipLaunchKernelGGL(stream_compact_kernel, dim3(1), dim3(1024), 0, h->stream, ctl.active, B_streams, (int*)ctl.row_map, B);
-      if (dt == SIMULST_F32)
-        hipLaunchKernelGGL(embed_first_kernel<float>, dim3(B), dim3(256), 0, h->stream, (const long*)tokens_io,
-                           (const float*)dd->E, dd->pos_table, dd->n_prev, (float*)dd->x, D, dd->pad_idx, dd->embed_scale, ctl.row_map);
-      else
-        hipLaunchKernelGGL(embed_first_kernel<bf16>, dim3(B), dim3(256), 0, h->stream, (const long*)tokens_io,
-                           (const bf16*)dd->E, dd->pos_table, dd->n_prev, (bf16*)dd->x, D, dd->pad_idx, dd->embed_scale, ctl.row_map);
-      if ((rc = sl_launch_status(h, "simulst_mma_stream_steps(compaction + embedding)")) != 0) return rc;
+      if ((rc = launch_embed(c, ctl.row_map))) return rc;
     }
     for (int l = 0; l < dd->n_layers; ++l) {
-      const simulst_dec_layer& L = layers[l];
       const void* xin = dd->x;                   // residual row entering the cross-attention block
       HeadSplit hs = {nullptr, nullptr, nullptr, pk};
-      if (l == 0 && pending_pairs > 0) {
-        if ((rc = sl_dec_embed_qkv_chain(h, (const float2*)dd->logits, pending_pairs, tokens_io, out_tokens + (long)(s - 1) * B,
-                                         dd->n_prev, np_uniform + s - 1, dd->E, dd->pos_table, dd->embed_scale, dd->pad_idx, dd->x,
-                                         L.ln1_g, L.ln1_b, L.wqkv, L.bqkv, dd->qkv, B))) return rc;
-        pending_pairs = 0;
-        if (!attn_chain)
-          if ((rc = sl_self_attention(h, dd->qkv, L.k_cache, L.v_cache, dd->n_prev, np_uniform + s, dd->ctx, B, H, d, dd->cap, dt))) return rc;
-      } else
-      if (split) {
-        if ((rc = sl_self_attention_fused(h, dd->x, L.ln1_g, L.ln1_b, L.wqkv, L.bqkv, L.wo, L.k_cache, L.v_cache,
-                                          dd->n_prev, np_uniform < 0 ? -1 : np_uniform + s, dd->partial_self, B, H, d,
-                                          dd->cap, dt))) return rc;
-        hs.po = dd->partial_self; hs.bo = L.bo; hs.x_mid = dd->x_mid;
-        xin = dd->x_mid;
-      } else {
-        if (qkv_done) {
-          qkv_done = false;                      // (x and qkv of this layer were written by the previous layer's launch)
-        } else if (chain_ffn && l > 0) {         // the previous layer's feed-forward slabs are added here, then LN1 + QKV
-          if ((rc = sl_dec_qkv_chain(h, dd->x_mid, dd->x, dd->ffn_partial, layers[l - 1].b2, L.ln1_g, L.ln1_b, L.wqkv, L.bqkv,
-                                     dd->qkv, B, F))) return rc;
-        } else {
-          if ((rc = lin(h, dt, B, 3 * D, D, dd->x, L.wqkv, L.bqkv, nullptr, dd->qkv, SIMULST_EPI_BIAS, L.ln1_g, L.ln1_b, pk))) return rc;
-        }
-        if (!attn_chain)
-          if ((rc = sl_self_attention(h, dd->qkv, L.k_cache, L.v_cache, dd->n_prev, np_uniform < 0 ? -1 : np_uniform + s,
-                                      dd->ctx, B, H, d, dd->cap, dt, compact ? ctl.row_map : nullptr))) return rc;
-        if (!chain)
-          if ((rc = lin(h, dt, B, D, D, dd->ctx, L.wo, L.bo, dd->x, dd->x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, pk))) return rc;
-      }
-      // (residual add of the head-split block +) LN2 + query projection(s) + policy + cross-attention in ONE launch:
-      // each (head, utterance) workgroup normalises its residual row and projects its own 64 query channels
-      const int n_hint = device_indexed ? -1
-                         : (dd->attn_type == SIMULST_ATTN_WAITK && np_uniform >= 0)
-                               ? (np_uniform + s + dd->waitk_k) * (dd->ratio < 0 ? -dd->ratio : dd->ratio) : dd->S_cap;
-      ctl.layer = l + 1;
-      if (fuse_q) {
-        if ((rc = policy_cross(h, nullptr, nullptr, L.Kmono, L.Ksoft ? L.Ksoft : L.Kmono, L.V, L.energy_bias, dd->enc_len,
-                               dd->n_prev, L.head_step, L.head_read, dd->ctx, B, H, d, dd->S_cap, dd->ratio,
-                               dd->attn_type, dd->waitk_k, dd->online, dd->mass_preservation, dt, n_hint, dd->x, L.ln2_g,
-                               L.ln2_b, L.c_wq, L.c_bq, L.c_wq_soft, L.c_bq_soft, ctlp ? &ctl : nullptr, &hs, L.Kpool,
-                               dd->P_cap))) return rc;
-      } else {
-        // many rows: every (head, row) workgroup re-streaming its 32 KB of the query projection through L2 costs
-        // more than one LN-prologue GEMM launch that reads the weights once per row tile
-        const void* qsoft = L.c_wq_soft ? dd->q2 : dd->q;
-        if (attn_chain) {                        // self-attention + out-proj + residual + LN2 + query projection(s): one launch
-          if ((rc = sl_dec_attn_proj_chain(h, dd->qkv, L.k_cache, L.v_cache, dd->n_prev, np_uniform < 0 ? -1 : np_uniform + s,
-                                           dd->cap, dd->x, L.wo, L.bo, L.ln2_g, L.ln2_b, L.c_wq, L.c_bq, dd->q, L.c_wq_soft,
-                                           L.c_bq_soft, dd->q2, B))) return rc;
-        } else if (chain && sl_dec_proj_cross_fused_ok(h, dt, B, H, d, dd->S_cap, dd->attn_type, !ctlp && !device_indexed && np_uniform >= 0,
-                                                       L.c_wq_soft != nullptr)) {
-          // experiment: the chain and the wait-k cross-attention in one launch (dec_chain.hip dec_proj_cross_fused_kernel)
-          if ((rc = sl_dec_proj_cross_fused(h, dd->ctx, dd->x, L.wo, L.bo, L.ln2_g, L.ln2_b, L.c_wq, L.c_bq, dd->q, L.Ksoft ? L.Ksoft : L.Kmono,
-                                            L.V, dd->enc_len, dd->n_prev, L.head_step, L.head_read, dd->ctx, B, H, dd->S_cap, dd->ratio,
-                                            dd->waitk_k, dd->online, dd->mass_preservation, n_hint))) return rc;
-          goto cross_done;
-        } else if (chain) {
-          if ((rc = sl_dec_proj_chain(h, dd->ctx, dd->x, L.wo, L.bo, L.ln2_g, L.ln2_b, L.c_wq, L.c_bq, dd->q, L.c_wq_soft,
-                                      L.c_bq_soft, dd->q2, B))) return rc;
-        } else {
-          if ((rc = lin(h, dt, B, D, D, dd->x, L.c_wq, L.c_bq, nullptr, dd->q, SIMULST_EPI_BIAS, L.ln2_g, L.ln2_b, pk))) return rc;
-          if (L.c_wq_soft)
-            if ((rc = lin(h, dt, B, D, D, dd->x, L.c_wq_soft, L.c_bq_soft, nullptr, dd->q2, SIMULST_EPI_BIAS, L.ln2_g, L.ln2_b, pk))) return rc;
-        }
-        if ((rc = policy_cross(h, dd->q, qsoft, L.Kmono, L.Ksoft ? L.Ksoft : L.Kmono, L.V, L.energy_bias, dd->enc_len,
-                               dd->n_prev, L.head_step, L.head_read, dd->ctx, B, H, d, dd->S_cap, dd->ratio,
-                               dd->attn_type, dd->waitk_k, dd->online, dd->mass_preservation, dt, n_hint, nullptr, nullptr,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, ctlp ? &ctl : nullptr, nullptr, L.Kpool, dd->P_cap))) return rc;
-      }
-    cross_done:
-      if (chain_ffn) {
-        if (fuse_ffn_qkv && l + 1 < dd->n_layers) {
-          const simulst_dec_layer& Ln = layers[l + 1];
-          if ((rc = sl_dec_ffn_qkv_chain(h, dd->ctx, dd->x, L.c_wo, L.c_bo, L.ln3_g, L.ln3_b, L.fc1, L.b1, L.fc2, L.b2, dd->ffn_partial,
-                                         B, F, Ln.ln1_g, Ln.ln1_b, Ln.wqkv, Ln.bqkv, dd->qkv))) return rc;
-          qkv_done = true;
-          continue;
-        }
-        if ((rc = sl_dec_ffn_chain(h, dd->ctx, dd->x, L.c_wo, L.c_bo, L.ln3_g, L.ln3_b, L.fc1, L.b1, L.fc2, L.b2,
-                                   dd->ffn_partial, dd->ffn_sem, dd->x_mid, B, F))) return rc;
-        continue;
-      }
-      if ((rc = lin(h, dt, B, D, D, dd->ctx, L.c_wo, L.c_bo, xin, dd->x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, pk))) return rc;
-      if ((rc = lin(h, dt, B, F, D, dd->x, L.fc1, L.b1, nullptr, dd->hidden, SIMULST_EPI_BIAS_GELU, L.ln3_g, L.ln3_b, pk))) return rc;
-      if ((rc = lin(h, dt, B, D, F, dd->hidden, L.fc2, L.b2, dd->x, dd->x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, pk))) return rc;
+      if ((rc = self_attention_block(c, s, l, hs, xin))) return rc;
+      if ((rc = cross_attention_block(c, s, l, hs))) return rc;
+      if ((rc = sl_step_ffn(h, c.plan, c.bufs, dd->ctx, xin, sl_ffn_of(layers[l]),
+                            l + 1 < dd->n_layers ? sl_qkv_of(layers[l + 1]) : sl_qkv_weights{}))) return rc;
     }
-    // greedy pick fused into the vocabulary projection where the shapes allow: dd->logits then holds (value, index) pairs per row
-    // and column range instead of fp32 rows.  The masks must be known when the projection is launched: streaming masks nothing,
-    // forced decoding masks pad + eos, free offline decoding masks eos only at position 0, which the host can tell only for
-    // lockstep rows (np_uniform).
-    const bool eos_first = !ctlp && !mask_eos;                                     // eos masked iff the row is at position 0
-    const bool masks_known = !eos_first || np_uniform >= 0;
-    const bool no_eos = !ctlp && (mask_eos || (np_uniform >= 0 && np_uniform + s == 0));
-    // round 4: the last layer's slab sum, the final LayerNorm, the projection and the partial pick in ONE launch (dec_vocab_chain_kernel)
-    const int vsplit = (chain_ffn && masks_known && h->fused_argmax)
-                           ? sl_dec_vocab_chain_split(h, dt, B, V, D, pk != 0, dd->ln_g != nullptr && dd->ln_b != nullptr) : 0;
-    if (chain_ffn && !vsplit)                    // the last layer's slabs
-      if ((rc = sl_dec_qkv_chain(h, dd->x_mid, dd->x, dd->ffn_partial, layers[dd->n_layers - 1].b2, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, B, F))) return rc;
-    // ... else the per-tile maxima out of the 64 x 64 tile kernel's (or the split row panel's) epilogue: [B][V / 64] pairs
-    const bool amax = vsplit > 0 || (sl_vocab_argmax_ok(h, dt, B, V, D, pk != 0) && masks_known);
-    if (vsplit) {
-      if ((rc = sl_dec_vocab_chain(h, dd->x_mid, dd->x, dd->ffn_partial, layers[dd->n_layers - 1].b2, dd->ln_g, dd->ln_b,
-                                   dd->out_proj, (float2*)dd->logits, B, F, V, vsplit, ctlp ? -1 : dd->pad_idx,
-                                   no_eos ? dd->eos_idx : -1))) return rc;
-    } else if (amax) {
-      if ((rc = sl_launch_vocab_argmax(h, dd->x, dd->out_proj, dd->ln_g, dd->ln_b, (float2*)dd->logits, B, V, D,
-                                       ctlp ? -1 : dd->pad_idx, no_eos ? dd->eos_idx : -1))) return rc;
-    } else if ((rc = lin(h, dt, B, V, D, dd->x, dd->out_proj, nullptr, nullptr, dd->logits, SIMULST_EPI_BIAS_F32OUT, dd->ln_g,
-                         dd->ln_b, pk))) return rc;
-    const int n_pairs_now = amax ? (vsplit ? vsplit : V / 64) : 0;
-    if (fuse_commit && n_pairs_now > 0 && n_pairs_now <= 64 && s + 1 < n_steps) {
-      pending_pairs = n_pairs_now;               // committed by the next step's first launch
-      continue;
-    }
-    {
-      const float2* part = amax ? (const float2*)dd->logits : nullptr;
-      KTimer t(h, SIMULST_K_ARGMAX);
-      if (dt == SIMULST_F32)
-        hipLaunchKernelGGL(argmax_embed_kernel<float>, dim3(B), dim3(256), 0, h->stream, dd->logits, (long*)tokens_io,
-                           (long*)out_tokens + (device_indexed ? 0 : (long)s * B), dd->n_prev, (const float*)dd->E,
-                           dd->pos_table, (float*)dd->x, V, D, dd->pad_idx, dd->eos_idx, mask_eos, dd->embed_scale, B,
-                           np_base, ctl, part, vsplit ? vsplit : V / 64);
-      else
-        hipLaunchKernelGGL(argmax_embed_kernel<bf16>, dim3(B), dim3(256), 0, h->stream, dd->logits, (long*)tokens_io,
-                           (long*)out_tokens + (device_indexed ? 0 : (long)s * B), dd->n_prev, (const bf16*)dd->E,
-                           dd->pos_table, (bf16*)dd->x, V, D, dd->pad_idx, dd->eos_idx, mask_eos, dd->embed_scale, B,
-                           np_base, ctl, part, vsplit ? vsplit : V / 64);
-      if ((rc = sl_launch_status(h, "simulst_mma_decode(argmax)")) != 0) return rc;
-    }
+    if ((rc = close_step(c, s, n_steps))) return rc;
   }
   return SIMULST_OK;
 }

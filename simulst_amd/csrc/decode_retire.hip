@@ -9,7 +9,7 @@
 //   retire_partition_kernel one workgroup: live count, (hole, source) pairs, the small per-row fields, rows_next
 //   retire_move_kernel      workgroup per (pair, layer, head): self K/V [0, n_prev), cross K/V (+ soft keys) [0, enc_len),
 //                           pooled keys of complete windows, in 16-byte copies
-#include "common.h"
+#include "decode_plan.h"
 
 namespace {
 
@@ -155,24 +155,6 @@ __global__ __launch_bounds__(256) void retire_move_kernel(const int* __restrict_
 
 }  // namespace
 
-// the row count below which a shrinking batch would leave the kernel class it started in (the decode loop's switch points of
-// handle.cpp, and the GEMM dispatch's row thresholds above them): tiles of 16 rows, at most the batch
-static int retire_floor_rows(const simulst_handle* h, int B) {
-  int f = 1;
-  if (B > h->dec_chain_ffn_max_rows) f = h->dec_chain_ffn_max_rows + 1;       // layer chains without the feed-forward chain
-  else if (B >= h->dec_chain_min_rows) f = h->dec_chain_min_rows;             // layer chains
-  else if (B > h->fuse_q_max_rows) f = h->fuse_q_max_rows + 1;                // separate query projection, no chains
-  // the decode-step GEMMs outside the chains (the first QKV projection of every call, the vocabulary projection beyond the chains)
-  // take the 64 x 64 tile kernels from 256 rows on (gemm_mid.hip sl_mid_wanted / sl_wave_tile_wanted) and the skinny kernel below:
-  // the two round differently, which flips near-tied greedy picks
-  if (B >= 256 && f < 256) f = 256;
-  if (B >= h->mid_narrow_min_rows && f < h->mid_narrow_min_rows) f = h->mid_narrow_min_rows;
-  if (B >= h->panel_split_min_rows && f < h->panel_split_min_rows) f = h->panel_split_min_rows;
-  if (B > 8192) f = B;                                                         // beyond the decode-step GEMMs' row limit
-  f = (f + 15) / 16 * 16;
-  return f < B ? f : B;
-}
-
 extern "C" int simulst_mma_retire_rows(simulst_handle* h, const simulst_decoder_desc* dd, const simulst_dec_layer* layers,
                                        const int64_t* chunk_tokens, int32_t n_steps, int32_t rows, int32_t B, int32_t* slot_row,
                                        int32_t* row_cap, int64_t* last_tokens, int64_t* hyp, int32_t U, int32_t* enc_len_bh,
@@ -203,7 +185,7 @@ extern "C" int simulst_mma_retire_rows(simulst_handle* h, const simulst_decoder_
                      (const int*)dd->n_prev, slot_row, (const int*)row_cap, (long*)hyp, U, B, dd->pad_idx, dd->eos_idx);
   int rc = sl_launch_status(h, "simulst_mma_retire_rows(scan)");
   if (rc) return rc;
-  hipLaunchKernelGGL(retire_partition_kernel, dim3(1), dim3(1024), 0, h->stream, rows, B, H, dd->n_layers, retire_floor_rows(h, B),
+  hipLaunchKernelGGL(retire_partition_kernel, dim3(1), dim3(1024), 0, h->stream, rows, B, H, dd->n_layers, sl_retire_floor_rows(h, B),
                      slot_row, row_cap, (long*)last_tokens, dd->n_prev, (int*)dd->enc_len, enc_len_bh, L, result);
   if ((rc = sl_launch_status(h, "simulst_mma_retire_rows(partition)"))) return rc;
   // at most rows / 2 pairs: a workgroup per (pair, layer, head), those beyond the device-side pair count leave at once

@@ -425,6 +425,9 @@ int dispatch(simulst_handle* h, int epi, const void* A, const void* W, const flo
 
 }  // namespace
 
+// decode-step shapes: up to 2048 rows, up to 8192 when the caller packed the weights for them (co-scheduled batches)
+int sl_skinny_max_rows(bool packed) { return packed ? 8192 : 2048; }
+
 extern "C" int simulst_linear(simulst_handle* h, const simulst_linear_desc* d, const void* A, const void* W,
                               const float* bias, const void* R, void* C, void* aux) {
   if (!h) return SIMULST_E_NULL;
@@ -467,8 +470,7 @@ extern "C" int simulst_linear(simulst_handle* h, const simulst_linear_desc* d, c
              SIMULST_E_ARG, "simulst_linear: head-major output needs the bias epilogue and head_dim % 8 == 0");
   if (d->ln_gamma || d->ln_beta)
     SL_REQUIRE(h, d->ln_gamma && d->ln_beta, SIMULST_E_NULL, "simulst_linear: LN prologue needs gamma and beta");
-  // decode-step shapes: up to 2048 rows, up to 8192 when the caller packed the weights for them (co-scheduled batches)
-  const bool skinny_ok = M <= (p.w_packed ? 8192 : 2048) && d->a_lead == 0 && d->a_row_stride >= d->K &&
+  const bool skinny_ok = M <= sl_skinny_max_rows(p.w_packed != 0) && d->a_lead == 0 && d->a_row_stride >= d->K &&
                          d->epilogue != SIMULST_EPI_GLU && d->epilogue != SIMULST_EPI_EMF_OUT;
   if (!skinny_ok) {
     if (sl_panel_wanted(d->dtype, d->epilogue, p)) {

@@ -102,8 +102,7 @@ bool sl_mid_wanted(const simulst_handle* h, int dtype, const LinArgs& p);
 int sl_launch_mid(simulst_handle* h, int dtype, int epilogue, const void* A, const void* W, const float* bias,
                   const void* R, void* C, const LinArgs& p);
 // the vocabulary projection of a decode step with the greedy pick's per-tile maxima as its output (bf16, LayerNorm prologue, no bias):
-// partial [B][V / 64] (value, index) pairs; sl_vocab_argmax_ok says whether the shape is taken
-bool sl_vocab_argmax_ok(const simulst_handle* h, int dtype, int B, int V, int D, bool packed);
+// partial [B][V / 64] (value, index) pairs; sl_vocab_argmax_ok (common.h) says whether the shape is taken
 int sl_launch_vocab_argmax(simulst_handle* h, const void* x, const void* W, const float* ln_g, const float* ln_b, float2* partial,
                            int B, int V, int D, int skip_a, int skip_b);
 

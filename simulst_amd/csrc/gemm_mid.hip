@@ -398,6 +398,12 @@ int mid_by_epilogue(simulst_handle* h, int epi, const void* A, const void* W, co
 
 }  // namespace
 
+// rows from which the tile kernels of this file (64 x 64, wave per 16 x 16) replace the skinny kernel, and from which the 64 x 64 one
+// takes narrow outputs as well: the decode loops' retire floor (decode_plan.cpp) keeps a shrinking batch on its side of them
+constexpr int TILE_MIN_ROWS = 256;
+int sl_tile_min_rows() { return TILE_MIN_ROWS; }
+int sl_mid_narrow_min_rows(const simulst_handle* h) { return h->mid_narrow_min_rows; }
+
 // shapes this kernel takes over from the 16 x BN kernel: co-scheduled batches with a wide output
 bool sl_mid_wanted(const simulst_handle* h, int dtype, const LinArgs& p) {
   const int KS = dtype == SIMULST_F32 ? 16 : 32;
@@ -405,8 +411,8 @@ bool sl_mid_wanted(const simulst_handle* h, int dtype, const LinArgs& p) {
   // narrow outputs with a short contraction (out-proj, q-proj: N = 256, K = 256) from mid_narrow_min_rows rows on:
   // one wave per 16 x 16 tile re-reads 16 KB of operands per 131 kflop and is L2-bound there (4096 rows: 9.3 -> 7.9 us
   // out-proj, 12.8 -> 7.6 us LN + q-proj).  fc2 (K = 2048) measured the same on both kernels and keeps the k-split one.
-  const bool narrow = p.N >= 64 && p.N < 512 && p.K <= 8 * KS && p.M >= h->mid_narrow_min_rows;
-  return p.M >= 256 && (p.N >= 512 || narrow) && blocks >= h->mid_min_blocks && p.K % KS == 0 && (!p.ln_g || p.K <= 8 * KS);
+  const bool narrow = p.N >= 64 && p.N < 512 && p.K <= 8 * KS && p.M >= sl_mid_narrow_min_rows(h);
+  return p.M >= TILE_MIN_ROWS && (p.N >= 512 || narrow) && blocks >= h->mid_min_blocks && p.K % KS == 0 && (!p.ln_g || p.K <= 8 * KS);
 }
 
 // the decode loops' vocabulary projection with the greedy pick's per-tile maxima as output: the shapes the 64 x 64 tile kernel
@@ -438,7 +444,7 @@ int sl_launch_vocab_argmax(simulst_handle* h, const void* x, const void* W, cons
 // narrow outputs of co-scheduled batches with a short contraction: one wave per tile
 bool sl_wave_tile_wanted(int dtype, const LinArgs& p) {
   const int KS = dtype == SIMULST_F32 ? 16 : 32;
-  return p.M >= 256 && p.N < 512 && p.K % KS == 0 && p.K <= 8 * KS;
+  return p.M >= TILE_MIN_ROWS && p.N < 512 && p.K % KS == 0 && p.K <= 8 * KS;
 }
 
 namespace {

@@ -502,8 +502,10 @@ static int split_steps(const simulst_handle* h, const LinArgs& p) {
   return (n_all + nsplit - 1) / nsplit;
 }
 
+int sl_panel_split_min_rows(const simulst_handle* h) { return h->panel_split_min_rows; }
+
 bool sl_panel_split_wanted(const simulst_handle* h, int dtype, int epi, const LinArgs& p) {
-  if (!(dtype == SIMULST_BF16 && p.w_packed && p.M >= h->panel_split_min_rows && p.K <= 256 && p.K % PB_KS == 0 &&
+  if (!(dtype == SIMULST_BF16 && p.w_packed && p.M >= sl_panel_split_min_rows(h) && p.K <= 256 && p.K % PB_KS == 0 &&
         p.N % 16 == 0 && p.N >= 512 && p.a_lead == 0 && p.a_rs >= p.K && (p.c_hd == 0 || p.c_hd % 8 == 0)))
     return false;
   if (p.ln_g ? !(epi == SIMULST_EPI_BIAS || epi == SIMULST_EPI_BIAS_GELU || epi == SIMULST_EPI_BIAS_F32OUT)
