@@ -894,6 +894,43 @@ int simulst_policy_cross_attention(simulst_handle* h, const void* qm, const void
                                    int32_t B, int32_t H, int32_t d, int32_t S_cap, int32_t ratio, int32_t attn_type,
                                    int32_t waitk_k, int32_t online, int32_t mass_preservation, int32_t dtype);
 
+/* ---- whole-target (teacher-forced) decoder pass ------------------------------------
+ * The train-mode FORWARD of MMADecoder (models/mma_model.py:156-220, modules/monotonic_multihead_attention.py:301-352) over a known
+ * target of U positions at once; csrc/teacher_forced.hip.  All three products run on the matrix cores: bf16 MFMAs for bf16
+ * activations, fp32 MFMAs for fp32 activations; fp32 accumulation in both.  head_dim <= 64, B * H <= 65535.
+ *
+ * Causal self-attention: qkv [B][U][3D] -> ctx [B][U][D], query u attends keys 0 .. u (fairseq's buffered_future_mask; no
+ * target padding mask, as in the reference).  Scores (q scaled by head_dim^-0.5) and softmax in fp32, P.V accumulated in fp32,
+ * one rounding to the activation dtype: the rounding points of simulst_decoder_self_attention.  Keys are tiled with a running
+ * maximum and sum, so U is not bounded by LDS. */
+int simulst_decoder_self_attention_causal(simulst_handle* h, const void* qkv, void* ctx, int32_t B, int32_t U, int32_t H,
+                                          int32_t d, int32_t dtype);
+
+/* Head energies of every (target, source) pair: q [B][U][D] (projected; scaled by head_dim^-0.5 inside), K [B][H][S_cap][head_dim]
+ * (the cached head-major projections) -> out [B*H][U][S] fp32, 0 < S <= S_cap <= 4096.
+ *   SOFT      raw energies over all S keys; no padding fill (simulst_expected_soft_attention masks by key_len itself)
+ *   MONOTONIC p_choose of a learned policy in train mode: keys pooled over the PADDED source (ceil(S / |ratio|) windows, no floor
+ *             trim; sign of ratio = pooling type as in simulst_step_p_choose, 'last' needs S >= |ratio|), energy + energy_bias,
+ *             -1e8 on pooled positions j > 0 whose window holds more than pad_threshold padding (key_len [B], NULL: none),
+ *             sigmoid, zero-inserted to source resolution with column S - 1 taking the last pooled value
+ *             (modules/fixed_pre_decision.py:97-167).  ratio 1: no pooling.
+ *   WAITK     q, K unused (may be NULL): target u is the one-hot of pooled position u + waitk_k - 1 clipped to the last pooled
+ *             position that mask leaves valid (utils/p_choose_strategy.py:6-53, online unset), zero-inserted the same way. */
+enum { SIMULST_ENERGY_SOFT = 0, SIMULST_ENERGY_MONOTONIC = 1, SIMULST_ENERGY_WAITK = 2 };
+int simulst_mma_energy(simulst_handle* h, const void* q, const void* K, float* out, const int32_t* key_len, float energy_bias,
+                       float pad_threshold, int32_t B, int32_t U, int32_t S, int32_t S_cap, int32_t H, int32_t d, int32_t ratio,
+                       int32_t mode, int32_t waitk_k, int32_t dtype);
+
+/* In-place softmax over the key_len[b] (NULL: S) valid keys of every row of energy [B*H][U][S] fp32, zeros behind them: the
+ * attention weights of full encoder-decoder attention (SIMULST_ATTN_FULL) from SOFT energies. */
+int simulst_mma_softmax(simulst_handle* h, float* energy, const int32_t* key_len, int32_t B, int32_t U, int32_t S, int32_t H);
+
+/* Expected context: beta [B*H][U][S] fp32, cast to the activation dtype first (the reference's beta.to(v.dtype)), times
+ * V [B][H][S_cap][head_dim] -> ctx [B][U][D], accumulated in fp32.  Replaces modules/monotonic_multihead_attention.py:401-409
+ * for a whole target. */
+int simulst_mma_context(simulst_handle* h, const float* beta, const void* V, void* ctx, int32_t B, int32_t U, int32_t S,
+                        int32_t S_cap, int32_t H, int32_t d, int32_t dtype);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,7 +167,12 @@ SIGNATURES = {
     "simulst_decoder_slab_sum_qkv": [_vp] * 10 + [_i32, _i32, _i32, _i32],
     "simulst_decoder_vocab_chain": [_vp] * 9 + [_i32] * 7 + [_vp, _i32, _i32],
     "simulst_has_experiments": [],
+    "simulst_decoder_self_attention_causal": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32],
+    "simulst_mma_energy": [_vp, _vp, _vp, _vp, _vp, _f32, _f32] + [_i32] * 10,
+    "simulst_mma_softmax": [_vp, _vp, _vp, _i32, _i32, _i32, _i32],
+    "simulst_mma_context": [_vp, _vp, _vp, _vp] + [_i32] * 7,
 }
+ENERGY_SOFT, ENERGY_MONOTONIC, ENERGY_WAITK = range(3)
 
 # entry points of a `make EXPERIMENTS=1` build (include/simulst_hip.h, SIMULST_EXPERIMENTS): measured-slower kernel families kept for A/B
 EXPERIMENT_SIGNATURES = {

@@ -389,8 +389,7 @@ class MMADecoder:
         of them every step, modules/monotonic_multihead_attention.py:401).  The number of written tokens is taken from
         prev_output_tokens, so a discarded prediction (force_finish) or a READ needs no rollback."""
         if incremental_state is None:
-            raise NotImplementedError("simulst_amd.MMADecoder.forward is the incremental (inference) path; "
-                                      "training-mode forward is out of scope (DESIGN.md section 7)")
+            return self._forward_whole_target(prev_output_tokens, encoder_out, features_only)
         enc = encoder_out["encoder_out"][0]
         T, B = enc.shape[0], enc.shape[1]
         n_written = prev_output_tokens.size(1) - 1
@@ -416,6 +415,94 @@ class MMADecoder:
         logits, action = self.step(st, last, stop_on_read=True)
         return (None if logits is None else logits.unsqueeze(1)), {"action": action, "attn_list": None,
                                                                  "encoder_out": encoder_out}
+
+    def _forward_whole_target(self, prev_output_tokens, encoder_out, features_only: bool):
+        """forward() without an incremental_state: the reference's whole-sequence path (models/mma_model.py:156-220 with
+        buffered_future_mask, MonotonicAttention.forward through monotonic_attention_process_train), forward only.
+        Returns (logits [B, U, V] fp32 -- or the features [B, U, D] with features_only --, {"action": 1, "attn": [None],
+        "attn_list": one {"p_choose", "alpha", "beta"} of [B, H, U, S] fp32 per layer (None per layer for attn_type "full"),
+        "encoder_out", "encoder_padding_mask"}).  Source padding comes from encoder_padding_mask (right padding only).  The
+        reference passes no self-attention padding mask, so the outputs at and behind a row's own target length are unspecified."""
+        enc = encoder_out["encoder_out"][0]
+        T, B = enc.shape[0], enc.shape[1]
+        pad = encoder_out.get("encoder_padding_mask") or []
+        has_pad = len(pad) > 0 and pad[0] is not None and pad[0].numel() > 0
+        lens = (~pad[0]).sum(1) if has_pad else torch.full((B,), T)
+        enc_btd = enc.to(device=self.device, dtype=self.dtype).transpose(0, 1).contiguous()
+        out, attn_list = self.forward_teacher_forced(prev_output_tokens, enc_btd, lens, features_only=features_only)
+        return out, {"action": 1, "attn": [None], "attn_list": attn_list, "encoder_out": encoder_out,
+                     "encoder_padding_mask": pad[0] if has_pad else None}
+
+    def forward_teacher_forced(self, prev_output_tokens: torch.Tensor, enc_btd: torch.Tensor, enc_len: torch.Tensor, *,
+                               features_only: bool = False, want_attn: bool = True):
+        """One pass over a known target: prev_output_tokens [B, U] = [eos] + target[:-1], enc_btd [B, S, D] the encoder states,
+        enc_len [B] the valid source rows (right padding).  Every layer runs over all B * U positions at once: the projections
+        and the feed-forward through simulst_linear, self-attention through simulst_decoder_self_attention_causal, the policy
+        through simulst_mma_energy + the expected-alignment scans, the context through simulst_mma_context.  The cross-attention
+        K / V projections are those of append_encoder_out on a cached state of the batch.  Policies follow the reference's TRAIN
+        mode: pre-decision pooling over the padded source with ceil and no floor trim, expected alignment instead of the step
+        search.  Returns (logits [B, U, V] fp32 or features [B, U, D], attn_list); with want_attn=False the [B*H, U, S]
+        buffers are shared by all layers and attn_list is None."""
+        from ._lib import ENERGY_MONOTONIC, ENERGY_SOFT, ENERGY_WAITK
+        ops, cfg, Wd = self.ops, self.cfg, self.w
+        B, U = prev_output_tokens.shape
+        S = enc_btd.shape[1]
+        D, H = cfg.embed_dim, cfg.num_heads
+        assert U >= 1 and S >= 1 and enc_btd.shape[0] == B
+        st = self._offline_state(B, 0, S, None, None, cache="_teacher_states")
+        self.append_encoder_out(st, enc_btd, enc_len)
+        ensure_positions(Wd, U + cfg.padding_idx + 2)
+        toks = prev_output_tokens.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
+        pos_row = torch.arange(cfg.padding_idx + 1, cfg.padding_idx + 1 + U, device=self.device, dtype=torch.int32).repeat(B)
+        x = ops.embed_tokens(toks, Wd.E, Wd.pos, pos_row, self.embed_scale)              # [B * U, D]
+        thr = cfg.fixed_pre_decision_pad_threshold
+        chunk = cfg.mocha_chunk_size if cfg.attn_type == "chunkwise" else None
+        attn_list, bufs = ([] if want_attn else None), None
+        for l, L in enumerate(Wd.layers):
+            y = ops.layernorm(x, L["ln1_g"], L["ln1_b"])
+            qkv = ops.linear(y, L["wqkv"], L["bqkv"])
+            ctx = ops.decoder_self_attention_causal(qkv.view(B, U, 3 * D), H=H)
+            x = ops.linear(ctx.view(B * U, D), L["wo"], L["bo"], epilogue=EPI_BIAS_RES, residual=x)
+            y = ops.layernorm(x, L["ln2_g"], L["ln2_b"])
+            if want_attn or bufs is None:
+                bufs = [torch.empty(B * H, U, S, device=self.device, dtype=torch.float32) for _ in range(4)]
+            p, alpha, e, beta = bufs
+            if self.full:              # plain encoder-decoder attention: softmax over [0, enc_len), no policy
+                q = ops.linear(y, L["c_wq"], L["c_bq"])
+                ops.mma_energy(q.view(B, U, D), st.Kmono[l], mode=ENERGY_SOFT, S=S, out=e)
+                beta = ops.mma_softmax(e, st.enc_len, H=H)
+            else:
+                if cfg.attn_type == "waitk":
+                    ops.mma_energy(None, st.Kmono[l], mode=ENERGY_WAITK, S=S, B=B, U=U, key_len=st.enc_len, ratio=self.ratio_arg,
+                                   pad_threshold=thr, waitk_k=cfg.waitk_lagging, out=p)
+                    q = ops.linear(y, L["c_wq"], L["c_bq"])            # soft energy shares the monotonic projections
+                else:
+                    q = ops.linear(y, L["c_wq"], L["c_bq"])
+                    ops.mma_energy(q.view(B, U, D), st.Kmono[l], mode=ENERGY_MONOTONIC, S=S, key_len=st.enc_len,
+                                   ratio=self.ratio_arg, energy_bias=L["energy_bias"], pad_threshold=thr, out=p)
+                    if self.separate_soft:
+                        q = ops.linear(y, L["c_wq_soft"], L["c_bq_soft"])
+                ops.expected_alignment(p, key_len=st.enc_len_bh, eps=cfg.attention_eps, out=alpha)
+                if cfg.mass_preservation:
+                    ops.mass_preservation(alpha, st.enc_len_bh)
+                if self.soft:
+                    ops.mma_energy(q.view(B, U, D), st.Ksoft[l] if self.separate_soft else st.Kmono[l], mode=ENERGY_SOFT, S=S, out=e)
+                    ops.expected_soft_attention(alpha, e, st.enc_len_bh, chunk_size=chunk, eps=cfg.attention_eps, out=beta)
+                else:
+                    beta = alpha
+            if want_attn:
+                attn_list.append(None if self.full else {"p_choose": p.view(B, H, U, S), "alpha": alpha.view(B, H, U, S),
+                                                         "beta": beta.view(B, H, U, S)})
+            ctx = ops.mma_context(beta, st.V[l])
+            x = ops.linear(ctx.view(B * U, D), L["c_wo"], L["c_bo"], epilogue=EPI_BIAS_RES, residual=x)
+            y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
+            hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
+            x = ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+        y = ops.layernorm(x, Wd.ln_g, Wd.ln_b)
+        if features_only:
+            return y.view(B, U, D), attn_list
+        logits = ops.linear(y, Wd.out_proj, None, epilogue=EPI_BIAS_F32OUT)
+        return logits.view(B, U, cfg.vocab), attn_list
 
     __call__ = forward
 

@@ -147,6 +147,38 @@ class SimulSTModel(FairseqModelSurface):
                                                                   lenpen=lenpen, nbest=nbest)
         return hypotheses(toks, lengths, scores, pos)
 
+    def score_reference(self, src_tokens, src_lengths, targets, *, return_alignments=False):
+        """eval/generate.py --score-reference (fairseq's SequenceScorer): the encoder once, then ONE decoder pass over
+        [eos] + target[:-1] of every sentence (MMADecoder.forward_teacher_forced).  targets: one EOS-terminated token list per
+        sentence.  Returns per sentence {"tokens", "score", "positional_scores", "alignment": None, "attention": None}, the schema
+        of generate(): positional_scores[u] = log_softmax(logits[u])[target[u]], score their mean.  return_alignments adds
+        "alpha": per layer the expected alignment [H, U_s, S_s] cut to the sentence's own target and source lengths (None per layer
+        for full attention); without it the per-layer [B, H, U, S] buffers are shared by all layers and not kept."""
+        cfg = self.cfg
+        targets = [[int(t) for t in tgt] for tgt in targets]
+        B = len(targets)
+        assert B == src_tokens.size(0) and all(len(t) >= 1 and t[-1] == cfg.eos for t in targets), "one EOS-terminated target per sentence"
+        U = max(len(t) for t in targets)
+        assert U <= cfg.max_target_positions, "target longer than max_target_positions"
+        prev = torch.full((B, U), cfg.padding_idx, dtype=torch.int64)
+        tgt = torch.full((B, U), cfg.padding_idx, dtype=torch.int64)
+        for b, t in enumerate(targets):
+            prev[b, :len(t)] = torch.tensor([cfg.eos] + t[:-1])
+            tgt[b, :len(t)] = torch.tensor(t)
+        enc = self.encoder.forward(src_tokens, src_lengths)
+        logits, attn_list = self.decoder.forward_teacher_forced(prev, enc["encoder_out_btd"], enc["encoder_lengths"],
+                                                                want_attn=return_alignments)
+        pos = self.get_normalized_probs((logits,), log_probs=True).gather(2, tgt.to(logits.device).unsqueeze(-1)).squeeze(-1).cpu()
+        enc_len = [int(n) for n in torch.as_tensor(enc["encoder_lengths"]).tolist()]
+        out = []
+        for b, t in enumerate(targets):
+            ps = pos[b, :len(t)].clone()
+            hyp = {"tokens": torch.tensor(t), "score": ps.mean(), "positional_scores": ps, "alignment": None, "attention": None}
+            if return_alignments:
+                hyp["alpha"] = [None if a is None else a["alpha"][b, :, :len(t), :enc_len[b]].cpu() for a in attn_list]
+            out.append(hyp)
+        return out
+
 
 @register_model("mma_model")
 class MMAModel(SimulSTModel):

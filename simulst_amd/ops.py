@@ -232,10 +232,10 @@ class Ops:
                      "simulst_mma_step_search")
         return head_read, alpha
 
-    def expected_alignment(self, p, key_len=None, eps=1e-6):
-        _chk_contig(p)
+    def expected_alignment(self, p, key_len=None, eps=1e-6, out=None):
+        _chk_contig(p, out)
         BH, U, S = p.shape
-        alpha = torch.empty_like(p)
+        alpha = torch.empty_like(p) if out is None else out
         self.h.check(self.lib.simulst_expected_alignment(self.h.ptr, _p(p), _p(alpha), _p(key_len), BH, U, S, eps),
                      "simulst_expected_alignment")
         return alpha
@@ -247,10 +247,10 @@ class Ops:
                      "simulst_mass_preservation")
         return alpha
 
-    def expected_soft_attention(self, alpha, energy, key_len=None, chunk_size=None, eps=1e-10):
-        _chk_contig(alpha, energy)
+    def expected_soft_attention(self, alpha, energy, key_len=None, chunk_size=None, eps=1e-10, out=None):
+        _chk_contig(alpha, energy, out)
         BH, U, S = alpha.shape
-        beta = torch.empty_like(alpha)
+        beta = torch.empty_like(alpha) if out is None else out
         self.h.check(self.lib.simulst_expected_soft_attention(self.h.ptr, _p(alpha), _p(energy), _p(beta),
                                                               _p(key_len), BH, U, S, int(chunk_size or 0), eps),
                      "simulst_expected_soft_attention")
@@ -349,6 +349,52 @@ class Ops:
                                                               attn_type, int(mass_preservation), dt(Vc)),
                      "simulst_decoder_cross_attention")
         return out, beta
+
+    # ------------------------------------------------------------------ whole-target (teacher-forced) pass
+    def decoder_self_attention_causal(self, qkv, *, H, out=None):
+        """qkv [B, U, 3D] -> ctx [B, U, D]: query u attends keys 0 .. u (simulst_decoder_self_attention_causal)"""
+        _chk_contig(qkv, out)
+        B, U, D3 = qkv.shape
+        D = D3 // 3
+        if out is None:
+            out = torch.empty(B, U, D, device=qkv.device, dtype=qkv.dtype)
+        self.h.check(self.lib.simulst_decoder_self_attention_causal(self.h.ptr, _p(qkv), _p(out), B, U, H, D // H, dt(qkv)),
+                     "simulst_decoder_self_attention_causal")
+        return out
+
+    def mma_energy(self, q, K, *, mode, S, B=None, U=None, key_len=None, ratio=1, energy_bias=0.0, pad_threshold=0.3, waitk_k=0,
+                   out=None):
+        """head energies / step probabilities of every (target, source) pair (simulst_mma_energy): q [B, U, D], K [B, H, S_cap, d]
+        -> [B*H, U, S] fp32.  mode ENERGY_WAITK reads neither q nor K's contents (K still gives the head geometry)."""
+        _chk_contig(q, K, out)
+        Bk, H, S_cap, d = K.shape
+        if q is not None:
+            B, U = q.shape[0], q.shape[1]
+        if out is None:
+            out = torch.empty(B * H, U, S, device=K.device, dtype=torch.float32)
+        self.h.check(self.lib.simulst_mma_energy(self.h.ptr, _p(q), _p(K), _p(out), _p(key_len), float(energy_bias),
+                                                 float(pad_threshold), B, U, int(S), S_cap, H, d, int(ratio), int(mode),
+                                                 int(waitk_k), dt(K)), "simulst_mma_energy")
+        return out
+
+    def mma_softmax(self, energy, key_len, *, H):
+        """in-place softmax over the valid keys of energy [B*H, U, S] (simulst_mma_softmax)"""
+        _chk_contig(energy)
+        BH, U, S = energy.shape
+        self.h.check(self.lib.simulst_mma_softmax(self.h.ptr, _p(energy), _p(key_len), BH // H, U, S, H), "simulst_mma_softmax")
+        return energy
+
+    def mma_context(self, beta, V, out=None):
+        """beta [B*H, U, S] fp32 x V [B, H, S_cap, d] -> ctx [B, U, D] (simulst_mma_context)"""
+        _chk_contig(beta, V, out)
+        B, H, S_cap, d = V.shape
+        BH, U, S = beta.shape
+        assert BH == B * H
+        if out is None:
+            out = torch.empty(B, U, H * d, device=V.device, dtype=V.dtype)
+        self.h.check(self.lib.simulst_mma_context(self.h.ptr, _p(beta), _p(V), _p(out), B, U, S, S_cap, H, d, dt(V)),
+                     "simulst_mma_context")
+        return out
 
     def decoder_proj_chain(self, ctx, x, wo_fm, bo, ln, wq_fm, bq, q=None, wq2_fm=None, bq2=None, q2=None):
         """x <- x + Wo ctx + bo (in place);  q = Wq LN(x) + bq  (and q2 with wq2_fm) in ONE launch
