@@ -369,6 +369,8 @@ int simulst_waitk_p_choose(simulst_handle* h, float* p, const int32_t* key_len, 
  * allowed step, take the FIRST index with p >= 0.5.
  * in : p [BH][S] fp32, head_step [BH] int64 (in/out), src_len [BH] int32 or NULL (= S)
  * out: head_read [BH] uint8, alpha [BH][S] fp32 one-hot (may be NULL).
+ * An EMPTY source (src_len[bh] == 0; the reference cannot run one, its search indexes position -1): no probability is read,
+ * head_step = 0, head_read = !mass_preservation (the forced stop at index len = 0), alpha all zero.
  * Replaces modules/monotonic_multihead_attention.py:196-275. */
 int simulst_mma_step_search(simulst_handle* h, const float* p, int64_t* head_step, uint8_t* head_read,
                             float* alpha, const int32_t* src_len, int32_t BH, int32_t S,
@@ -423,7 +425,7 @@ int simulst_expected_soft_attention(simulst_handle* h, const float* alpha, const
                                     int32_t S, int32_t chunk_size, float eps);
 
 /* Step probabilities for ONE decode step of every utterance, with fixed pre-decision:
- * p [B*H][S_cap] fp32 (zero beyond key_len[b]).
+ * p [B*H][S_cap] fp32 (zero beyond key_len[b]; an empty source, key_len[b] == 0, has a zero row).
  *   q     [B][D]  monotonic-energy query = q_proj(x) (1/sqrt(d) scaling applied inside)
  *   Kmono [B][H][S_cap][head_dim] (HEAD-MAJOR) = k_proj(encoder states), cached by the caller as the source grows
  *         (simulst_linear with c_head_dim writes it in this order).
@@ -499,6 +501,7 @@ int simulst_decoder_self_attention(simulst_handle* h, const void* qkv, void* k_c
  *          inference: the reference's inference softmax ignores the chunk size, :278-293)
  *   FULL : ctx = softmax_{s < key_len[b]}(q.Kc[s]) Vc (a 1-row source attends to its one key); `step` is not read
  *          and may be NULL, beta (if given) holds the softmax weights
+ * An EMPTY source (key_len[b] == 0): the ctx row (and beta) is zero for every attention type and no row of Kc / Vc is loaded.
  * Replaces modules/monotonic_multihead_attention.py:278-297,401-409. */
 int simulst_decoder_cross_attention(simulst_handle* h, const void* q, const void* Kc, const void* Vc,
                                     const int64_t* step, const int32_t* key_len, void* ctx, float* beta,
@@ -887,7 +890,10 @@ int simulst_pool_keys(simulst_handle* h, const void* Kmono, float* Kpool, const 
 /* policy + cross-attention of one layer for one step in ONE launch (simulst_step_p_choose +
  * simulst_mma_step_search + simulst_decoder_cross_attention, same results). qm/qs: monotonic / soft
  * queries [B][D] (qm unused for WAITK and FULL, qs unused for HARD).  FULL: no policy, ctx = softmax over
- * the key_len[b] keys of Ksoft; tgt_idx and Kmono may be NULL, head_step / head_read are not touched (may be NULL). */
+ * the key_len[b] keys of Ksoft; tgt_idx and Kmono may be NULL, head_step / head_read are not touched (may be NULL).
+ * An EMPTY source (key_len[b] == 0, reachable: the offline decode entry points take the caller's lengths as they are) gives what
+ * the three calls give: step probabilities all zero, head_step = 0, head_read = !mass_preservation, a zero ctx row, and no key or
+ * value row is loaded for the gather. */
 int simulst_policy_cross_attention(simulst_handle* h, const void* qm, const void* qs, const void* Kmono,
                                    const void* Ksoft, const void* Vc, float energy_bias, const int32_t* key_len,
                                    const int32_t* tgt_idx, int64_t* head_step, uint8_t* head_read, void* ctx,

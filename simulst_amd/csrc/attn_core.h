@@ -7,8 +7,8 @@
 //                        reduces its quarter of the rows to (max, sum, partial channels) with shuffles, the four
 //                        partials meet in LDS behind ONE workgroup barrier (split softmax)
 //   prefetch / finish    (any other head dim): one K row per thread, scores through LDS, block max / exp / sum
-// Both cover n <= 256 keys (cross-attention over <= 256 encoder frames, self-attention over <= 256 target
-// positions); longer key ranges take `looped`.
+// prefetch2 / finish3 cover n <= 256 keys (cross-attention over <= 256 encoder frames, self-attention over <= 256 target
+// positions); prefetch / finish cover n <= row_lane_rows(d) -- 256 only where d / 4 divides 256; longer key ranges take `looped`.
 #pragma once
 #include "common.h"
 
@@ -69,6 +69,11 @@ template <typename T> struct Regs {
   float v[16][4];                                // up to 16 V rows x 4 channels per thread
 };
 
+// Key rows the row-per-lane pair below covers: its V pass gives d / 4 threads to a row, so the 256 threads hold 256 / (d / 4)
+// row groups (rounded DOWN) of d / 4 rows each -- 252 rows for d = 24, 250 for d = 40; the threads behind the last whole group
+// take no part.  Callers send longer key ranges to `looped`.
+__host__ __device__ inline int row_lane_rows(int d) { return 256 / (d >> 2) * (d >> 2); }
+
 // issue every load; rows >= n_max are clamped to row 0 (values unused)
 template <typename T>
 __device__ __forceinline__ void prefetch(Regs<T>& r, const T* qp, const T* Kb, long ks, const T* Vb, long vs,
@@ -93,7 +98,7 @@ __device__ __forceinline__ void prefetch(Regs<T>& r, const T* qp, const T* Kb, l
   }
 }
 
-// softmax(q.K[0..n)) V from the prefetched registers. n <= n_max <= 256. Threads tid < d return ctx[tid].
+// softmax(q.K[0..n)) V from the prefetched registers. n <= n_max <= row_lane_rows(d). Threads tid < d return ctx[tid].
 // q_lds != nullptr: the (already scaled) query is read from LDS instead of the prefetched registers.
 template <typename T>
 __device__ __forceinline__ float finish(const Regs<T>& r, int n, int d, float qscale, float* sc, float* red,

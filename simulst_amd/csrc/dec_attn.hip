@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const T* __restrict__ qk
       }
       o = attn::finish3<T, NP>(r, n, n, rsqrtf((float)d), red, nullptr, nullptr);
     }
-  } else if (n <= 256) {
+  } else if (n <= attn::row_lane_rows(d)) {
     attn::Regs<T> r;
     attn::prefetch<T>(r, row + h * d, Kh, d, Vh, d, n, d, np, row + D + h * d, row + 2 * D + h * d);
     if (tid < d) {                                      // append for the following steps
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const T* __restrict__ q
     // (step == len) attends to nothing (monotonic_multihead_attention.py:261-275)
     const long scl = st < 0 ? 0 : (st > len - 1 ? len - 1 : st);
     const bool dead = (!mass_pres) && st == len;
-    if (!dead) {
+    if (!dead && len > 0) {                    // an empty source has no row to gather: zero ctx and beta, no load
       if (tid < d) o = to_f32(Vh[scl * d + tid]);
       if (bt && tid == 0) bt[scl] = 1.f;
     }
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const T* __restrict__ q
           attn::prefetch2<T, NP>(r, q + (long)b * D + h * d, Kh, d, Vh, d, n, -1, nullptr, nullptr);
           o = attn::finish3<T, NP>(r, n, n, rsqrtf((float)d), red, bt);
         }
-      } else if (n <= 256) {
+      } else if (n <= attn::row_lane_rows(d)) {
         attn::Regs<T> r;
         attn::prefetch<T>(r, q + (long)b * D + h * d, Kh, d, Vh, d, n, d, -1, nullptr, nullptr);
         o = attn::finish<T>(r, n, d, rsqrtf((float)d), sc, red, bt);

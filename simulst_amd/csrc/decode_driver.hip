@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
     if (ctl.step_force) { const long f = ctl.step_force[(long)(ctl.layer - 1) * gridDim.y * H + r]; if (f >= 0) found = (int)f; }
     if (lane == 0) {
       const int clampi = min(max(found, 0), len - 1);
-      const bool hr = found == max_steps && pl[clampi] < 0.5f;
+      const bool hr = found == max_steps && (clampi < 0 || pl[clampi] < 0.5f);   // clampi < 0: an empty source (len == 0)
       head_step[r] = found;
       head_read[r] = hr ? 1 : 0;
       if (ctl.read_flag && hr && online) ctl.read_flag[b] = (unsigned char)ctl.layer;   // same-value race between heads
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
   if (!soft) {
     const long scl = st < 0 ? 0 : (st > len - 1 ? len - 1 : st);
     const bool dead = (!mass_pres) && st == len;
-    if (!dead && tid < d) o = to_f32(Vh[scl * d + tid]);
+    if (!dead && len > 0 && tid < d) o = to_f32(Vh[scl * d + tid]);   // an empty source has no row to gather: zero, no load
   } else {
     const int n = (int)(st < len - 1 ? st : len - 1) + 1;
     if ((st > 0 || full) && n > 0) {                    // FULL has no "zero while the head has not moved" rule

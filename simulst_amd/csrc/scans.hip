@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void step_search_kernel(const float* __restric
   }
   if (found < 0) found = 0;                      // unreachable: the forced 1.0 always hits
   const int clampi = min(max(found, 0), len - 1);
-  const float p_i = pr[clampi];
+  const float p_i = clampi >= 0 ? pr[clampi] : 0.f;   // clampi < 0: an empty source (len == 0), nothing to read
   const bool dead = (!mass_pres) && found == max_steps;
   if (alpha)
     for (int j = lane; j < S; j += 64) alpha[(long)r * S + j] = (j == clampi && !dead) ? 1.f : 0.f;
