@@ -937,6 +937,44 @@ int simulst_mma_softmax(simulst_handle* h, float* energy, const int32_t* key_len
 int simulst_mma_context(simulst_handle* h, const float* beta, const void* V, void* ctx, int32_t B, int32_t U, int32_t S,
                         int32_t S_cap, int32_t H, int32_t d, int32_t dtype);
 
+/* ---- transducer inference (models/transducer_model.py:28-212; csrc/transducer.hip) ----------------------------------------
+ * Every entry point below refuses with SIMULST_E_ARG, BEFORE it looks at a pointer: an unknown dtype, D % 32 != 0, V < 4, k < 1,
+ * S' < 1 (T_max < 1), a blank index outside [0, V), n_split outside [1, 64].
+ *
+ * AvgPool1dTBCPad (:79-98): x [B][S_in][D] rows (batch stride x_batch_stride elements), lengths [B], T_max = the batch's longest
+ * valid length (the reference's time dimension, <= S_in), window k.  y [B][S'][D], S' = ceil(T_max / k):
+ *   y[b][j] = (sum of x[b][t], t in [jk, min(jk + k, T_max)), t < lengths[b]) / (min(jk + k, T_max) - jk)
+ *   times k / r at j = (lengths[b] - 1) / k when lengths[b] < T_max, r = (lengths[b] - 1) % k + 1   -- so a row's pooled states
+ *   depend on the batch's T_max; positions j >= ceil(lengths[b] / k) are zero.  new_len[b] = ceil(lengths[b] / k). */
+int simulst_transducer_pool(simulst_handle* h, const void* x, const int32_t* lengths, void* y, int32_t* new_len, int32_t B,
+                            int32_t S_in, int32_t D, int64_t x_batch_stride, int32_t T_max, int32_t k, int32_t dtype);
+
+/* Joiner scan of one decode step (:60-76 with one target position, the argmax of :191).  P fp32 [B][S][D] = source_projection of
+ * the pooled states, g fp32 [B][D] = target_projection of the prediction network's output, W_fm = simulst_pack_fragment_major of
+ * the output projection [ceil(V / 16) * 16][D] (rows >= V zero) in the model dtype.  For every (b, s) with
+ * clamp(prev_emit[b], 0, src_len[b] - 1) <= s < src_len[b], logits = W . tanh(P[b][s] + g[b]) (the tanh rounded to the model
+ * dtype, fp32 accumulation) and part p of the n_split column ranges:
+ *   blank_logit[b][s]           the logit of column `blank` (written by the part that holds that column)
+ *   best[b][s][p], best_idx[..] the largest logit of the part's columns other than `blank` and its lowest index
+ *                               (-inf / INT32_MAX for a part without such a column)
+ * Other positions of the outputs are not written; the [B][S][V] logits never exist.  Row tiles of 16 positions that lie wholly
+ * outside the scanned range are skipped. */
+int simulst_joiner_scan(simulst_handle* h, const float* P, const float* g, const void* W_fm, const int32_t* prev_emit,
+                        const int32_t* src_len, float* blank_logit, float* best, int32_t* best_idx, int32_t B, int32_t S,
+                        int32_t D, int32_t V, int32_t blank, int32_t n_split, int32_t dtype);
+
+/* Emission (:170-209) from the scan's outputs: new_emit[b] = the first scanned s whose best non-blank logit beats the blank one
+ * (ties go to the lower column, as torch.argmax), the blank logit taken as -1e4 at s = src_len[b] - 1.  prev_emit[b] <- new_emit[b],
+ * z[b] = tanh(P[b][new_emit] + g[b]) in the model dtype ([B][D]; the returned vocabulary row is simulst_linear of it),
+ * at_eos[b] = (new_emit[b] == src_len[b] - 1). */
+int simulst_joiner_emit(simulst_handle* h, const float* P, const float* g, const float* blank_logit, const float* best,
+                        const int32_t* best_idx, int32_t* prev_emit, const int32_t* src_len, void* z, int32_t* at_eos, int32_t B,
+                        int32_t S, int32_t D, int32_t V, int32_t blank, int32_t n_split, int32_t dtype);
+
+/* logits fp32 [B][V]: column `blank` of the rows with at_eos[b] != 0 becomes -1e4 (the row gathered at :203-206 keeps the
+ * scatter of :176-180). */
+int simulst_joiner_mask_blank(simulst_handle* h, float* logits, const int32_t* at_eos, int32_t B, int32_t V, int32_t blank);
+
 #ifdef __cplusplus
 }
 #endif

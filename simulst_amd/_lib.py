@@ -171,6 +171,10 @@ SIGNATURES = {
     "simulst_mma_energy": [_vp, _vp, _vp, _vp, _vp, _f32, _f32] + [_i32] * 10,
     "simulst_mma_softmax": [_vp, _vp, _vp, _i32, _i32, _i32, _i32],
     "simulst_mma_context": [_vp, _vp, _vp, _vp] + [_i32] * 7,
+    "simulst_transducer_pool": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i32, _i32],
+    "simulst_joiner_scan": [_vp] * 9 + [_i32] * 7,
+    "simulst_joiner_emit": [_vp] * 10 + [_i32] * 7,
+    "simulst_joiner_mask_blank": [_vp, _vp, _vp, _i32, _i32, _i32],
 }
 ENERGY_SOFT, ENERGY_MONOTONIC, ENERGY_WAITK = range(3)
 

@@ -23,7 +23,7 @@ from typing import Dict, Iterable, List, Mapping, Optional
 
 import torch
 
-from .config import ModelConfig, cif_transformer_s, mma_model_s, s2t_emformer_s
+from .config import ModelConfig, cif_transformer_s, mma_model_s, s2t_emformer_s, transducer_model_s
 from .weights import init_model
 
 
@@ -32,7 +32,8 @@ def config_from_args(args: Mapping) -> ModelConfig:
     defaults of s2t_emformer_s / mma_model_s / cif_transformer_s filling what is absent."""
     g = args.get
     arch = g("arch", "mma_model_s")
-    base = cif_transformer_s() if arch.startswith("cif") else s2t_emformer_s() if arch.startswith("s2t_emformer") else mma_model_s()
+    base = (cif_transformer_s() if arch.startswith("cif") else s2t_emformer_s() if arch.startswith("s2t_emformer") else
+            transducer_model_s() if arch.startswith("transducer_model") else mma_model_s())
     kw = {}
     names = {"conv_channels": "conv_channels", "encoder_embed_dim": "embed_dim", "encoder_ffn_embed_dim": "ffn_dim",
              "encoder_attention_heads": "num_heads", "encoder_layers": "encoder_layers",
@@ -49,6 +50,8 @@ def config_from_args(args: Mapping) -> ModelConfig:
              "cif_highway": "cif_highway", "max_source_positions": "max_source_positions",
              "max_target_positions": "max_target_positions", "no_scale_embedding": "no_scale_embedding",
              "input_feat_per_channel": "input_feat"}
+    if base.model == "transducer_model":         # --downsample (models/transducer_model.py:278-281)
+        names["downsample"] = "downsample"
     for src, dst in names.items():
         if g(src) is not None:
             kw[dst] = g(src)
@@ -56,10 +59,10 @@ def config_from_args(args: Mapping) -> ModelConfig:
         kw["conv_kernel_sizes"] = tuple(int(k) for k in str(g("conv_kernel_sizes")).split(","))
     if arch.startswith("mma") and g("mass_preservation") is None:
         kw["mass_preservation"] = False          # the arch's own default (models/mma_model.py:265), not exp/2-mma.sh's
-    if base.model == "s2t_emformer":             # a plain TransformerDecoder: no policy flags apply
+    if base.model in ("s2t_emformer", "transducer_model"):      # a plain TransformerDecoder: no policy flags apply
         for k in ("simul_attn_type", "waitk_lagging", "mass_preservation", "energy_bias"):
             kw.pop(k, None)
-    if g("waitk_testtime") is not None and base.model != "s2t_emformer":          # inference lagging overrides the training one (:504-506)
+    if g("waitk_testtime") is not None and base.model not in ("s2t_emformer", "transducer_model"):          # inference lagging overrides the training one (:504-506)
         kw["waitk_lagging"] = g("waitk_testtime")
     from dataclasses import replace
     return replace(base, **kw)
@@ -91,6 +94,9 @@ def upgrade_state_dict(state: Mapping[str, torch.Tensor], cfg: ModelConfig, voca
     # shared embeddings: fairseq stores both keys pointing at one tensor; some exports omit one
     if "decoder.output_projection.weight" not in sd and "decoder.embed_tokens.weight" in sd:
         sd["decoder.output_projection.weight"] = sd["decoder.embed_tokens.weight"]
+    if cfg.model == "transducer_model" and "decoder.output_projection.weight" in sd:
+        # the joiner's output projection is the decoder's own module (models/transducer_model.py:110): one tensor, two names
+        sd.setdefault("decoder.joiner.output_projection.weight", sd["decoder.output_projection.weight"])
     missing = [k for k in ref if k not in sd]
     # CIF / CTC projections may be absent from a checkpoint that is only an encoder pre-training
     # (cif_transformer.py:323-337): keep the initialised weights
@@ -104,6 +110,10 @@ def upgrade_state_dict(state: Mapping[str, torch.Tensor], cfg: ModelConfig, voca
         policy = [k for k in sd if re.search(r"encoder_attn\.(energy_bias|[qk]_proj_soft\.)", k)]
         if policy:
             raise KeyError(f"s2t_emformer checkpoint holds {len(policy)} monotonic-attention tensors, e.g. {policy[:4]}")
+    if strict and cfg.model == "transducer_model":    # TransformerDecoder(no_encoder_attn=True) holds no cross-attention
+        stray = [k for k in sd if re.search(r"^decoder\..*encoder_attn", k)]
+        if stray:
+            raise KeyError(f"transducer_model checkpoint holds {len(stray)} encoder-attention tensors, e.g. {stray[:4]}")
     for k, v in ref.items():
         if k in sd and tuple(sd[k].shape) != tuple(v.shape):
             raise ValueError(f"shape mismatch for {k}: checkpoint {tuple(sd[k].shape)} vs model {tuple(v.shape)}")
@@ -220,8 +230,9 @@ def read_checkpoint(path: str, arg_overrides: Optional[Mapping] = None) -> Dict:
         # hydra configs carry the MODEL name in `_name` ('mma_model'), not the architecture ('mma_model_s'): take the one
         # architecture registered for that model, or say what is missing
         from . import cif, model  # noqa: F401  (register the models and archs)
-        from .registry import ARCH_REGISTRY
+        from .registry import ARCH_REGISTRY, ensure_registered
         name = model_args["_name"]
+        ensure_registered(name)
         if name in ARCH_REGISTRY:
             model_args["arch"] = name
         else:

@@ -12,7 +12,7 @@ from typing import Tuple
 
 @dataclass
 class ModelConfig:
-    model: str = "mma_model"                 # mma_model | cif_transformer | s2t_emformer
+    model: str = "mma_model"                 # mma_model | cif_transformer | s2t_emformer | transducer_model
     # fairseq s2t_transformer_s
     input_feat: int = 80
     conv_kernel_sizes: Tuple[int, ...] = (5, 5)
@@ -52,6 +52,8 @@ class ModelConfig:
     cif_beta: float = 1.0
     cif_conv_kernel: int = 3
     cif_highway: bool = False
+    # transducer_model_s (models/transducer_model.py:278-281,306-310): average-pool window over the encoder states
+    downsample: int = 1
 
     # ---- derived (models/s2t_emformer.py:69-73)
     @property
@@ -96,6 +98,13 @@ def s2t_emformer_s(**kw) -> ModelConfig:
     """arch s2t_emformer_s (models/s2t_emformer.py:398-413): the offline CTC + attention ASR model whose decoder is fairseq's
     plain TransformerDecoder -- cross-attention over every valid encoder row, no read/write policy (ctc_layer defaults off)."""
     return replace(ModelConfig(model="s2t_emformer", simul_attn_type="full", ctc_layer=False, mass_preservation=False), **kw)
+
+
+def transducer_model_s(**kw) -> ModelConfig:
+    """arch transducer_model_s (models/transducer_model.py:303-310): the Emformer encoder, an average-pool downsample of 8, a
+    self-attention-only prediction network (TransformerDecoder with no_encoder_attn) and the joiner."""
+    return replace(ModelConfig(model="transducer_model", simul_attn_type="none", ctc_layer=False, mass_preservation=False,
+                               downsample=8), **kw)
 
 
 def cif_transformer_s(**kw) -> ModelConfig:

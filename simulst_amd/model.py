@@ -201,6 +201,9 @@ class S2TEmformerModel(SimulSTModel):
 def refuse_offline_model(model, who: str):
     """The simultaneous agents need a read/write policy; a model with full encoder-decoder attention has none."""
     cfg = getattr(model, "cfg", None)
+    if cfg is not None and cfg.model == "transducer_model":        # the reference has no transducer agent
+        raise ValueError(f"{who}: the transducer_model emits through its joiner and has no simultaneous agent; use "
+                         f"model.generate_offline")
     if cfg is not None and (cfg.model == "s2t_emformer" or cfg.attn_type == "full"):
         raise ValueError(f"{who}: the {cfg.model} model attends to the whole source (full attention, no read/write policy) and "
                          f"cannot be decoded simultaneously; use model.generate / model.generate_offline")

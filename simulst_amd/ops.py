@@ -492,6 +492,61 @@ class Ops:
                                                     eos_idx, int(mask_eos)), "simulst_greedy_argmax")
         return out
 
+    # ------------------------------------------------------------------ transducer (csrc/transducer.hip)
+    def transducer_pool(self, x, lengths, *, T_max, k):
+        """AvgPool1dTBCPad (models/transducer_model.py:79-98): x [B, S_in, D] (rows contiguous, any batch stride), lengths [B] int32,
+        T_max the batch's longest valid length -> (y [B, ceil(T_max / k), D], new lengths [B] int32)."""
+        B, S_in, D = x.shape
+        assert x.stride(2) == 1 and x.stride(1) == D
+        S_out = (max(int(T_max), 1) + max(int(k), 1) - 1) // max(int(k), 1)
+        y = torch.empty(B, S_out, D, device=x.device, dtype=x.dtype)
+        new_len = torch.empty(B, device=x.device, dtype=torch.int32)
+        self.h.check(self.lib.simulst_transducer_pool(self.h.ptr, _p(x), _p(lengths), _p(y), _p(new_len), B, S_in, D, x.stride(0),
+                                                      int(T_max), int(k), dt(x)), "simulst_transducer_pool")
+        return y, new_len
+
+    def pack_joiner_weight(self, W):
+        """output projection [V, D] -> simulst_pack_fragment_major of its rows padded with zeros to a multiple of 16
+        ([ceil(V / 16) * 16, D]), what simulst_joiner_scan reads"""
+        V, D = W.shape
+        V16 = (V + 15) // 16 * 16
+        Wz = W if V16 == V else torch.cat([W, torch.zeros(V16 - V, D, device=W.device, dtype=W.dtype)], 0)
+        return self.pack_fragment_major(Wz.contiguous())
+
+    @staticmethod
+    def joiner_split(B, S, V, dtype):
+        """column ranges of the joiner scan: enough workgroups for the chip's 256 compute units, at least 4 column tiles each"""
+        rows_per_wg = 64 if dtype == torch.bfloat16 else 32
+        row_wgs = max(1, (B * ((S + 15) // 16) * 16 + rows_per_wg - 1) // rows_per_wg)
+        return max(1, min(64, (V + 15) // 16 // 4, (512 + row_wgs - 1) // row_wgs))
+
+    def joiner_scan(self, P, g, W_fm, prev_emit, src_len, blank_logit, best, best_idx, *, V, blank=0):
+        """simulst_joiner_scan: P [B, S, D] fp32, g [B, D] fp32, W_fm from pack_joiner_weight, prev_emit / src_len [B] int32;
+        writes blank_logit [B, S], best / best_idx [B, S, n_split] at the scanned positions only."""
+        _chk_contig(P, g, W_fm, prev_emit, src_len, blank_logit, best, best_idx)
+        B, S, D = P.shape
+        n_split = best.shape[2]
+        assert P.dtype == torch.float32 and g.dtype == torch.float32 and best_idx.dtype == torch.int32
+        self.h.check(self.lib.simulst_joiner_scan(self.h.ptr, _p(P), _p(g), _p(W_fm), _p(prev_emit), _p(src_len), _p(blank_logit),
+                                                  _p(best), _p(best_idx), B, S, D, int(V), int(blank), n_split, dt(W_fm)),
+                     "simulst_joiner_scan")
+
+    def joiner_emit(self, P, g, blank_logit, best, best_idx, prev_emit, src_len, z, at_eos, *, V, blank=0):
+        """simulst_joiner_emit: prev_emit [B] int32 updated IN PLACE, z [B, D] (model dtype) and at_eos [B] int32 written"""
+        _chk_contig(P, g, blank_logit, best, best_idx, prev_emit, src_len, z, at_eos)
+        B, S, D = P.shape
+        self.h.check(self.lib.simulst_joiner_emit(self.h.ptr, _p(P), _p(g), _p(blank_logit), _p(best), _p(best_idx), _p(prev_emit),
+                                                  _p(src_len), _p(z), _p(at_eos), B, S, D, int(V), int(blank), best.shape[2], dt(z)),
+                     "simulst_joiner_emit")
+
+    def joiner_mask_blank(self, logits, at_eos, *, blank=0):
+        _chk_contig(logits, at_eos)
+        B, V = logits.shape
+        assert logits.dtype == torch.float32
+        self.h.check(self.lib.simulst_joiner_mask_blank(self.h.ptr, _p(logits), _p(at_eos), B, V, int(blank)),
+                     "simulst_joiner_mask_blank")
+        return logits
+
     # ------------------------------------------------------------------ beam search (csrc/beam.hip)
     def beam_topk(self, logits, max_len, finished, cand_lp, cand_tok, *, beam, step, pad_idx, eos_idx):
         _chk_contig(logits, max_len, finished, cand_lp, cand_tok)

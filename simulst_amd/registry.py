@@ -112,7 +112,15 @@ for _n, _v in (("hard_aligned", ("hard_aligned", False)), ("infinite_lookback", 
     register_monotonic_attention(_n)(_v)
 
 
+def ensure_registered(name):
+    """The transducer registers on demand (simulst_amd/transducer.py registers nothing at import): asking for its model or arch name
+    is what brings it into the registries."""
+    if isinstance(name, str) and name.startswith("transducer_model") and "transducer_model" not in MODEL_REGISTRY:
+        importlib.import_module(__package__ + ".transducer").register()
+
+
 def build_model(cfg, weights, **kw):
+    ensure_registered(cfg.model)
     return MODEL_REGISTRY[cfg.model](cfg, weights, **kw)
 
 
@@ -120,6 +128,7 @@ def build_model_from_args(args, task=None):
     """``task.build_model(args)`` as fairseq resolves it: arch function fills the defaults, the model class of the
     arch builds the model (agents/default_agent.py:215)."""
     arch = getattr(args, "arch", None)
+    ensure_registered(arch)
     if arch not in ARCH_REGISTRY:
         raise KeyError(f"unknown --arch {arch!r}; registered: {sorted(ARCH_REGISTRY)}")
     model_name, fn = ARCH_REGISTRY[arch]

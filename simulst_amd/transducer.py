@@ -1,0 +1,303 @@
+"""transducer_model on MI355X: inference of models/transducer_model.py:28-212 -- the Emformer encoder, an average-pool
+downsample of its states (AvgPool1dTBCPad, :79-98), a self-attention-only prediction network (fairseq's TransformerDecoder with
+no_encoder_attn, :101-122,158-162) and the joiner (:28-76) with its greedy emission (:163-209).
+
+Per decode step the reference scores every source position of every row against the whole vocabulary,
+``W_out tanh(source_projection(pooled[b, s]) + target_projection(features[b]))``, as a [B, S, V] tensor, and keeps an argmax per
+position.  Here ``P = source_projection(pooled)`` is computed once per utterance, and a step is: the prediction network on the
+per-op kernels, ``g = target_projection(features)``, simulst_joiner_scan (blank logit and best non-blank per remaining position, on
+the matrix cores, never the [B, S, V] tensor), simulst_joiner_emit (the first position whose non-blank wins, the blank forced out
+at the row's last position), and simulst_linear of the emitted position's tanh row.
+
+The module registers nothing at import (the local registries hold the three models of the streaming agents); ``register()`` adds
+``transducer_model`` / ``transducer_model_s``, and registry.build_model_from_args / checkpoint.load call it when that name is asked
+for.  Training (the [B, S, T, V] lattice, :148-156), beam search and the reference's rollback (:214-239, not callable as written)
+are out of scope.
+"""
+import math
+from typing import Dict, List, Optional
+
+import torch
+
+from .config import ModelConfig
+from .decoder import _DecoderLayerView, _Dictionary, ensure_positions, sinusoidal_table
+from .encoder import S2TEmformerEncoder
+from .model import FairseqModelSurface, _default, s2t_emformer_s
+from .ops import EPI_BIAS_F32OUT, EPI_BIAS_GELU, EPI_BIAS_RES, Ops
+
+BLANK = 0          # the blank is bos (models/transducer_model.py:140,176,195)
+BLANK_AT_EOS = -1e4
+
+
+class TransducerWeights:
+    """prediction network + joiner weights on the device"""
+
+    def __init__(self, w: Dict[str, torch.Tensor], cfg: ModelConfig, device, dtype, ops: Ops, prefix="decoder"):
+        f32 = dict(device=device, dtype=torch.float32)
+        act = dict(device=device, dtype=dtype)
+        p = prefix
+
+        def W(name):
+            return w[name].contiguous().to(**act)
+
+        def Bv(name):
+            return w[name].float().contiguous().to(**f32)
+
+        self.E = W(f"{p}.embed_tokens.weight")
+        self.out_proj = W(f"{p}.output_projection.weight")
+        self.pos = sinusoidal_table(cfg.max_target_positions + cfg.padding_idx + 2, cfg.embed_dim, cfg.padding_idx).to(**f32)
+        self._pos_args = (cfg.embed_dim, cfg.padding_idx, f32)
+        self.ln_g, self.ln_b = Bv(f"{p}.layer_norm.weight"), Bv(f"{p}.layer_norm.bias")
+        self.layers = []
+        for l in range(cfg.decoder_layers):
+            lp = f"{p}.layers.{l}"
+            L = {}
+            L["wqkv"] = torch.cat([w[f"{lp}.self_attn.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0).contiguous().to(**act)
+            L["bqkv"] = torch.cat([w[f"{lp}.self_attn.{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0).float().to(**f32)
+            L["wo"], L["bo"] = W(f"{lp}.self_attn.out_proj.weight"), Bv(f"{lp}.self_attn.out_proj.bias")
+            L["ln1_g"], L["ln1_b"] = Bv(f"{lp}.self_attn_layer_norm.weight"), Bv(f"{lp}.self_attn_layer_norm.bias")
+            L["ln3_g"], L["ln3_b"] = Bv(f"{lp}.final_layer_norm.weight"), Bv(f"{lp}.final_layer_norm.bias")
+            L["fc1"], L["b1"] = W(f"{lp}.fc1.weight"), Bv(f"{lp}.fc1.bias")
+            L["fc2"], L["b2"] = W(f"{lp}.fc2.weight"), Bv(f"{lp}.fc2.bias")
+            self.layers.append(L)
+        # joiner (:28-58)
+        self.w_src, self.b_src = W(f"{p}.joiner.source_projection.weight"), Bv(f"{p}.joiner.source_projection.bias")
+        self.w_tgt = W(f"{p}.joiner.target_projection.weight")
+        self.out_proj_fm = ops.pack_joiner_weight(self.out_proj)        # the scan's B operand (rows padded to whole 16-column tiles)
+        torch.cuda.synchronize(device)
+
+
+class TransducerState:
+    """Device-resident incremental state of one hypothesis batch: the self-attention caches, P, src_len', prev_emit, g."""
+
+    def __init__(self, cfg: ModelConfig, B: int, cap: int, device, dtype):
+        H, d = cfg.num_heads, cfg.head_dim
+        self.B, self.cap = B, cap
+        self.k_cache = [torch.zeros(B, H, cap, d, device=device, dtype=dtype) for _ in range(cfg.decoder_layers)]
+        self.v_cache = [torch.zeros(B, H, cap, d, device=device, dtype=dtype) for _ in range(cfg.decoder_layers)]
+        self.n_prev = torch.zeros(B, device=device, dtype=torch.int32)
+        self.n_prev_host = 0
+        self.P = None                    # [B, S', D] fp32
+        self.pooled = None               # [B, S', D] model dtype
+        self.src_len = None              # [B] int32 (src_len')
+        self.prev_emit = torch.zeros(B, device=device, dtype=torch.int32)
+        self.g = None                    # [B, D] fp32, the last step's target projection
+        self.enc_rows = -1               # encoder rows the pooled states were made from (forward())
+        # the emit position BEFORE the step that wrote token t (forward(): a repeated prefix restarts from it)
+        self.emit_before: List[torch.Tensor] = []
+
+    def grow(self, cap: int):
+        def regrow(lst):
+            out = []
+            for t in lst:
+                n = torch.zeros(t.shape[0], t.shape[1], cap, t.shape[3], device=t.device, dtype=t.dtype)
+                n[:, :, :t.shape[2]] = t
+                out.append(n)
+            return out
+        if cap > self.cap:
+            self.k_cache, self.v_cache, self.cap = regrow(self.k_cache), regrow(self.v_cache), cap
+
+
+class TransducerDecoder:
+    """Mirror of models/transducer_model.py:TransducerDecoder (inference, incremental)."""
+
+    STATE_KEY = "simulst_amd.transducer_state"
+
+    def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], device="cuda", dtype=torch.float32,
+                 ops: Optional[Ops] = None, prefix="decoder"):
+        if cfg.downsample < 1:
+            raise ValueError(f"--downsample {cfg.downsample}: a window of at least 1")
+        self.cfg = cfg
+        self.device, self.dtype = torch.device(device), dtype
+        self.ops = ops or Ops()
+        self.w = TransducerWeights(weights, cfg, self.device, dtype, self.ops, prefix)
+        self.embed_scale = 1.0 if cfg.no_scale_embedding else math.sqrt(cfg.embed_dim)
+        self.layers = [_DecoderLayerView(cfg, l) for l in range(cfg.decoder_layers)]
+        self.dictionary = _Dictionary(cfg)
+
+    def max_positions(self):
+        return self.cfg.max_target_positions
+
+    # ------------------------------------------------------------------ source side
+    def new_state(self, B: int, cap: int = 128) -> TransducerState:
+        ensure_positions(self.w, cap + self.cfg.padding_idx + 2)
+        return TransducerState(self.cfg, B, cap, self.device, self.dtype)
+
+    def downsample(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, T: Optional[int] = None):
+        """AvgPool1dTBCPad (:79-98) -> (pooled [B, S', D], src_len' [B] int32).  T: the batch's longest valid length (the reference's
+        time dimension; read from enc_len when not given).  downsample == 1: the reference has no pooling op (:104-108)."""
+        lens = enc_len.to(device=self.device, dtype=torch.int32).contiguous()
+        if T is None:
+            T = int(lens.max().item())
+        T = max(1, min(int(T), enc_btd.size(1)))
+        return self.ops.transducer_pool(enc_btd, lens, T_max=T, k=self.cfg.downsample)
+
+    def set_source(self, st: TransducerState, enc_btd: torch.Tensor, enc_len: torch.Tensor, T: Optional[int] = None):
+        """pool the encoder states and project them once per utterance: P = source_projection(pooled) (:64), fp32"""
+        B, _, D = enc_btd.shape
+        st.pooled, st.src_len = self.downsample(enc_btd.to(self.dtype), enc_len, T)
+        S = st.pooled.size(1)
+        st.P = self.ops.linear(st.pooled.view(B * S, D), self.w.w_src, self.w.b_src, epilogue=EPI_BIAS_F32OUT).view(B, S, D)
+        n_split = Ops.joiner_split(B, S, self.cfg.vocab, self.dtype)
+        st.blank_logit = torch.empty(B, S, device=self.device, dtype=torch.float32)
+        st.best = torch.empty(B, S, n_split, device=self.device, dtype=torch.float32)
+        st.best_idx = torch.empty(B, S, n_split, device=self.device, dtype=torch.int32)
+        st.z = torch.empty(B, D, device=self.device, dtype=self.dtype)
+        st.at_eos = torch.empty(B, device=self.device, dtype=torch.int32)
+        st.prev_emit.zero_()
+        st.emit_before = []
+        st.enc_rows = enc_btd.size(1)
+
+    # ------------------------------------------------------------------ one decode step
+    def features(self, st: TransducerState, last_tokens: torch.Tensor) -> torch.Tensor:
+        """prediction network on the newest token of [bos] + hypothesis (:158-162): TransformerDecoder.extract_features with
+        self-attention + GELU feed-forward layers only -> [B, D]"""
+        ops, cfg, Wd = self.ops, self.cfg, self.w
+        ensure_positions(Wd, st.cap + cfg.padding_idx + 2)
+        if st.n_prev_host == 0:          # prev_output_tokens[:, 0] = bos (:144), whatever the caller's first token is
+            last_tokens = torch.full_like(last_tokens, BLANK)
+        pos_row = (st.n_prev + (cfg.padding_idx + 1)).contiguous()
+        x = ops.embed_tokens(last_tokens, Wd.E, Wd.pos, pos_row, self.embed_scale)
+        for l, L in enumerate(Wd.layers):
+            y = ops.layernorm(x, L["ln1_g"], L["ln1_b"])
+            qkv = ops.linear(y, L["wqkv"], L["bqkv"])
+            ctx = ops.decoder_self_attention(qkv, st.k_cache[l], st.v_cache[l], st.n_prev)
+            x = ops.linear(ctx, L["wo"], L["bo"], epilogue=EPI_BIAS_RES, residual=x)
+            y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
+            hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
+            x = ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+        return ops.layernorm(x, Wd.ln_g, Wd.ln_b)
+
+    def step(self, st: TransducerState, last_tokens: torch.Tensor) -> torch.Tensor:
+        """One target position for every row: last_tokens [B] int64 (the newest of [bos] + hypothesis) -> logits [B, V] fp32 of
+        the position each row emits at (:163-209); st.prev_emit moves there."""
+        ops, V = self.ops, self.cfg.vocab
+        feats = self.features(st, last_tokens.to(device=self.device, dtype=torch.int64).contiguous())
+        st.g = ops.linear(feats, self.w.w_tgt, None, epilogue=EPI_BIAS_F32OUT)            # target_projection, no bias (:40-44)
+        ops.joiner_scan(st.P, st.g, self.w.out_proj_fm, st.prev_emit, st.src_len, st.blank_logit, st.best, st.best_idx, V=V, blank=BLANK)
+        ops.joiner_emit(st.P, st.g, st.blank_logit, st.best, st.best_idx, st.prev_emit, st.src_len, st.z, st.at_eos, V=V, blank=BLANK)
+        logits = ops.linear(st.z, self.w.out_proj, None, epilogue=EPI_BIAS_F32OUT)
+        return ops.joiner_mask_blank(logits, st.at_eos, blank=BLANK)
+
+    def commit(self, st: TransducerState):
+        """Advance the target position after a token is kept (the K/V row appended by step() becomes permanent)."""
+        st.n_prev += 1
+        st.n_prev_host += 1
+        if st.n_prev_host + 1 >= st.cap:
+            st.grow(2 * st.cap)
+
+    def greedy_offline(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, n_steps: int, mask_eos: bool = False,
+                       T: Optional[int] = None):
+        """Batched greedy decode (beam 1; pad never, EOS masked at the first step as SequenceGenerator's min_len 1).
+        Returns (tokens [B, n_steps] int64, emit [B, n_steps] int32 -- the pooled frame each token was emitted at, state)."""
+        cfg, ops = self.cfg, self.ops
+        B = enc_btd.size(0)
+        st = self.new_state(B, cap=n_steps + 2)
+        self.set_source(st, enc_btd, enc_len, T)
+        toks = torch.full((B,), BLANK, device=self.device, dtype=torch.int64)
+        out = torch.empty(n_steps, B, device=self.device, dtype=torch.int64)
+        emit = torch.empty(n_steps, B, device=self.device, dtype=torch.int32)
+        for s in range(n_steps):
+            logits = self.step(st, toks)
+            toks = ops.greedy_argmax(logits, pad_idx=cfg.padding_idx, eos_idx=cfg.eos, mask_eos=mask_eos or s == 0, out=out[s])
+            emit[s].copy_(st.prev_emit)
+            self.commit(st)
+        return out.t().contiguous(), emit.t().contiguous(), st
+
+    # ------------------------------------------------------------------ the reference's call shape
+    def forward(self, prev_output_tokens: torch.Tensor, encoder_out: Optional[Dict[str, List[torch.Tensor]]] = None,
+                incremental_state: Optional[dict] = None, **unused):
+        """TransducerDecoder.forward (:124-212) with an incremental state: prev_output_tokens [B, 1 + written] (its first column is
+        read as bos), encoder_out["encoder_out"][0] [T, B, C] and its padding mask, incremental_state the CALLER's dict (it owns
+        the state).  Returns (logits [B, 1, V] fp32, {"padding_mask": the pooled padding mask [B, S']}).  The written-token count
+        is taken from prev_output_tokens: a call that repeats a prefix (a discarded prediction) restarts from the emit position
+        that prefix had, no rollback call is needed."""
+        if incremental_state is None:
+            raise NotImplementedError("TransducerDecoder.forward without an incremental state is the training lattice [B, S, T, V] "
+                                      "(models/transducer_model.py:148-156), out of scope here")
+        enc = encoder_out["encoder_out"][0]
+        T, B = enc.shape[0], enc.shape[1]
+        n_written = prev_output_tokens.size(1) - 1
+        st = incremental_state.get(self.STATE_KEY)
+        if st is None:
+            st = self.new_state(B, cap=max(32, n_written + 8))
+            incremental_state[self.STATE_KEY] = st
+        if n_written + 2 > st.cap:
+            st.grow(max(2 * st.cap, n_written + 8))
+        if st.enc_rows != T:
+            pad = encoder_out.get("encoder_padding_mask") or []
+            lens = (~pad[0]).sum(1) if len(pad) > 0 and pad[0] is not None and pad[0].numel() > 0 else torch.full((B,), T)
+            self.set_source(st, enc.to(device=self.device, dtype=self.dtype).transpose(0, 1).contiguous(), lens, T=T)
+        if n_written > len(st.emit_before):
+            raise ValueError(f"TransducerDecoder.forward: {n_written} tokens written but only {len(st.emit_before)} steps were taken")
+        if n_written < len(st.emit_before):                      # a repeated prefix: back to where its last step started
+            st.prev_emit.copy_(st.emit_before[n_written])
+            del st.emit_before[n_written:]
+        if st.n_prev_host != n_written:
+            st.n_prev.fill_(n_written)
+            st.n_prev_host = n_written
+        st.emit_before.append(st.prev_emit.clone())
+        logits = self.step(st, prev_output_tokens[:, -1])
+        S = st.P.size(1)
+        padding_mask = torch.arange(S, device=self.device).unsqueeze(0) >= st.src_len.unsqueeze(1)
+        return logits.unsqueeze(1), {"padding_mask": padding_mask, "attn": [None], "inner_states": None}
+
+    def reorder_incremental_state(self, incremental_state, new_order):
+        raise NotImplementedError("beam search for the transducer is not implemented (prev_emit would have to be carried through "
+                                  "simulst_beam_reorder)")
+
+
+class TransducerModel(FairseqModelSurface):
+    """models/transducer_model.py:271-300: S2TEmformerModel's encoder with the TransducerDecoder.  An offline model:
+    generate_offline (greedy); no streaming agent exists for it."""
+
+    def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], device="cuda", dtype=torch.float32,
+                 ops: Optional[Ops] = None):
+        if cfg.model != "transducer_model":
+            raise ValueError(f"TransducerModel builds config.transducer_model_s, not {cfg.model!r}")
+        self.cfg = cfg
+        self._deferred = None
+        self.ops = ops or Ops()
+        self.device, self.dtype = torch.device(device), dtype
+        self.encoder = S2TEmformerEncoder(cfg, weights, device, dtype, self.ops)
+        self.decoder = TransducerDecoder(cfg, weights, device, dtype, self.ops)
+
+    @staticmethod
+    def add_args(parser):
+        """S2TEmformerModel.add_args + --downsample (:273-287)"""
+        FairseqModelSurface.add_args(parser)
+        parser.add_argument("--downsample", type=int)
+
+    def get_normalized_probs(self, net_output, log_probs=True):
+        logits = net_output[0]
+        return torch.log_softmax(logits.float(), -1) if log_probs else torch.softmax(logits.float(), -1)
+
+    def max_decoder_positions(self):
+        return self.cfg.max_target_positions
+
+    def generate_offline(self, src_tokens, src_lengths, n_steps=None, mask_eos=False):
+        """the encoder once, then greedy transducer steps.  Returns tokens [B, n] and a dict with "emit" [B, n] (the pooled frame
+        each token was emitted at), the encoder output and the state.  T = max(encoder_lengths) is read once per batch: the pooled
+        states of a row depend on it (AvgPool1dTBCPad)."""
+        enc = self.encoder.forward(src_tokens, src_lengths)
+        if n_steps is None:
+            n_steps = int(0.1 * src_tokens.size(1) + 10)
+        T = int(enc["encoder_lengths"].max().item())
+        toks, emit, st = self.decoder.greedy_offline(enc["encoder_out_btd"], enc["encoder_lengths"], n_steps, mask_eos, T=T)
+        return toks, {"emit": emit, "encoder": enc, "state": st}
+
+
+def transducer_model_s_arch(args):
+    """models/transducer_model.py:303-310"""
+    _default(args, "downsample", 8)
+    _default(args, "activation_fn", "gelu")
+    s2t_emformer_s(args)
+
+
+def register():
+    """add transducer_model / transducer_model_s to the registries (idempotent)"""
+    from .registry import ARCH_REGISTRY, MODEL_REGISTRY, register_model, register_model_architecture
+    if "transducer_model" not in MODEL_REGISTRY:
+        register_model("transducer_model")(TransducerModel)
+    if "transducer_model_s" not in ARCH_REGISTRY:
+        register_model_architecture("transducer_model", "transducer_model_s")(transducer_model_s_arch)

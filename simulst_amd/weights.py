@@ -99,7 +99,9 @@ def init_model(cfg: ModelConfig, seed: int = 999, ln_jitter: float = 0.02) -> Di
         w[f"{p}.self_attn.out_proj.weight"] = _xavier(gen, D, D)
         w[f"{p}.self_attn.out_proj.bias"] = torch.zeros(D)
         _ln(w, p + ".self_attn_layer_norm", D, gen, ln_jitter)
-        if cfg.model == "cif_transformer":
+        if cfg.model == "transducer_model":        # TransformerDecoder(no_encoder_attn=True): self-attention + feed-forward only
+            pass
+        elif cfg.model == "cif_transformer":
             w[f"{p}.encoder_attn.q_proj.weight"] = _xavier(gen, D, D, s2)
             w[f"{p}.encoder_attn.k_proj.weight"] = _xavier(gen, D, D, s2)
             w[f"{p}.encoder_attn.k_proj.bias"] = _uniform_bias(gen, D, D)
@@ -126,11 +128,19 @@ def init_model(cfg: ModelConfig, seed: int = 999, ln_jitter: float = 0.02) -> Di
                         w[f"{p}.encoder_attn.{n}_soft.{m}"] = w[f"{p}.encoder_attn.{n}.{m}"]
             if cfg.energy_bias and cfg.model != "s2t_emformer":
                 w[f"{p}.encoder_attn.energy_bias"] = cfg.energy_bias_init * torch.ones(1)
-        _ln(w, p + ".encoder_attn_layer_norm", D, gen, ln_jitter)
+        if cfg.model != "transducer_model":
+            _ln(w, p + ".encoder_attn_layer_norm", D, gen, ln_jitter)
         w[p + ".fc1.weight"] = _xavier(gen, F, D)
         w[p + ".fc1.bias"] = torch.zeros(F)
         w[p + ".fc2.weight"] = _xavier(gen, D, F)
         w[p + ".fc2.bias"] = torch.zeros(D)
         _ln(w, p + ".final_layer_norm", D, gen, ln_jitter)
     _ln(w, "decoder.layer_norm", D, gen, ln_jitter)
+    if cfg.model == "transducer_model":
+        # SimpleJoiner (models/transducer_model.py:28-58); its output projection IS the decoder's (:110), the state dict carries
+        # the tensor under both names
+        w["decoder.joiner.source_projection.weight"] = _xavier(gen, D, D, (cfg.encoder_layers + 1) ** -0.5)
+        w["decoder.joiner.source_projection.bias"] = _uniform_bias(gen, D, D)
+        w["decoder.joiner.target_projection.weight"] = _xavier(gen, D, D, (cfg.decoder_layers + 1) ** -0.5)
+        w["decoder.joiner.output_projection.weight"] = w["decoder.output_projection.weight"]
     return w
