@@ -10,6 +10,7 @@
 //            bf16 / 16-byte fp32 loads, coalesced along channels), partial sums reduced through LDS
 // HBM-bound: algorithmic bytes per (b,h) = n keys * 2 * d * sizeof(T).
 #include "attn_core.h"
+#include "policy_core.h"
 
 namespace {
 
@@ -180,18 +181,14 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const T* __restrict__ q
   }
   float o = 0.f;
   if (attn_type == SIMULST_ATTN_HARD) {
-    // alpha one-hot at clamp(step); without mass preservation a head that ran off the end
-    // (step == len) attends to nothing (monotonic_multihead_attention.py:261-275)
-    const long scl = st < 0 ? 0 : (st > len - 1 ? len - 1 : st);
-    const bool dead = (!mass_pres) && st == len;
-    if (!dead && len > 0) {                    // an empty source has no row to gather: zero ctx and beta, no load
-      if (tid < d) o = to_f32(Vh[scl * d + tid]);
-      if (bt && tid == 0) bt[scl] = 1.f;
+    const long row = policy::hard_row(st, len, mass_pres);   // alpha one-hot at it; -1: zero ctx and beta, no load
+    if (row >= 0) {
+      if (tid < d) o = to_f32(Vh[row * d + tid]);
+      if (bt && tid == 0) bt[row] = 1.f;
     }
   } else {
-    // softmax over keys <= step, zeroed if the head has not moved (:278-293)
-    const int n = (int)(st < len - 1 ? st : len - 1) + 1;
-    if ((st > 0 || full) && n > 0) {
+    const int n = policy::attended_keys(st, len, full);
+    if (n > 0) {
       if (NP > 0 && n <= 256) {
         if constexpr (NP > 0) {
           attn::Regs2<T, NP> r;

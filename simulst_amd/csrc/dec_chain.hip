@@ -29,6 +29,7 @@
 // independent, no waiting anywhere (nothing can hang), deterministic (fixed split order in one workgroup).
 #include "gemm_args.h"
 #include "attn_core.h"
+#include "policy_core.h"
 
 namespace {
 

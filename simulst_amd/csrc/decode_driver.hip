@@ -7,6 +7,7 @@
 //   argmax_embed_kernel      : greedy pick + commit (n_prev += 1) + next token's embedding
 // LayerNorms ride as prologues of the following skinny GEMM (simulst_linear_desc.ln_gamma).
 #include "attn_core.h"
+#include "policy_core.h"
 #include "gemv_mfma.h"
 #include "decode_plan.h"
 
@@ -50,6 +51,15 @@ struct StreamCtl {
   int compact_rows;          // slots per round
 };
 
+// streaming row gate: the row is parked / finished, or an EARLIER layer asked for source (the heads of one layer all run);
+// the branch form of the three copies it replaces, kept as it was
+__device__ __forceinline__ bool row_skipped(const StreamCtl ctl, int b) {
+  if (!ctl.active) return false;
+  const unsigned char rf = ctl.read_flag[b];
+  if (!ctl.active[b] || (rf && rf != ctl.layer)) return true;
+  return false;
+}
+
 // head-split projections around the policy kernel (all null: separate GEMM launches do the projections)
 struct HeadSplit {
   const float* po;     // [B][H][D] self-attention output-projection partials to add to the residual row
@@ -92,10 +102,7 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
   const int slot = blockIdx.y;              // row of the step's activations (q, ctx); the stream's state lives at row b
   int brow = slot;
   if (ctl.row_map) { brow = ctl.row_map[slot]; if (brow < 0) return; }
-  if (ctl.active) {   // row parked / finished, or an EARLIER layer asked for source (heads of one layer all run)
-    const unsigned char rf = ctl.read_flag[brow];
-    if (!ctl.active[brow] || (rf && rf != ctl.layer)) return;
-  }
+  if (row_skipped(ctl, brow)) return;
   if (ctl.online) online = ctl.online[brow];
   extern __shared__ float sm[];
   float* q_s = sm;                 // [64]
@@ -218,36 +225,19 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
     }
     __syncthreads();
   }
-  // ---- 1+2. policy.  wait-k in closed form (no LDS rows, no barrier): the one-hot pooled probability sits at pooled
-  //           index wk, i.e. at frame (wk+1)*ratio - 1, and/or at the last frame when the final window is the
-  //           pooled position wk (fixed_pre_decision.py:133-167); the search then is a minimum over <= 3 candidates.
-  //           Every thread computes it; thread 0 publishes.  Other attention types: pooled energies + search below.
+  // ---- 1+2. policy.  wait-k in closed form (policy::waitk_step: no LDS rows, no barrier): every thread computes it, thread 0
+  //           publishes.  Other attention types: pooled energies + search below.
   long st;
   if (full) {
     st = len - 1;                                       // the last key: phase 3 attends over [0, len)
   } else if (attn_type == SIMULST_ATTN_WAITK) {
-    int wk = tg + waitk_k - 1;
-    if (!online) wk = min(wk, P - 1);
-    int s1 = -1, s2 = -1;                               // frames with p = 1
-    if (wk < P) {
-      const int c1 = (wk + 1) * ratio - 1;
-      if (c1 < len) s1 = c1;
-      if (wk == P - 1 && P * ratio >= len) s2 = len - 1;
-    }
-    const int max_steps = mass_pres ? len - 1 : len;
-    int found = max_steps;                              // the forced stop, valid even below head_step
-    if (s1 >= 0 && (long)s1 >= hs) found = min(found, s1);
-    if (s2 >= 0 && (long)s2 >= hs) found = min(found, s2);
-    if (found < 0) found = 0;
+    const policy::Step w = policy::waitk_step(tg, waitk_k, online, P, ratio, len, mass_pres, hs);
+    st = w.found;
     if (tid == 0) {
-      const int clampi = min(max(found, 0), len - 1);
-      const bool one = clampi >= 0 && (clampi == s1 || clampi == s2);
-      const bool hr = found == max_steps && !one;
-      head_step[r] = found;
-      head_read[r] = hr ? 1 : 0;
-      if (ctl.read_flag && hr && online) ctl.read_flag[b] = (unsigned char)ctl.layer;
+      head_step[r] = w.found;
+      head_read[r] = w.read ? 1 : 0;
+      if (ctl.read_flag && w.read && online) ctl.read_flag[b] = (unsigned char)ctl.layer;
     }
-    st = found;
   } else {
   {
     if (!fusedq) {
@@ -285,36 +275,17 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
   }
   __syncthreads();
   for (int s = tid; s < S_cap; s += 256) {
-    float v = 0.f;
-    if (s < len) {
-      if ((s + 1) % ratio == 0 && (s + 1) / ratio - 1 < P) v = pp[(s + 1) / ratio - 1];
-      if (s == len - 1 && P * ratio >= len) v = pp[P - 1];
-    }
-    pl[s] = v;
+    const int j = policy::pooled_index_at(s, len, ratio, P);
+    pl[s] = j >= 0 ? pp[j] : 0.f;
   }
   __syncthreads();
   // ---- 2. step search (wave 0)
   if (tid < 64) {
-    const int max_steps = mass_pres ? len - 1 : len;
-    const int n = mass_pres ? S_cap : S_cap + 1;
-    int found = -1;
-    for (int j0 = 0; j0 < n && found < 0; j0 += 64) {
-      const int j = j0 + lane;
-      float v = 0.f;
-      if (j < n) {
-        v = (j < S_cap) ? pl[j] : 0.f;
-        if ((long)j < hs) v = 0.f;
-        if (j == max_steps) v = 1.f;
-      }
-      const unsigned long long m = __ballot(j < n && v >= 0.5f);
-      if (m) found = j0 + __ffsll((long long)m) - 1;
-    }
-    if (found < 0) found = 0;
+    int found = policy::first_step(pl, S_cap, len, mass_pres, hs, lane);
     if (ctl.step_probe && lane == 0) ctl.step_probe[(long)(ctl.layer - 1) * gridDim.y * H + r] = found;
     if (ctl.step_force) { const long f = ctl.step_force[(long)(ctl.layer - 1) * gridDim.y * H + r]; if (f >= 0) found = (int)f; }
     if (lane == 0) {
-      const int clampi = min(max(found, 0), len - 1);
-      const bool hr = found == max_steps && (clampi < 0 || pl[clampi] < 0.5f);   // clampi < 0: an empty source (len == 0)
+      const bool hr = policy::head_read_of(found, len, mass_pres, policy::p_at_clamp(pl, found, len));
       head_step[r] = found;
       head_read[r] = hr ? 1 : 0;
       if (ctl.read_flag && hr && online) ctl.read_flag[b] = (unsigned char)ctl.layer;   // same-value race between heads
@@ -327,12 +298,11 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : (FQ ? 3 : SL_POLICY_WGS)) void 
   // ---- 3. value aggregation
   float o = 0.f;
   if (!soft) {
-    const long scl = st < 0 ? 0 : (st > len - 1 ? len - 1 : st);
-    const bool dead = (!mass_pres) && st == len;
-    if (!dead && len > 0 && tid < d) o = to_f32(Vh[scl * d + tid]);   // an empty source has no row to gather: zero, no load
+    const long row = policy::hard_row(st, len, mass_pres);
+    if (row >= 0 && tid < d) o = to_f32(Vh[row * d + tid]);   // a dead head / an empty source has no row to gather: zero, no load
   } else {
-    const int n = (int)(st < len - 1 ? st : len - 1) + 1;
-    if ((st > 0 || full) && n > 0) {                    // FULL has no "zero while the head has not moved" rule
+    const int n = policy::attended_keys(st, len, full);
+    if (n > 0) {
       const float* qfused = fusedq ? (Wqs ? qsoft_s : q_s) : nullptr;
       if (fast) {
         if constexpr (NP > 0) o = attn::finish3<T, NP>(rg2, n, n_pref, rsqrtf((float)d), red, nullptr, qfused);
@@ -364,10 +334,7 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : 4) void waitk_cross_attn_block_
     const int* __restrict__ tgt_idx, long* __restrict__ head_step, unsigned char* __restrict__ head_read,
     float* __restrict__ part, int H, int d, int S_cap, int ratio, int waitk_k, int online, int mass_pres, int n_hint,
     StreamCtl ctl, int full) {
-  if (ctl.active) {
-    const unsigned char rf = ctl.read_flag[blockIdx.y];
-    if (!ctl.active[blockIdx.y] || (rf && rf != ctl.layer)) return;
-  }
+  if (row_skipped(ctl, blockIdx.y)) return;
   if (ctl.online) online = ctl.online[blockIdx.y];
   __shared__ float red[attn::RED_FLOATS];
   const int h = blockIdx.x, b = blockIdx.y, kb = blockIdx.z, nblk = gridDim.z, tid = threadIdx.x;
@@ -389,32 +356,16 @@ __global__ __launch_bounds__(256, NP >= 16 ? 2 : 4) void waitk_cross_attn_block_
     attn::prefetch2<T, NP>(rg2, qs + (long)b * D + h * d, Ks + hb + (long)j0 * d, d, Vc + hb + (long)j0 * d, d, n_pref, -1, nullptr, nullptr);
   long st = len - 1;                                   // FULL: keys [0, len)
   if (!full) {
-  // the closed-form wait-k policy of policy_cross_attn_kernel
-  int wk = tg + waitk_k - 1;
-  if (!online) wk = min(wk, P - 1);
-  int s1 = -1, s2 = -1;
-  if (wk < P) {
-    const int c1 = (wk + 1) * ratio - 1;
-    if (c1 < len) s1 = c1;
-    if (wk == P - 1 && P * ratio >= len) s2 = len - 1;
+    const policy::Step w = policy::waitk_step(tg, waitk_k, online, P, ratio, len, mass_pres, hs);
+    if (kb == 0 && tid == 0) {
+      head_step[r] = w.found;
+      head_read[r] = w.read ? 1 : 0;
+      if (ctl.read_flag && w.read && online) ctl.read_flag[b] = (unsigned char)ctl.layer;
+    }
+    st = w.found;
   }
-  const int max_steps = mass_pres ? len - 1 : len;
-  int found = max_steps;
-  if (s1 >= 0 && (long)s1 >= hs) found = min(found, s1);
-  if (s2 >= 0 && (long)s2 >= hs) found = min(found, s2);
-  if (found < 0) found = 0;
-  if (kb == 0 && tid == 0) {
-    const int clampi = min(max(found, 0), len - 1);
-    const bool one = clampi >= 0 && (clampi == s1 || clampi == s2);
-    const bool hr = found == max_steps && !one;
-    head_step[r] = found;
-    head_read[r] = hr ? 1 : 0;
-    if (ctl.read_flag && hr && online) ctl.read_flag[b] = (unsigned char)ctl.layer;
-  }
-  st = found;
-  }
-  const int n = (int)(st < len - 1 ? st : len - 1) + 1;                  // keys [0, n) take part
-  const int nb = ((st > 0 || full) && n > 0) ? max(0, min(n - j0, KB_KEYS)) : 0;   // ... of them in this block (uniform over the workgroup)
+  const int n = policy::attended_keys(st, len, full != 0);             // keys [0, n) take part
+  const int nb = n > 0 ? max(0, min(n - j0, KB_KEYS)) : 0;             // ... of them in this block (uniform over the workgroup)
   float* pw = part + ((long)r * nblk + kb) * (d + 2);
   if (nb <= 0 || n_pref <= 0) {
     if (tid == 0) { pw[0] = -INFINITY; pw[1] = 0.f; }
@@ -431,10 +382,7 @@ template <typename T>
 __global__ __launch_bounds__(64) void cross_attn_merge_kernel(const float* __restrict__ part, T* __restrict__ ctx, int H, int d,
                                                               int nblk, StreamCtl ctl) {
   const int r = blockIdx.x, b = r / H, h = r - b * H, tid = threadIdx.x;
-  if (ctl.active) {
-    const unsigned char rf = ctl.read_flag[b];
-    if (!ctl.active[b] || (rf && rf != ctl.layer)) return;
-  }
+  if (row_skipped(ctl, b)) return;
   const float* p = part + (long)r * nblk * (d + 2);
   float m = -INFINITY;
   for (int k = 0; k < nblk; ++k) m = fmaxf(m, p[k * (d + 2)]);

@@ -66,27 +66,12 @@ __global__ __launch_bounds__(256, 2) void dec_proj_cross_fused_kernel(
     const int nh = n_hint < 0 ? (tg + waitk_k) * ratio : n_hint;
     pr.n_pref = min(S_cap, nh);
     attn::prefetch2<bf16, NP>(rg, nullptr, Ks + hb, d, Vc + hb, d, pr.n_pref, -1, nullptr, nullptr);   // K / V only: no query yet
-    // wait-k policy in closed form, as policy_cross_attn_kernel (decode_driver.hip)
-    int wk = tg + waitk_k - 1;
-    if (!online) wk = min(wk, P - 1);
-    int s1 = -1, s2 = -1;
-    if (wk < P) {
-      const int c1 = (wk + 1) * ratio - 1;
-      if (c1 < pr.len) s1 = c1;
-      if (wk == P - 1 && P * ratio >= pr.len) s2 = pr.len - 1;
-    }
-    const int max_steps = mass_pres ? pr.len - 1 : pr.len;
-    int found = max_steps;
-    if (s1 >= 0 && (long)s1 >= hs) found = min(found, s1);
-    if (s2 >= 0 && (long)s2 >= hs) found = min(found, s2);
-    if (found < 0) found = 0;
+    const policy::Step w = policy::waitk_step(tg, waitk_k, online, P, ratio, pr.len, mass_pres, hs);
     if (tid == 0) {
-      const int clampi = min(max(found, 0), pr.len - 1);
-      const bool one = clampi >= 0 && (clampi == s1 || clampi == s2);
-      head_step[p] = found;
-      head_read[p] = (found == max_steps && !one) ? 1 : 0;
+      head_step[p] = w.found;
+      head_read[p] = w.read ? 1 : 0;
     }
-    pr.st = found;
+    pr.st = w.found;
   };
   auto consume = [&](attn::Regs2<bf16, NP>& rg, const Prob& pr) {
     // the row's query: wait for its tile of the projection chain (one lane polls; acquire; the workgroup meets)
@@ -106,8 +91,8 @@ __global__ __launch_bounds__(256, 2) void dec_proj_cross_fused_kernel(
       rg.q = __builtin_bit_cast(uint4, qv);
     }
     float o = 0.f;
-    const int n = (int)(pr.st < pr.len - 1 ? pr.st : pr.len - 1) + 1;
-    if (pr.st > 0 && n > 0) o = attn::finish3<bf16, NP>(rg, n, pr.n_pref, rsqrtf((float)d), red, nullptr, nullptr);
+    const int n = policy::attended_keys(pr.st, pr.len, false);
+    if (n > 0) o = attn::finish3<bf16, NP>(rg, n, pr.n_pref, rsqrtf((float)d), red, nullptr, nullptr);
     if (tid < d) ctx_out[(long)pr.b * D + pr.h * d + tid] = from_f32<bf16>(o);
   };
   attn::Regs2<bf16, NP> ra, rb;

@@ -2,7 +2,7 @@
 // All fp32; one 64-lane wavefront owns one row and walks it in 64-wide chunks with a carried
 // prefix (wavefront prefix scan by __shfl_up); integer decisions (first p >= 0.5,
 // floor(csum / beta)) are thresholded in fp32 exactly like the reference.
-#include "common.h"
+#include "policy_core.h"
 
 namespace {
 
@@ -28,29 +28,14 @@ __global__ __launch_bounds__(256) void step_search_kernel(const float* __restric
   const float* pr = p + (long)r * S;
   const int len = src_len ? src_len[r] : S;
   const long hs = head_step[r];
-  const int max_steps = mass_pres ? len - 1 : len;
-  const int n = mass_pres ? S : S + 1;           // length of the searched row
-  int found = -1;
-  for (int j0 = 0; j0 < n && found < 0; j0 += 64) {
-    const int j = j0 + lane;
-    float v = 0.f;
-    if (j < n) {
-      v = (j < S) ? pr[j] : 0.f;
-      if ((long)j < hs) v = 0.f;                 // mask the past
-      if (j == max_steps) v = 1.f;               // force stop at the end
-    }
-    const unsigned long long m = __ballot(j < n && v >= 0.5f);
-    if (m) found = j0 + __ffsll((long long)m) - 1;
-  }
-  if (found < 0) found = 0;                      // unreachable: the forced 1.0 always hits
-  const int clampi = min(max(found, 0), len - 1);
-  const float p_i = clampi >= 0 ? pr[clampi] : 0.f;   // clampi < 0: an empty source (len == 0), nothing to read
-  const bool dead = (!mass_pres) && found == max_steps;
+  const int found = policy::first_step(pr, S, len, mass_pres, hs, lane);
+  const float p_i = policy::p_at_clamp(pr, found, len);
+  const int row = policy::hard_row(found, len, mass_pres);    // alpha: the one-hot the hard gather reads
   if (alpha)
-    for (int j = lane; j < S; j += 64) alpha[(long)r * S + j] = (j == clampi && !dead) ? 1.f : 0.f;
+    for (int j = lane; j < S; j += 64) alpha[(long)r * S + j] = (j == row) ? 1.f : 0.f;
   if (lane == 0) {
     head_step[r] = found;
-    head_read[r] = (found == max_steps && p_i < 0.5f) ? 1 : 0;
+    head_read[r] = policy::head_read_of(found, len, mass_pres, p_i) ? 1 : 0;
   }
 }
 
@@ -508,24 +493,14 @@ __global__ __launch_bounds__(256) void step_p_choose_kernel(const T* __restrict_
           for (int f = f0; f < f1; ++f) acc += to_f32(Km[(((long)b * H + h) * S_cap + f) * d + lane]);
         acc = acc / (float)(f1 - f0) * qv;
         const float en = wave_sum(acc) + energy_bias;
-        bool masked = false;
-        if (S_pad > 0 && j > 0) {                              // pooled padding mask, threshold, first position never masked
-          const int n_pad = f1 - max(f0, min(f1, len_b));
-          masked = (float)n_pad / (float)(f1 - f0) > pad_thr;
-        }
+        const bool masked = S_pad > 0 && policy::window_masked(j, f0, f1, len_b, pad_thr);
         if (lane == 0) pp[j] = masked ? 0.f : 1.0f / (1.0f + expf(-en));
       }
     }
     __builtin_amdgcn_wave_barrier();
-    // zero insertion: pooled j lands on frame (j+1)*ratio-1; if the upsampled row reaches past the
-    // source it is cropped and the LAST column takes the last pooled value (fixed_pre_decision.py:143-159)
-    for (int s = lane; s < S_cap; s += 64) {
-      float v = 0.f;
-      if (s < len) {
-        if ((s + 1) % ratio == 0 && (s + 1) / ratio - 1 < P) v = pp[(s + 1) / ratio - 1];
-        if (s == len - 1 && P * ratio >= len) v = pp[P - 1];
-      }
-      pr[s] = v;
+    for (int s = lane; s < S_cap; s += 64) {                   // zero insertion
+      const int j = policy::pooled_index_at(s, len, ratio, P);
+      pr[s] = j >= 0 ? pp[j] : 0.f;
     }
     __builtin_amdgcn_wave_barrier();
   }

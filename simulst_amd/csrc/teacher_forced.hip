@@ -9,7 +9,7 @@
 // softmax in fp32, P . V accumulated in fp32, one rounding to the activation dtype at the store.  With bf16 activations the
 // probabilities are rounded to bf16 as the A operand of the second product, which is the reference's own `.type_as(q)` /
 // `beta.to(v.dtype)`.
-#include "common.h"
+#include "policy_core.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
@@ -192,11 +192,10 @@ __global__ __launch_bounds__(256) void mma_energy_kernel(const T* __restrict__ q
     const f32x4 e = Tile<T>::mma(f32x4{0.f, 0.f, 0.f, 0.f}, Qs + 16 * wave * LDQ, LDQ, Ks + 16 * n * LDQ, LDQ, dp);
     const int j = j0 + 16 * n + r;
     bool masked = false;
-    if (monotonic && j > 0 && j < P) {                   // pooled padding mask: threshold, the first position never masked
+    if (monotonic && j < P) {
       int f0, f1;
       pooled_frames(j, S, ratio, pool_last, f0, f1);
-      const int n_pad = f1 - max(f0, min(f1, len));
-      masked = (float)n_pad / (float)(f1 - f0) > pad_thr;
+      masked = policy::window_masked(j, f0, f1, len, pad_thr);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -215,10 +214,8 @@ __global__ __launch_bounds__(256) void mma_energy_kernel(const T* __restrict__ q
     const int row = idx / span, s = s_lo + (idx - row * span);
     const int u = u0 + row;
     if (u >= U) break;
-    float v = 0.f;
-    if ((s + 1) % ratio == 0 && (s + 1) / ratio - 1 < P) v = Es[row * LDE + (s + 1) / ratio - 1 - j0];
-    if (s == S - 1) v = Es[row * LDE + P - 1 - j0];
-    out[((long)bh * U + u) * S + s] = v;
+    const int j = policy::pooled_index_at(s, S, ratio, P);
+    out[((long)bh * U + u) * S + s] = j >= 0 ? Es[row * LDE + j - j0] : 0.f;
   }
 }
 
@@ -235,15 +232,13 @@ __global__ __launch_bounds__(64) void mma_waitk_p_kernel(float* __restrict__ p, 
   for (int j = P - 1; j > 0; --j) {
     int f0, f1;
     pooled_frames(j, S, ratio, pool_last, f0, f1);
-    const int n_pad = f1 - max(f0, min(f1, len));
-    if (!((float)n_pad / (float)(f1 - f0) > pad_thr)) { valid = j + 1; break; }
+    if (!policy::window_masked(j, f0, f1, len, pad_thr)) { valid = j + 1; break; }
   }
   const int step = min(u + k - 1, valid - 1);
   float* row = p + ((long)bh * U + u) * S;
   for (int s = threadIdx.x; s < S; s += 64) {
-    float v = ((s + 1) % ratio == 0 && (s + 1) / ratio - 1 == step) ? 1.f : 0.f;
-    if (s == S - 1) v = step == P - 1 ? 1.f : 0.f;
-    row[s] = v;
+    const int j = policy::pooled_index_at(s, S, ratio, P);
+    row[s] = (j >= 0 && j == step) ? 1.f : 0.f;
   }
 }
 

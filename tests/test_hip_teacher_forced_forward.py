@@ -3,10 +3,10 @@ own outputs (g24), against the step path fed the same tokens (wait-k, full atten
 torch, SimulSTModel.score_reference, and the link to the latency loss.  The CPU restatement and its cases live in
 tests/test_teacher_forced_oracle.py."""
 import math
+from types import SimpleNamespace
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from oracle import monotonic as mono
 from oracle.configs import from_model_config
@@ -149,9 +149,20 @@ def _kv(B, H, S, d, dtype, seed):
     return K.to(dtype)
 
 
+# ratio < 0: 'last' pooling with ratio |ratio| (the entry point rejects it for S < |ratio|)
+ENERGY_CASES = [(S, r) for r in (1, 8, 4) for S in S_SET] + [(S, -4) for S in (8, 9, 17)]
+
+
+def _pool(x, ratio):
+    """x [N, S, C] pooled over S as the padded batch is in a training-mode forward: oracle.monotonic's own pooling"""
+    if abs(ratio) == 1:
+        return x
+    cfg = SimpleNamespace(pre_decision_ratio=abs(ratio), pre_decision_type="average" if ratio > 0 else "last")
+    return mono.pool_keys(x.transpose(0, 1), cfg).transpose(0, 1)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
-@pytest.mark.parametrize("ratio", [1, 8])
-@pytest.mark.parametrize("S", S_SET)
+@pytest.mark.parametrize("S,ratio", ENERGY_CASES)
 def test_energy_kernel(ops, S, ratio, dtype):
     from simulst_amd import _lib
     B, H, d, U = 2, 2, 64, 70
@@ -169,14 +180,14 @@ def test_energy_kernel(ops, S, ratio, dtype):
     torch.testing.assert_close(got, want, atol=TOL[dtype]["atol"] * 2, rtol=TOL[dtype]["rtol"])
     # monotonic: pooled keys (ceil, no trim), bias, pooled padding mask (0.3, first column never), sigmoid, zero insertion + tail
     bias = -0.5
-    pooled = F.avg_pool1d(Kh.transpose(1, 2), ratio, ratio, ceil_mode=True).transpose(1, 2) if ratio > 1 else Kh
+    pooled = _pool(Kh, ratio)
     pad = (torch.arange(S).unsqueeze(0) >= key_len.unsqueeze(1)).float()
-    mp = (F.avg_pool1d(pad.unsqueeze(1), ratio, ratio, ceil_mode=True).squeeze(1) if ratio > 1 else pad) > 0.3
+    mp = _pool(pad.unsqueeze(-1), ratio).squeeze(-1) > 0.3
     mp[:, 0] = False
     e = qh @ pooled.transpose(1, 2) + bias
     e = e.masked_fill(mp.repeat_interleave(H, 0).unsqueeze(1), -1e8)
     pp = torch.sigmoid(e)
-    want = mono.insert_zeros(pp, ratio)[:, :, :S].clone()
+    want = mono.insert_zeros(pp, abs(ratio))[:, :, :S].clone()
     want[:, :, -1] = pp[:, :, -1]
     got = ops.mma_energy(q.cuda(), K.cuda(), mode=_lib.ENERGY_MONOTONIC, S=S, key_len=key_len.cuda(), ratio=ratio, energy_bias=bias).cpu()
     print(f"monotonic p_choose S={S} ratio={ratio} {dtype}: max diff {(got - want.float()).abs().max().item():.3e}")
@@ -188,7 +199,7 @@ def test_energy_kernel(ops, S, ratio, dtype):
     last = (~mp).sum(1) - 1
     step = torch.minimum(torch.arange(U).unsqueeze(0) + k - 1, last.unsqueeze(1))                       # [B, U]
     onehot = (torch.arange(P).view(1, 1, P) == step.unsqueeze(-1)).double().repeat_interleave(H, 0)
-    want = mono.insert_zeros(onehot, ratio)[:, :, :S].clone()
+    want = mono.insert_zeros(onehot, abs(ratio))[:, :, :S].clone()
     want[:, :, -1] = onehot[:, :, -1]
     assert torch.equal(got, want.float())
 
