@@ -304,14 +304,6 @@ int sl_self_attention(simulst_handle* h, const void* qkv, void* k_cache, void* v
 static inline bool sl_self_attention_fused_ok(int H, int d, int cap) {
   return (d == 32 || d == 64) && H * d <= 1024 && cap <= 256;
 }
-// the row counts at which simulst_linear's dispatch of decode-step shapes changes kernel, each owned by the file that applies it
-// (gemm.hip, gemm_mid.hip, gemm_panel.hip); sl_retire_floor_rows (decode_plan.cpp) keeps a shrinking batch between them
-int sl_skinny_max_rows(bool packed);
-int sl_tile_min_rows();
-int sl_mid_narrow_min_rows(const simulst_handle* h);
-int sl_panel_split_min_rows(const simulst_handle* h);
-// the vocabulary projection with the greedy pick's per-tile maxima as its output (gemm_mid.hip sl_launch_vocab_argmax) takes this shape
-bool sl_vocab_argmax_ok(const simulst_handle* h, int dtype, int B, int V, int D, bool packed);
 // row-local chains of the decoder layer for co-scheduled bf16 batches (dec_chain.hip)
 bool sl_dec_chain_ok(const simulst_handle* h, int dtype, int B, int D, int F, bool packed);
 int sl_dec_proj_chain(simulst_handle* h, const void* ctx, void* x, const void* Wo, const float* bo, const float* ln_g,

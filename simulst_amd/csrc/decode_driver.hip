@@ -10,6 +10,7 @@
 #include "policy_core.h"
 #include "gemv_mfma.h"
 #include "decode_plan.h"
+#include "gemm_plan.h"      // sl_launch_vocab_argmax
 
 namespace {
 

@@ -1,6 +1,7 @@
 // Path selection of the decoder step loops, the retire floor that follows from it, and the launches the MMA and the CIF loop share
 // (decode_plan.h).  Host code only.
 #include "decode_plan.h"
+#include "gemm_plan.h"
 
 // the head-split self-attention block is an EXPERIMENTS build's (decode_fused.hip: measured slower); the product never plans it
 #ifdef SL_EXPERIMENTS
@@ -60,12 +61,10 @@ int sl_retire_floor_rows(const simulst_handle* h, int B) {
   if (!rows_chain_ffn(h, B)) f = h->dec_chain_ffn_max_rows + 1;               // layer chains without the feed-forward chain
   else if (B >= h->dec_chain_min_rows) f = h->dec_chain_min_rows;             // layer chains
   else if (!rows_fuse_q(h, B)) f = h->fuse_q_max_rows + 1;                    // separate query projection, no chains
-  const int gemm_rows[] = {sl_tile_min_rows(), sl_mid_narrow_min_rows(h), sl_panel_split_min_rows(h)};
-  for (int t : gemm_rows)
+  for (int t : {TILE_MIN_ROWS, h->mid_narrow_min_rows, h->panel_split_min_rows})      // gemm_plan.cpp plan_decode_step
     if (B >= t && f < t) f = t;
-  if (B > sl_skinny_max_rows(true)) f = B;                                    // beyond the decode-step GEMMs' row limit
-  f = (f + 15) / 16 * 16;
-  return f < B ? f : B;
+  if (B > SKINNY_MAX_ROWS_PACKED) f = B;                                      // beyond the decode-step GEMMs' row limit
+  return min((f + 15) / 16 * 16, B);
 }
 
 int sl_lin(simulst_handle* h, int dtype, int B, int N, int K, const void* A, const void* W, const float* bias, const void* R,

@@ -12,7 +12,7 @@
 //   fp32 LDS image: k-major [BK][BM+1] (stride == 1 mod 32 banks: conflict-free
 //                   transposed writes, conflict-free per-k reads)
 //   bf16 LDS image: row-major [BM][BK+8] (144-B rows: ds_read_b128 conflict-free)
-#include "gemm_args.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -375,12 +375,9 @@ __global__ __launch_bounds__(256) void linear_kernel(const TA* __restrict__ A, c
 }
 
 template <typename TA, typename TC, int BM, int BN, int EPI>
-void launch(simulst_handle* h, const void* A, const void* W, const float* bias, const void* R, void* C,
-            void* aux, const LinArgs& p) {
-  int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  dim3 grid(nbm * nbn);
-  hipLaunchKernelGGL((linear_kernel<TA, TC, BM, BN, EPI>), grid, dim3(256), 0, h->stream,
-                     (const TA*)A, (const TA*)W, bias, (const TA*)R, (TC*)C, (TA*)aux, p);
+void launch(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  hipLaunchKernelGGL((linear_kernel<TA, TC, BM, BN, EPI>), dim3(pl.grid[0]), dim3(256), 0, h->stream,
+                     (const TA*)o.A, (const TA*)o.W, o.bias, (const TA*)o.R, (TC*)o.C, (TA*)o.aux, p);
 #ifdef SL_PROBE
   if (EPI == SIMULST_EPI_GLU && p.M > 100000) {
     (void)hipStreamSynchronize(h->stream);
@@ -393,40 +390,30 @@ void launch(simulst_handle* h, const void* A, const void* W, const float* bias, 
 #endif
 }
 
+// the 128 x 128 tile or the 64 x 64 one, as planned (decode-step shapes are routed to gemm_skinny.hip before this point)
 template <typename TA, typename TC, int EPI>
-void launch_tiles(simulst_handle* h, const void* A, const void* W, const float* bias, const void* R,
-                  void* C, void* aux, const LinArgs& p) {
-  // tall problems get the 128x128 tile, mid-size the 64x64 one (decode-step shapes are routed to
-  // gemm_skinny.hip before this point)
-  // (a 256 x 128 tile was measured 2x SLOWER on MI355X for the encoder shapes: 272+ VGPRs and 55 KB of LDS leave
-  // one workgroup per CU)
-  if (EPI == SIMULST_EPI_GLU || p.M > 512)
-    launch<TA, TC, 128, 128, EPI>(h, A, W, bias, R, C, aux, p);
+void launch_tiles(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  if (pl.family == SL_LIN_TILE128)
+    launch<TA, TC, 128, 128, EPI>(h, pl, o, p);
   else {
-    if constexpr (EPI != SIMULST_EPI_GLU) launch<TA, TC, 64, 64, EPI>(h, A, W, bias, R, C, aux, p);
+    if constexpr (EPI != SIMULST_EPI_GLU) launch<TA, TC, 64, 64, EPI>(h, pl, o, p);
   }
 }
 
 template <typename TA>
-int dispatch(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R,
-             void* C, void* aux, const LinArgs& p) {
-  switch (epi) {
-    case SIMULST_EPI_BIAS: launch_tiles<TA, TA, SIMULST_EPI_BIAS>(h, A, W, bias, R, C, aux, p); break;
-    case SIMULST_EPI_BIAS_GELU: launch_tiles<TA, TA, SIMULST_EPI_BIAS_GELU>(h, A, W, bias, R, C, aux, p); break;
-    case SIMULST_EPI_BIAS_RES: launch_tiles<TA, TA, SIMULST_EPI_BIAS_RES>(h, A, W, bias, R, C, aux, p); break;
-    case SIMULST_EPI_GLU: launch_tiles<TA, TA, SIMULST_EPI_GLU>(h, A, W, bias, R, C, aux, p); break;
-    case SIMULST_EPI_EMF_OUT: launch_tiles<TA, TA, SIMULST_EPI_EMF_OUT>(h, A, W, bias, R, C, aux, p); break;
-    case SIMULST_EPI_BIAS_F32OUT: launch_tiles<TA, float, SIMULST_EPI_BIAS>(h, A, W, bias, R, C, aux, p); break;
-    case SIMULST_EPI_BIAS_RES_GELU: launch_tiles<TA, TA, SIMULST_EPI_BIAS_RES_GELU>(h, A, W, bias, R, C, aux, p); break;
-    default: h->err = "simulst_linear: unknown epilogue"; return SIMULST_E_ARG;
+void dispatch(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  switch (pl.epi) {
+    case SIMULST_EPI_BIAS: launch_tiles<TA, TA, SIMULST_EPI_BIAS>(h, pl, o, p); break;
+    case SIMULST_EPI_BIAS_GELU: launch_tiles<TA, TA, SIMULST_EPI_BIAS_GELU>(h, pl, o, p); break;
+    case SIMULST_EPI_BIAS_RES: launch_tiles<TA, TA, SIMULST_EPI_BIAS_RES>(h, pl, o, p); break;
+    case SIMULST_EPI_GLU: launch_tiles<TA, TA, SIMULST_EPI_GLU>(h, pl, o, p); break;
+    case SIMULST_EPI_EMF_OUT: launch_tiles<TA, TA, SIMULST_EPI_EMF_OUT>(h, pl, o, p); break;
+    case SIMULST_EPI_BIAS_F32OUT: launch_tiles<TA, float, SIMULST_EPI_BIAS>(h, pl, o, p); break;
+    default: launch_tiles<TA, TA, SIMULST_EPI_BIAS_RES_GELU>(h, pl, o, p); break;      // (the plan refused unknown epilogues)
   }
-  return SIMULST_OK;
 }
 
 }  // namespace
-
-// decode-step shapes: up to 2048 rows, up to 8192 when the caller packed the weights for them (co-scheduled batches)
-int sl_skinny_max_rows(bool packed) { return packed ? 8192 : 2048; }
 
 extern "C" int simulst_linear(simulst_handle* h, const simulst_linear_desc* d, const void* A, const void* W,
                               const float* bias, const void* R, void* C, void* aux) {
@@ -470,24 +457,21 @@ extern "C" int simulst_linear(simulst_handle* h, const simulst_linear_desc* d, c
              SIMULST_E_ARG, "simulst_linear: head-major output needs the bias epilogue and head_dim % 8 == 0");
   if (d->ln_gamma || d->ln_beta)
     SL_REQUIRE(h, d->ln_gamma && d->ln_beta, SIMULST_E_NULL, "simulst_linear: LN prologue needs gamma and beta");
-  const bool skinny_ok = M <= sl_skinny_max_rows(p.w_packed != 0) && d->a_lead == 0 && d->a_row_stride >= d->K &&
-                         d->epilogue != SIMULST_EPI_GLU && d->epilogue != SIMULST_EPI_EMF_OUT;
-  if (!skinny_ok) {
-    if (sl_panel_wanted(d->dtype, d->epilogue, p)) {
-      if (d->epilogue == SIMULST_EPI_EMF_OUT) SL_CHECK_NULL(h, aux);
-      return sl_launch_panel(h, d->epilogue, A, W, bias, R, C, aux, p);
-    }
+  const sl_linear_ops o = {A, W, bias, R, C, aux};
+  const sl_linear_plan pl = sl_plan_linear(h, d->dtype, d->epilogue, p, o);
+  switch (pl.family) {
+    case SL_LIN_REFUSED: h->err = pl.err; return pl.status;
+    case SL_LIN_WSTAT: return sl_launch_wstat(h, pl, o, p);
+    case SL_LIN_PANEL_WIDE: return sl_launch_panel_wide(h, pl, o, p);
+    case SL_LIN_PANEL: return sl_launch_panel(h, pl, o, p);
+    case SL_LIN_PANEL_SPLIT: return sl_launch_panel_split(h, pl, o, p);
+    case SL_LIN_MID: return sl_launch_mid(h, pl, o, p);
+    case SL_LIN_WAVE_TILE: return sl_launch_wave_tile(h, pl, o, p);
+    case SL_LIN_SKINNY: return sl_launch_skinny(h, pl, o, p);
+    case SL_LIN_TILE256: return sl_launch_tile256(h, pl, o, p);
+    default: break;                                                  // SL_LIN_TILE128, SL_LIN_TILE64
   }
-  if (p.w_packed)
-    SL_REQUIRE(h, skinny_ok && d->N % 16 == 0 && d->K % (4 * G) == 0, SIMULST_E_SHAPE,
-               "simulst_linear: fragment-major weights need a decode-step shape (or a tall bf16 problem with K <= 256), "
-               "N % 16 == 0 and K % (64 bytes) == 0");
-  if (skinny_ok) return sl_launch_skinny(h, d->dtype, d->epilogue, A, W, bias, R, C, p);
-  SL_REQUIRE(h, !p.ln_g, SIMULST_E_SHAPE, "simulst_linear: LN prologue needs a decode-step shape");
-  if (sl_tile256_wanted(h, d->dtype, d->epilogue, p, C)) return sl_launch_tile256(h, A, W, bias, C, p);
-  KTimer t(h, SIMULST_K_LINEAR);
-  int rc = d->dtype == SIMULST_F32 ? dispatch<float>(h, d->epilogue, A, W, bias, R, C, aux, p)
-                                   : dispatch<bf16>(h, d->epilogue, A, W, bias, R, C, aux, p);
-  if (rc != SIMULST_OK) return rc;
+  KTimer t(h, pl.timer);
+  if (d->dtype == SIMULST_F32) dispatch<float>(h, pl, o, p); else dispatch<bf16>(h, pl, o, p);
   return sl_launch_status(h, "simulst_linear");
 }

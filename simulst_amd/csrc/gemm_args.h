@@ -1,4 +1,4 @@
-// Shared argument block of the contraction kernels (gemm.hip, gemm_skinny.hip).
+// Shared argument block of the contraction kernels (gemm*.hip; which of them a call takes: gemm_plan.h).
 #pragma once
 #include "common.h"
 
@@ -75,41 +75,6 @@ __device__ __forceinline__ void moments_mid(uint4 v, float& s1, float& s2, bf16)
     s2 = fmaf(lo, lo, fmaf(hi, hi, s2));
   }
 }
-
-// decode-step (M <= 128) contraction, defined in gemm_skinny.hip
-int sl_launch_skinny(simulst_handle* h, int dtype, int epilogue, const void* A, const void* W, const float* bias,
-                     const void* R, void* C, const LinArgs& p);
-
-// A-stationary row panels for tall bf16 problems with K <= 256 (encoder QKV / out-proj / fc1), defined in gemm_panel.hip
-bool sl_panel_wanted(int dtype, int epi, const LinArgs& p);
-int sl_launch_panel(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R, void* C,
-                    void* aux, const LinArgs& p);
-// 256 x 256 tiles with the GLU epilogue for the subsampler's convolutions, defined in gemm_tile256.hip
-bool sl_tile256_wanted(const simulst_handle* h, int dtype, int epi, const LinArgs& p, const void* C);
-int sl_launch_tile256(simulst_handle* h, const void* A, const void* W, const float* bias, void* C, const LinArgs& p);
-// weight-stationary persistent kernel for the encoder's tall K = 256 projections (QKV, out-proj), defined in gemm_wstat.hip
-bool sl_wstat_wanted(const simulst_handle* h, int dtype, int epi, const LinArgs& p, const void* A, const void* C, const void* R);
-int sl_launch_wstat(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R, void* C, void* aux,
-                    const LinArgs& p);
-// the same kernel for co-scheduled decode batches (thousands of rows): column range split over blockIdx.y so that the
-// chip is filled, optional LayerNorm prologue on the stationary A fragments
-bool sl_panel_split_wanted(const simulst_handle* h, int dtype, int epi, const LinArgs& p);
-int sl_launch_panel_split(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R,
-                          void* C, const LinArgs& p);
-
-// 64 x 64 tile for co-scheduled batches (M >= 256) with wide outputs, defined in gemm_mid.hip
-bool sl_mid_wanted(const simulst_handle* h, int dtype, const LinArgs& p);
-int sl_launch_mid(simulst_handle* h, int dtype, int epilogue, const void* A, const void* W, const float* bias,
-                  const void* R, void* C, const LinArgs& p);
-// the vocabulary projection of a decode step with the greedy pick's per-tile maxima as its output (bf16, LayerNorm prologue, no bias):
-// partial [B][V / 64] (value, index) pairs; sl_vocab_argmax_ok (common.h) says whether the shape is taken
-int sl_launch_vocab_argmax(simulst_handle* h, const void* x, const void* W, const float* ln_g, const float* ln_b, float2* partial,
-                           int B, int V, int D, int skip_a, int skip_b);
-
-// one wave per 16 x 16 tile for narrow outputs (N < 512) of co-scheduled batches with K <= 8 k-steps, gemm_mid.hip
-bool sl_wave_tile_wanted(int dtype, const LinArgs& p);
-int sl_launch_wave_tile(simulst_handle* h, int dtype, int epilogue, const void* A, const void* W, const float* bias,
-                        const void* R, void* C, const LinArgs& p);
 
 // simulst_emformer_ffn_prenorm (ffn_pipe.hip ZOUT): where the fused feed-forward launch writes the NEXT layer's normalised rows and
 // segment summaries

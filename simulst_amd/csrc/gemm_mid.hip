@@ -9,7 +9,7 @@
 // operand staging and no cross-wave reduction.  The LayerNorm prologue needs no barrier either: a wave holds
 // complete rows (K <= 8 k-steps), so the row moments are two shuffles away.  The epilogue goes through LDS once to
 // turn the MFMA accumulator layout into 32-byte row segments.
-#include "gemm_args.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -337,35 +337,25 @@ __global__ __launch_bounds__(256) void wave_tile_kernel(const TA* __restrict__ A
 }
 
 template <typename TA, typename TC, int EPI>
-int launch_wave_tile(simulst_handle* h, const void* A, const void* W, const float* bias, const void* R, void* C,
-                     const LinArgs& p) {
-  const int tiles_n = (p.N + 15) / 16;
-  const long tiles = (long)((p.M + 15) / 16) * tiles_n;
-  dim3 grid((unsigned)((tiles + 3) / 4));
-  KTimer t(h, SIMULST_K_LINEAR_SKINNY);
-  if (p.ln_g)
-    hipLaunchKernelGGL((wave_tile_kernel<TA, TC, EPI, true>), grid, dim3(256), 0, h->stream, (const TA*)A, (const TA*)W,
-                       bias, (const TA*)R, (TC*)C, p, tiles_n);
+int launch_wave_tile(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  KTimer t(h, pl.timer);
+  if (pl.ln)
+    hipLaunchKernelGGL((wave_tile_kernel<TA, TC, EPI, true>), dim3(pl.grid[0]), dim3(256), 0, h->stream, (const TA*)o.A, (const TA*)o.W,
+                       o.bias, (const TA*)o.R, (TC*)o.C, p, pl.tiles_n);
   else
-    hipLaunchKernelGGL((wave_tile_kernel<TA, TC, EPI, false>), grid, dim3(256), 0, h->stream, (const TA*)A,
-                       (const TA*)W, bias, (const TA*)R, (TC*)C, p, tiles_n);
+    hipLaunchKernelGGL((wave_tile_kernel<TA, TC, EPI, false>), dim3(pl.grid[0]), dim3(256), 0, h->stream, (const TA*)o.A,
+                       (const TA*)o.W, o.bias, (const TA*)o.R, (TC*)o.C, p, pl.tiles_n);
   return sl_launch_status(h, "simulst_linear(wave per 16x16 tile)");
 }
 
 template <typename TA, typename TC, int EPI>
-int launch_mid(simulst_handle* h, const void* A, const void* W, const float* bias, const void* R, void* C,
-               const LinArgs& p) {
-  // 128-row tiles only when they still give every CU two workgroups (measured at 1024 rows: fc1 with 256 tall
-  // workgroups 14.0 us, with 512 of 64 rows 11.5 us; the vocabulary projection 20.7 vs 21.2 us)
-  const int nt = (p.N + 63) / 64;
-  const bool tall = (long)((p.M + 127) / 128) * nt >= 512;
-  dim3 grid(nt, tall ? (p.M + 127) / 128 : (p.M + 63) / 64);
-  KTimer t(h, SIMULST_K_LINEAR_TILE64);
-#define MID(LN, RWW)                                                                                                  \
-  hipLaunchKernelGGL((mid_kernel<TA, TC, EPI, LN, RWW>), grid, dim3(256), 0, h->stream, (const TA*)A, (const TA*)W,   \
-                     bias, (const TA*)R, (TC*)C, p)
-  if (p.ln_g) { if (tall) MID(true, 2); else MID(true, 1); }
-  else { if (tall) MID(false, 2); else MID(false, 1); }
+int launch_mid(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  KTimer t(h, pl.timer);
+#define MID(LN, RWW)                                                                                                       \
+  hipLaunchKernelGGL((mid_kernel<TA, TC, EPI, LN, RWW>), dim3(pl.grid[0], pl.grid[1]), dim3(256), 0, h->stream, (const TA*)o.A, \
+                     (const TA*)o.W, o.bias, (const TA*)o.R, (TC*)o.C, p)
+  if (pl.ln) { if (pl.tall) MID(true, 2); else MID(true, 1); }
+  else { if (pl.tall) MID(false, 2); else MID(false, 1); }
 #undef MID
 #ifdef SL_PROBE
   {
@@ -383,93 +373,26 @@ int launch_mid(simulst_handle* h, const void* A, const void* W, const float* bia
   return sl_launch_status(h, "simulst_linear(64x64 decode tile)");
 }
 
-template <typename TA>
-int mid_by_epilogue(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R, void* C,
-                    const LinArgs& p) {
-  switch (epi) {
-    case SIMULST_EPI_BIAS: return launch_mid<TA, TA, SIMULST_EPI_BIAS>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_GELU: return launch_mid<TA, TA, SIMULST_EPI_BIAS_GELU>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_RES: return launch_mid<TA, TA, SIMULST_EPI_BIAS_RES>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_F32OUT: return launch_mid<TA, float, SIMULST_EPI_BIAS>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_RES_GELU: return launch_mid<TA, TA, SIMULST_EPI_BIAS_RES_GELU>(h, A, W, bias, R, C, p);
-    default: h->err = "simulst_linear: epilogue not available for decode-step shapes"; return SIMULST_E_ARG;
-  }
-}
-
 }  // namespace
 
-// rows from which the tile kernels of this file (64 x 64, wave per 16 x 16) replace the skinny kernel, and from which the 64 x 64 one
-// takes narrow outputs as well: the decode loops' retire floor (decode_plan.cpp) keeps a shrinking batch on its side of them
-constexpr int TILE_MIN_ROWS = 256;
-int sl_tile_min_rows() { return TILE_MIN_ROWS; }
-int sl_mid_narrow_min_rows(const simulst_handle* h) { return h->mid_narrow_min_rows; }
-
-// shapes this kernel takes over from the 16 x BN kernel: co-scheduled batches with a wide output
-bool sl_mid_wanted(const simulst_handle* h, int dtype, const LinArgs& p) {
-  const int KS = dtype == SIMULST_F32 ? 16 : 32;
-  const long blocks = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);     // 64 x 64 tiles: most of the chip gets one
-  // narrow outputs with a short contraction (out-proj, q-proj: N = 256, K = 256) from mid_narrow_min_rows rows on:
-  // one wave per 16 x 16 tile re-reads 16 KB of operands per 131 kflop and is L2-bound there (4096 rows: 9.3 -> 7.9 us
-  // out-proj, 12.8 -> 7.6 us LN + q-proj).  fc2 (K = 2048) measured the same on both kernels and keeps the k-split one.
-  const bool narrow = p.N >= 64 && p.N < 512 && p.K <= 8 * KS && p.M >= sl_mid_narrow_min_rows(h);
-  return p.M >= TILE_MIN_ROWS && (p.N >= 512 || narrow) && blocks >= h->mid_min_blocks && p.K % KS == 0 && (!p.ln_g || p.K <= 8 * KS);
-}
-
-// the decode loops' vocabulary projection with the greedy pick's per-tile maxima as output: the shapes the 64 x 64 tile kernel
-// takes anyway (co-scheduled bf16 batches below the split-panel threshold), final LayerNorm as prologue
-static LinArgs vocab_args(int B, int V, int D, const float* ln_g, const float* ln_b) {
-  LinArgs p = {};
-  p.M = B; p.rpb = B; p.N = V; p.K = D;
-  p.a_bs = 0; p.a_rs = D; p.a_lead = 0; p.c_bs = 0; p.c_rs = V; p.r_bs = 0; p.r_rs = V;
-  p.scale = 1.f; p.ln_g = ln_g; p.ln_b = ln_b; p.w_packed = 1;
-  return p;
-}
-
-bool sl_vocab_argmax_ok(const simulst_handle* h, int dtype, int B, int V, int D, bool packed) {
-  if (!h->fused_argmax || dtype != SIMULST_BF16 || !packed || V % 64 != 0 || D % 32 != 0 || D > 256) return false;
-  const LinArgs p = vocab_args(B, V, D, (const float*)h, (const float*)h);      // any non-null: the LayerNorm prologue is part of the shape test
-  return sl_panel_split_wanted(h, dtype, SIMULST_EPI_BIAS_F32OUT, p) || sl_mid_wanted(h, dtype, p);
-}
-
+// the decode loops' vocabulary projection with the greedy pick's per-tile maxima as output (sl_plan_vocab_argmax): always bf16 rows
+// and fp32 pairs, so the 64 x 64 tile needs no epilogue ladder
 int sl_launch_vocab_argmax(simulst_handle* h, const void* x, const void* W, const float* ln_g, const float* ln_b, float2* partial,
                            int B, int V, int D, int skip_a, int skip_b) {
-  LinArgs p = vocab_args(B, V, D, ln_g, ln_b);
+  const sl_linear_plan pl = sl_plan_vocab_argmax(h, SIMULST_BF16, B, V, D, true, ln_g != nullptr);
+  if (pl.family == SL_LIN_REFUSED) { h->err = pl.err; return pl.status; }      // (the decode plan asks sl_vocab_argmax_ok first)
+  LinArgs p = sl_vocab_args(B, V, D, ln_g, ln_b);
   p.amax = partial; p.amax_tiles = V / 64; p.amax_skip_a = skip_a; p.amax_skip_b = skip_b;
-  // the kernel simulst_linear would pick for these rows: the split row panel from thousands of rows on, else the 64 x 64 tile
-  if (sl_panel_split_wanted(h, SIMULST_BF16, SIMULST_EPI_BIAS_F32OUT, p))
-    return sl_launch_panel_split(h, SIMULST_EPI_BIAS_F32OUT, x, W, nullptr, nullptr, partial, p);
-  return launch_mid<bf16, float, SIMULST_EPI_BIAS>(h, x, W, nullptr, nullptr, partial, p);
+  const sl_linear_ops o = {x, W, nullptr, nullptr, partial, nullptr};
+  return pl.family == SL_LIN_PANEL_SPLIT ? sl_launch_panel_split(h, pl, o, p) : launch_mid<bf16, float, SIMULST_EPI_BIAS>(h, pl, o, p);
 }
 
-// narrow outputs of co-scheduled batches with a short contraction: one wave per tile
-bool sl_wave_tile_wanted(int dtype, const LinArgs& p) {
-  const int KS = dtype == SIMULST_F32 ? 16 : 32;
-  return p.M >= TILE_MIN_ROWS && p.N < 512 && p.K % KS == 0 && p.K <= 8 * KS;
+int sl_launch_wave_tile(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  auto go = [&](auto ta, auto tc, auto e) { return launch_wave_tile<decltype(ta), decltype(tc), decltype(e)::value>(h, pl, o, p); };
+  return pl.dtype == SIMULST_F32 ? sl_by_decode_epilogue<float>(h, pl.epi, go) : sl_by_decode_epilogue<bf16>(h, pl.epi, go);
 }
 
-namespace {
-template <typename TA>
-int wave_tile_by_epilogue(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R,
-                          void* C, const LinArgs& p) {
-  switch (epi) {
-    case SIMULST_EPI_BIAS: return launch_wave_tile<TA, TA, SIMULST_EPI_BIAS>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_GELU: return launch_wave_tile<TA, TA, SIMULST_EPI_BIAS_GELU>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_RES: return launch_wave_tile<TA, TA, SIMULST_EPI_BIAS_RES>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_F32OUT: return launch_wave_tile<TA, float, SIMULST_EPI_BIAS>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_RES_GELU: return launch_wave_tile<TA, TA, SIMULST_EPI_BIAS_RES_GELU>(h, A, W, bias, R, C, p);
-    default: h->err = "simulst_linear: epilogue not available for decode-step shapes"; return SIMULST_E_ARG;
-  }
-}
-}  // namespace
-
-int sl_launch_wave_tile(simulst_handle* h, int dtype, int epilogue, const void* A, const void* W, const float* bias,
-                        const void* R, void* C, const LinArgs& p) {
-  return dtype == SIMULST_F32 ? wave_tile_by_epilogue<float>(h, epilogue, A, W, bias, R, C, p)
-                              : wave_tile_by_epilogue<bf16>(h, epilogue, A, W, bias, R, C, p);
-}
-
-int sl_launch_mid(simulst_handle* h, int dtype, int epilogue, const void* A, const void* W, const float* bias,
-                  const void* R, void* C, const LinArgs& p) {
-  return dtype == SIMULST_F32 ? mid_by_epilogue<float>(h, epilogue, A, W, bias, R, C, p)
-                              : mid_by_epilogue<bf16>(h, epilogue, A, W, bias, R, C, p);
+int sl_launch_mid(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  auto go = [&](auto ta, auto tc, auto e) { return launch_mid<decltype(ta), decltype(tc), decltype(e)::value>(h, pl, o, p); };
+  return pl.dtype == SIMULST_F32 ? sl_by_decode_epilogue<float>(h, pl.epi, go) : sl_by_decode_epilogue<bf16>(h, pl.epi, go);
 }

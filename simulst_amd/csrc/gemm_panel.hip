@@ -12,11 +12,10 @@
 //     row-contiguous stores with bias / GELU / residual / Emformer summary handling; no workgroup barrier in it
 // A is read from HBM exactly once, weights stream from L2 once per panel, the output is written once.
 // Measured on MI355X (1024 utterances): out-proj 300 -> 221 us, QKV / cross K-V projections 203 -> 200 us.
-#include "gemm_args.h"
+#include "gemm_plan.h"
 
 namespace {
 
-constexpr int PB_M = 128, PB_N = 64, PB_KS = 32;
 constexpr int PB_PF = 3;                 // weight fragments in flight from LDS per wave (register ring)
 
 #ifdef SL_PROBE
@@ -285,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void panel_kernel(const bf16* __restrict__ 
 //     leave for memory at the start of the next step.
 // One workgroup barrier per step.  Results are identical to panel_kernel's (tests/test_hip_kernels.py::test_wide_row_panel_equals_the_row_panel).
 constexpr int PW_PF = 4;                                           // weight fragments in flight from LDS per wave
-constexpr int PW_M = 256, PW_N = 32, PW_SS = 40;                   // rows per workgroup, columns per step, staging row stride (bf16 elements)
+constexpr int PW_SS = 40;                                          // staging row stride (bf16 elements)
 constexpr int PW_NS = 3;                                           // weight slots (requests run two steps ahead)
 typedef __attribute__((address_space(3))) void pw_lds_void;
 typedef const __attribute__((address_space(1))) void pw_gbl_void;
@@ -430,111 +429,50 @@ __global__ __launch_bounds__(256, 2) void panel_wide_kernel(const bf16* __restri
 
 }  // namespace
 
-// shapes the panel kernel takes: bf16, fragment-major weights, tall problems with a short contraction
-bool sl_panel_wanted(int dtype, int epi, const LinArgs& p) {
-  return dtype == SIMULST_BF16 && p.w_packed && p.M >= 4096 && p.K <= 256 && p.K % PB_KS == 0 && p.N % 16 == 0 &&
-         p.a_lead == 0 && p.a_rs >= p.K && (p.c_hd == 0 || p.c_hd % 8 == 0) &&
-         // LayerNorm prologue (the encoder's pre-FFN LayerNorm rides in fc1: applied ONCE to the stationary A
-         // fragments of a panel, one launch and 0.8 MB of HBM traffic per utterance and layer less)
-         (!p.ln_g || epi == SIMULST_EPI_BIAS || epi == SIMULST_EPI_BIAS_GELU) &&
-         // (fc1 + GELU: 1568 us here vs 1795 us on the 128 x 128 tile kernel at 605 k rows, N = 2048, now that the
-         //  GELU issues on the packed fp32 pipe; with the exp-based form the tile kernel had been the faster one)
-         (epi == SIMULST_EPI_BIAS || epi == SIMULST_EPI_BIAS_GELU || epi == SIMULST_EPI_BIAS_RES || epi == SIMULST_EPI_EMF_OUT);
-}
-
-// the wide form: bias-only epilogue, K == 256, whole 32-column steps, 16-byte aligned output rows / heads
-static bool panel_wide_wanted(const simulst_handle* h, int epi, const LinArgs& p, const void* A, const void* C, const float* bias) {
-  // 16-byte loads of A rows and 16-byte streaming stores of C rows: the base pointers must be aligned like the strides;
-  // the bias travels by 4-byte DMA
-  if ((((uintptr_t)A | (uintptr_t)C) & 15) != 0 || ((uintptr_t)bias & 3) != 0) return false;
-  return h->panel_wide && epi == SIMULST_EPI_BIAS && !p.ln_g && p.K == 256 && p.N % PW_N == 0 && p.M >= 8192 &&
-         ((p.c_rs | p.c_bs | p.c_hs | p.c_ts) & 7) == 0 && (p.c_hd == 0 || p.c_hd % 8 == 0) && (p.a_rs & 7) == 0 && (p.a_bs & 7) == 0;
-}
-
-int sl_launch_panel(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R, void* C,
-                    void* aux, const LinArgs& p) {
-  if (sl_wstat_wanted(h, SIMULST_BF16, epi, p, A, C, R)) return sl_launch_wstat(h, epi, A, W, bias, R, C, aux, p);
-  if (panel_wide_wanted(h, epi, p, A, C, bias)) {
-    KTimer tw(h, SIMULST_K_LINEAR);
+int sl_launch_panel_wide(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  KTimer t(h, pl.timer);
 #ifdef SL_EXPERIMENTS      // default-policy stores instead of streaming ones (SIMULST_OPT_PANEL_WIDE = 2): measured slower
-    if (h->panel_wide_plain_stores)
-      hipLaunchKernelGGL(panel_wide_kernel<false>, dim3((p.M + PW_M - 1) / PW_M), dim3(256), 0, h->stream, (const bf16*)A, (const bf16*)W, bias,
-                         (bf16*)C, p);
-    else
+  if (h->panel_wide_plain_stores)
+    hipLaunchKernelGGL(panel_wide_kernel<false>, dim3(pl.grid[0]), dim3(256), 0, h->stream, (const bf16*)o.A, (const bf16*)o.W, o.bias, (bf16*)o.C, p);
+  else
 #endif
-      hipLaunchKernelGGL(panel_wide_kernel<true>, dim3((p.M + PW_M - 1) / PW_M), dim3(256), 0, h->stream, (const bf16*)A, (const bf16*)W, bias,
-                         (bf16*)C, p);
-    return sl_launch_status(h, "simulst_linear(wide row panel)");
-  }
-  dim3 grid((p.M + PB_M - 1) / PB_M);
-  const int spb = (p.N + PB_N - 1) / PB_N;
-  KTimer t(h, SIMULST_K_LINEAR);
-#define PANEL(E)                                                                                                     \
-  hipLaunchKernelGGL((panel_kernel<E, false>), grid, dim3(256), 0, h->stream, (const bf16*)A, (const bf16*)W, bias, \
-                     (const bf16*)R, (bf16*)C, (bf16*)aux, p, spb)
-#define PANEL_LN(E)                                                                                                 \
-  hipLaunchKernelGGL((panel_kernel<E, true>), grid, dim3(256), 0, h->stream, (const bf16*)A, (const bf16*)W, bias, \
-                     (const bf16*)R, (bf16*)C, (bf16*)aux, p, spb)
-  if (p.ln_g) {
-    if (epi == SIMULST_EPI_BIAS) PANEL_LN(SIMULST_EPI_BIAS); else PANEL_LN(SIMULST_EPI_BIAS_GELU);
+    hipLaunchKernelGGL(panel_wide_kernel<true>, dim3(pl.grid[0]), dim3(256), 0, h->stream, (const bf16*)o.A, (const bf16*)o.W, o.bias, (bf16*)o.C, p);
+  return sl_launch_status(h, "simulst_linear(wide row panel)");
+}
+
+#define PANEL(E, LN)                                                                                                                \
+  hipLaunchKernelGGL((panel_kernel<E, LN>), dim3(pl.grid[0], pl.grid[1]), dim3(256), 0, h->stream, (const bf16*)o.A, (const bf16*)o.W, \
+                     o.bias, (const bf16*)o.R, (bf16*)o.C, (bf16*)o.aux, p, pl.spb)
+
+int sl_launch_panel(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  KTimer t(h, pl.timer);
+  if (pl.ln) {
+    if (pl.epi == SIMULST_EPI_BIAS) PANEL(SIMULST_EPI_BIAS, true); else PANEL(SIMULST_EPI_BIAS_GELU, true);
     return sl_launch_status(h, "simulst_linear(row panel, LayerNorm prologue)");
   }
-  switch (epi) {
-    case SIMULST_EPI_BIAS: PANEL(SIMULST_EPI_BIAS); break;
-    case SIMULST_EPI_BIAS_GELU: PANEL(SIMULST_EPI_BIAS_GELU); break;
-    case SIMULST_EPI_BIAS_RES: PANEL(SIMULST_EPI_BIAS_RES); break;
-    default: PANEL(SIMULST_EPI_EMF_OUT); break;
+  switch (pl.epi) {
+    case SIMULST_EPI_BIAS: PANEL(SIMULST_EPI_BIAS, false); break;
+    case SIMULST_EPI_BIAS_GELU: PANEL(SIMULST_EPI_BIAS_GELU, false); break;
+    case SIMULST_EPI_BIAS_RES: PANEL(SIMULST_EPI_BIAS_RES, false); break;
+    default: PANEL(SIMULST_EPI_EMF_OUT, false); break;
   }
-#undef PANEL
-#undef PANEL_LN
   return sl_launch_status(h, "simulst_linear(row panel)");
 }
 
-// ---- co-scheduled decode batches -----------------------------------------------------------------------------------
-// Thousands of rows are too few panels to fill 256 CUs, so the column range is split: ~panel_split_blocks workgroups,
-// each keeping its (LayerNorm-ed) A fragments for >= 2 column steps.  With one step per workgroup this would be the
-// 64 x 64 kernel of gemm_mid.hip, which keeps those shapes.
-static int split_steps(const simulst_handle* h, const LinArgs& p) {
-  const int panels = (p.M + PB_M - 1) / PB_M, n_all = (p.N + PB_N - 1) / PB_N;
-  int nsplit = (h->panel_split_blocks + panels - 1) / panels;
-  if (nsplit < 1) nsplit = 1;
-  if (nsplit > n_all) nsplit = n_all;
-  return (n_all + nsplit - 1) / nsplit;
-}
-
-int sl_panel_split_min_rows(const simulst_handle* h) { return h->panel_split_min_rows; }
-
-bool sl_panel_split_wanted(const simulst_handle* h, int dtype, int epi, const LinArgs& p) {
-  if (!(dtype == SIMULST_BF16 && p.w_packed && p.M >= sl_panel_split_min_rows(h) && p.K <= 256 && p.K % PB_KS == 0 &&
-        p.N % 16 == 0 && p.N >= 512 && p.a_lead == 0 && p.a_rs >= p.K && (p.c_hd == 0 || p.c_hd % 8 == 0)))
-    return false;
-  if (p.ln_g ? !(epi == SIMULST_EPI_BIAS || epi == SIMULST_EPI_BIAS_GELU || epi == SIMULST_EPI_BIAS_F32OUT)
-             : !(epi == SIMULST_EPI_BIAS || epi == SIMULST_EPI_BIAS_GELU || epi == SIMULST_EPI_BIAS_RES))
-    return false;
-  if (epi == SIMULST_EPI_BIAS_F32OUT && p.c_hd != 0) return false;
-  return split_steps(h, p) >= 2;
-}
-
-int sl_launch_panel_split(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R,
-                          void* C, const LinArgs& p) {
-  const int spb = split_steps(h, p), n_all = (p.N + PB_N - 1) / PB_N;
-  dim3 grid((p.M + PB_M - 1) / PB_M, (n_all + spb - 1) / spb);
-  KTimer t(h, SIMULST_K_LINEAR_TILE64);
-#define PANEL(E, LN)                                                                                              \
-  hipLaunchKernelGGL((panel_kernel<E, LN>), grid, dim3(256), 0, h->stream, (const bf16*)A, (const bf16*)W, bias, \
-                     (const bf16*)R, (bf16*)C, (bf16*)nullptr, p, spb)
-  if (p.ln_g) {
-    if (epi == SIMULST_EPI_BIAS) PANEL(SIMULST_EPI_BIAS, true);
-    else if (epi == SIMULST_EPI_BIAS_F32OUT) PANEL(SIMULST_EPI_BIAS_F32OUT, true);     // final LayerNorm + vocabulary projection
+// co-scheduled decode batches: the column range split over blockIdx.y
+int sl_launch_panel_split(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  KTimer t(h, pl.timer);
+  if (pl.ln) {
+    if (pl.epi == SIMULST_EPI_BIAS) PANEL(SIMULST_EPI_BIAS, true);
+    else if (pl.epi == SIMULST_EPI_BIAS_F32OUT) PANEL(SIMULST_EPI_BIAS_F32OUT, true);     // final LayerNorm + vocabulary projection
     else PANEL(SIMULST_EPI_BIAS_GELU, true);
   } else {
-    switch (epi) {
+    switch (pl.epi) {
       case SIMULST_EPI_BIAS: PANEL(SIMULST_EPI_BIAS, false); break;
       case SIMULST_EPI_BIAS_GELU: PANEL(SIMULST_EPI_BIAS_GELU, false); break;
       default: PANEL(SIMULST_EPI_BIAS_RES, false); break;
     }
   }
-#undef PANEL
 #ifdef SL_PROBE
   {
     static int calls = 0;
@@ -543,10 +481,11 @@ int sl_launch_panel_split(simulst_handle* h, int epi, const void* A, const void*
       long t[16];
       (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(sl_probe_panel), sizeof t);
       fprintf(stderr, "[probe split panel] M=%d N=%d ln=%d epi=%d spb=%d: A+LN %.2f  W0 %.2f  mfma0 %.2f  epi0 %.2f  rest %.2f  total %.2f us\n",
-              p.M, p.N, p.ln_g != nullptr, epi, spb, (t[1] - t[0]) * 0.01, (t[2] - t[1]) * 0.01, (t[3] - t[2]) * 0.01,
+              p.M, p.N, p.ln_g != nullptr, pl.epi, pl.spb, (t[1] - t[0]) * 0.01, (t[2] - t[1]) * 0.01, (t[3] - t[2]) * 0.01,
               (t[4] - t[3]) * 0.01, (t[5] - t[4]) * 0.01, (t[5] - t[0]) * 0.01);
     }
   }
 #endif
   return sl_launch_status(h, "simulst_linear(row panel, split columns)");
 }
+#undef PANEL

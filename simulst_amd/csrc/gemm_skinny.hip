@@ -13,7 +13,7 @@
 //     the unfused LayerNorm kernel)
 //   * SPLITK > 1 (K >= 4096): fp32 partial tiles to the handle's scratch, summed in a FIXED order by
 //     splitk_epilogue_kernel (deterministic; no atomics)
-#include "gemm_args.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -276,42 +276,8 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const float* __res
 }
 
 template <typename TA, typename TC, int EPI>
-int launch_all(simulst_handle* h, const void* A, const void* W, const float* bias, const void* R, void* C,
-               const LinArgs& p) {
-  constexpr bool F32 = std::is_same<TA, float>::value;
-  constexpr int KS = F32 ? 16 : 32;
-  // spread over the chip: start from 64 x 32 tiles (a weight fragment reused by 4 row tiles) and shrink -- columns
-  // first, then rows -- until the grid has >= 512 workgroups (two per CU) or the tile is the 16 x 16 minimum
-  int MTs = 4, NTs = 2;
-  auto blocks = [&](int m_, int n_) { return (long)((p.M + 16 * m_ - 1) / (16 * m_)) * ((p.N + 16 * n_ - 1) / (16 * n_)); };
-  // co-scheduled batches (more rows than columns: fc2) keep the 64 x 32 tile down to 192 workgroups: measured at
-  // 1536 / 2048 / 3072 rows 14.9 / 15.1 / 22.7 us against 15.6 / 19.3 / 26.8 us for the tiles the 512 rule picks
-  // (the 64 x 16 tile in between is the worst of the three: 19.3 us at 1536 rows)
-  const bool keep_big = p.M > p.N && blocks(4, 2) >= h->skinny_min_blocks_tall;
-  while (!keep_big && blocks(MTs, NTs) < 512 && (MTs > 1 || NTs > 1)) {
-    if (NTs > 1) NTs = 1; else MTs >>= 1;
-  }
-  if (MTs == 1 && NTs == 1 && blocks(1, 1) > 512) NTs = 2;      // the M <= 64 policy of the 16 x BN kernel
-  const bool wide = NTs == 2;
-  const int mt = (p.M + 16 * MTs - 1) / (16 * MTs);
-  const int bn = 16 * NTs;
-  const int nt = (p.N + bn - 1) / bn;
-  int splits = 1;
-  // measured on MI355X (bench.py, K = 2048 fc2): one 16x16-tile launch streaming 128 KB per workgroup is as
-  // fast end to end as 4-way split-K + epilogue launch, so splitting starts only at K >= 4096
-  if (!p.ln_g && p.K >= 4096) {
-    splits = p.K / 1024;
-    while (splits > 1 && (long)mt * nt * splits > 1024) splits >>= 1;
-    if (splits > 1) { MTs = 1; }
-  }
-  int kps = (p.K + splits - 1) / splits;
-  kps = (kps + KS - 1) / KS * KS;
-  splits = (p.K + kps - 1) / kps;
-  if (p.ln_g && p.K > 4 * 4 * KS) {
-    h->err = "simulst_linear: LN prologue needs K <= 512 (bf16) / 256 (fp32)";
-    return SIMULST_E_SHAPE;
-  }
-  if (p.ln_g && MTs > 2 && p.K > 4 * 2 * KS) MTs = 2;           // 64-row tiles keep 2 k-steps per wave in flight
+int launch_all(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  const int splits = pl.splits;
   float* partial = nullptr;
   if (splits > 1) {
     const size_t need = (size_t)splits * p.M * p.N * sizeof(float);
@@ -325,21 +291,21 @@ int launch_all(simulst_handle* h, const void* A, const void* W, const float* bia
     }
     partial = (float*)h->ws;
   }
-  const int mt2 = (p.M + 16 * MTs - 1) / (16 * MTs);
-  dim3 grid(nt, mt2, splits);
-#define SK_LAUNCH(LN, NTT, SP, MTT)                                                                                \
-  hipLaunchKernelGGL((skinny_kernel<TA, TC, EPI, LN, NTT, SP, MTT>), grid, dim3(256), 0, h->stream, (const TA*)A, \
-                     (const TA*)W, bias, (const TA*)R, (TC*)C, partial, p, kps)
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+  const bool wide = pl.NTs == 2;
+#define SK_LAUNCH(LN, NTT, SP, MTT)                                                                                  \
+  hipLaunchKernelGGL((skinny_kernel<TA, TC, EPI, LN, NTT, SP, MTT>), grid, dim3(256), 0, h->stream, (const TA*)o.A, \
+                     (const TA*)o.W, o.bias, (const TA*)o.R, (TC*)o.C, partial, p, pl.kps)
 #define SK_BY_MT(LN, NTT, SP)                                                          \
   do {                                                                                 \
-    if (MTs == 4) SK_LAUNCH(LN, NTT, SP, 4);                                           \
-    else if (MTs == 2) SK_LAUNCH(LN, NTT, SP, 2);                                      \
+    if (pl.MTs == 4) SK_LAUNCH(LN, NTT, SP, 4);                                        \
+    else if (pl.MTs == 2) SK_LAUNCH(LN, NTT, SP, 2);                                   \
     else SK_LAUNCH(LN, NTT, SP, 1);                                                    \
   } while (0)
   {
-    KTimer t(h, SIMULST_K_LINEAR_SKINNY);
+    KTimer t(h, pl.timer);
     if (splits > 1) { if (wide) SK_LAUNCH(false, 2, true, 1); else SK_LAUNCH(false, 1, true, 1); }
-    else if (p.ln_g) { if (wide) SK_BY_MT(true, 2, false); else SK_BY_MT(true, 1, false); }
+    else if (pl.ln) { if (wide) SK_BY_MT(true, 2, false); else SK_BY_MT(true, 1, false); }
     else { if (wide) SK_BY_MT(false, 2, false); else SK_BY_MT(false, 1, false); }
   }
 #undef SK_BY_MT
@@ -347,35 +313,18 @@ int launch_all(simulst_handle* h, const void* A, const void* W, const float* bia
   int rc = sl_launch_status(h, "simulst_linear(skinny)");
   if (rc) return rc;
   if (splits > 1) {
-    KTimer t(h, SIMULST_K_LINEAR_SKINNY);
+    KTimer t(h, pl.timer);
     const long n = (long)p.M * p.N;
     hipLaunchKernelGGL((splitk_epilogue_kernel<TA, TC, EPI>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       h->stream, partial, bias, (const TA*)R, (TC*)C, p, splits);
+                       h->stream, partial, o.bias, (const TA*)o.R, (TC*)o.C, p, splits);
     rc = sl_launch_status(h, "simulst_linear(split-K epilogue)");
   }
   return rc;
 }
 
-template <typename TA>
-int by_epilogue(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R, void* C,
-                const LinArgs& p) {
-  switch (epi) {
-    case SIMULST_EPI_BIAS: return launch_all<TA, TA, SIMULST_EPI_BIAS>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_GELU: return launch_all<TA, TA, SIMULST_EPI_BIAS_GELU>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_RES: return launch_all<TA, TA, SIMULST_EPI_BIAS_RES>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_F32OUT: return launch_all<TA, float, SIMULST_EPI_BIAS>(h, A, W, bias, R, C, p);
-    case SIMULST_EPI_BIAS_RES_GELU: return launch_all<TA, TA, SIMULST_EPI_BIAS_RES_GELU>(h, A, W, bias, R, C, p);
-    default: h->err = "simulst_linear: epilogue not available for decode-step shapes"; return SIMULST_E_ARG;
-  }
-}
-
 }  // namespace
 
-int sl_launch_skinny(simulst_handle* h, int dtype, int epilogue, const void* A, const void* W, const float* bias,
-                     const void* R, void* C, const LinArgs& p) {
-  if (sl_panel_split_wanted(h, dtype, epilogue, p)) return sl_launch_panel_split(h, epilogue, A, W, bias, R, C, p);
-  if (sl_mid_wanted(h, dtype, p)) return sl_launch_mid(h, dtype, epilogue, A, W, bias, R, C, p);
-  if (sl_wave_tile_wanted(dtype, p)) return sl_launch_wave_tile(h, dtype, epilogue, A, W, bias, R, C, p);
-  return dtype == SIMULST_F32 ? by_epilogue<float>(h, epilogue, A, W, bias, R, C, p)
-                              : by_epilogue<bf16>(h, epilogue, A, W, bias, R, C, p);
+int sl_launch_skinny(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  auto go = [&](auto ta, auto tc, auto e) { return launch_all<decltype(ta), decltype(tc), decltype(e)::value>(h, pl, o, p); };
+  return pl.dtype == SIMULST_F32 ? sl_by_decode_epilogue<float>(h, pl.epi, go) : sl_by_decode_epilogue<bf16>(h, pl.epi, go);
 }

@@ -12,7 +12,7 @@
 //   * the epilogue is gemm.hip's bf16 GLU: value * sigmoid(gate) * scale in registers, staged through LDS, 16-byte row segments
 // Same MFMA shape, same k order, same epilogue arithmetic as the 128 x 128 kernel: bit-identical outputs
 // (tests/test_hip_kernels.py::test_subsampler_big_tiles_equal_the_128_tiles).
-#include "gemm_args.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -22,9 +22,6 @@ __device__ long sl_probe_t256[16];
 #else
 #define TPROBE(i)
 #endif
-
-constexpr int TB = 256, TBK = 128, TLD = TBK + 8;                   // tile edge, k depth, LDS row stride (272-byte rows: conflict-free b128)
-constexpr int T_STAGE = 2 * TB * TLD;                               // bf16 elements of the LDS stage (A rows then W rows): 136 KB
 
 __global__ __launch_bounds__(512, 1) void tile256_glu_kernel(const bf16* __restrict__ A, const bf16* __restrict__ W,
                                                              const float* __restrict__ bias, bf16* __restrict__ C, LinArgs p) {
@@ -173,8 +170,6 @@ __global__ __launch_bounds__(512, 1) void tile256_glu_kernel(const bf16* __restr
 //     is fetched from a 64-byte page of zeros: LDS-DMA takes a per-lane source address
 //   * 64-deep tiles also cut the first convolution's padding (K = 400: 448 instead of 512 columns of MFMA work)
 // Same MFMA shape, same ascending k order, same epilogue: bit-identical to both other tile kernels (tests/test_hip_kernels.py).
-constexpr int RBK = 64;
-constexpr int R_STAGE = 2 * TB * RBK * 2;                           // bytes of one stage: 32 KB of A rows + 32 KB of W rows
 __device__ __attribute__((aligned(64))) const unsigned int sl_zero_page[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 typedef __attribute__((address_space(3))) void t_lds_void;
 
@@ -295,37 +290,24 @@ __global__ __launch_bounds__(512, 1) void tile256_ring_kernel(const bf16* __rest
 
 }  // namespace
 
-// bf16 GLU contractions of tall problems whose width is a multiple of 256 (the subsampler at the model's widths), 16-byte aligned
-// output rows
-bool sl_tile256_wanted(const simulst_handle* h, int dtype, int epi, const LinArgs& p, const void* C) {
-  // the kernel addresses its operands with 32-bit element offsets: both must span fewer than 2^31 elements (a 5 000-utterance batch of
-  // the second convolution does not -- it stays on the 128 x 128 kernel's 64-bit pointers)
-  const long a_span = (long)((p.M + p.rpb - 1) / p.rpb) * p.a_bs + (long)p.rpb * p.a_rs + p.K, w_span = (long)p.N * p.K;
-  return h->tile256 && dtype == SIMULST_BF16 && epi == SIMULST_EPI_GLU && p.M >= 8192 && p.N % TB == 0 && p.K % 8 == 0 &&
-         ((p.c_rs | p.c_bs) & 7) == 0 && ((uintptr_t)C & 15) == 0 && !p.w_packed && !p.ln_g && a_span < (1L << 31) && w_span < (1L << 31) &&
-         p.a_bs >= 0 && p.a_rs >= 0;
-}
-
-int sl_launch_tile256(simulst_handle* h, const void* A, const void* W, const float* bias, void* C, const LinArgs& p) {
-  const size_t lds = (size_t)T_STAGE * sizeof(bf16);
-  if (!h->tile256_lds_attr_set) {
-    const hipError_t e = hipFuncSetAttribute((const void*)tile256_glu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { h->err = std::string("simulst_linear(256 x 256 tiles): cannot raise the dynamic LDS limit: ") + hipGetErrorString(e); return (int)e; }
-    h->tile256_lds_attr_set = true;
-  }
-  KTimer t(h, SIMULST_K_LINEAR);
-  const int grid = ((p.M + TB - 1) / TB) * (p.N / TB);
-  if (h->tile256 == 2) {                                             // the LDS-DMA ring (round 6)
-    if (!h->tile256_ring_attr_set) {
-      const hipError_t e = hipFuncSetAttribute((const void*)tile256_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) { h->err = std::string("simulst_linear(256 x 256 tiles, ring): cannot raise the dynamic LDS limit: ") + hipGetErrorString(e); return (int)e; }
-      h->tile256_ring_attr_set = true;
+int sl_launch_tile256(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
+  const void* kernel = pl.ring ? (const void*)tile256_ring_kernel : (const void*)tile256_glu_kernel;
+  bool& attr_set = pl.ring ? h->tile256_ring_attr_set : h->tile256_lds_attr_set;
+  if (!attr_set) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) {
+      h->err = std::string(pl.ring ? "simulst_linear(256 x 256 tiles, ring)" : "simulst_linear(256 x 256 tiles)") +
+               ": cannot raise the dynamic LDS limit: " + hipGetErrorString(e);
+      return (int)e;
     }
-    const size_t lds_ring = 2 * (size_t)R_STAGE > (size_t)TB * (TB / 2 + 8) * 2 ? 2 * (size_t)R_STAGE : (size_t)TB * (TB / 2 + 8) * 2;
-    hipLaunchKernelGGL(tile256_ring_kernel, dim3(grid), dim3(512), lds_ring, h->stream, (const bf16*)A, (const bf16*)W, bias, (bf16*)C, p);
+    attr_set = true;
+  }
+  KTimer t(h, pl.timer);
+  if (pl.ring) {                                                     // the LDS-DMA ring (round 6)
+    hipLaunchKernelGGL(tile256_ring_kernel, dim3(pl.grid[0]), dim3(512), pl.lds, h->stream, (const bf16*)o.A, (const bf16*)o.W, o.bias, (bf16*)o.C, p);
     return sl_launch_status(h, "simulst_linear(256 x 256 tiles on an LDS-DMA ring, GLU)");
   }
-  hipLaunchKernelGGL(tile256_glu_kernel, dim3(grid), dim3(512), lds, h->stream, (const bf16*)A, (const bf16*)W, bias, (bf16*)C, p);
+  hipLaunchKernelGGL(tile256_glu_kernel, dim3(pl.grid[0]), dim3(512), pl.lds, h->stream, (const bf16*)o.A, (const bf16*)o.W, o.bias, (bf16*)o.C, p);
 #ifdef SL_PROBE
   if (p.M > 100000) {
     (void)hipStreamSynchronize(h->stream);

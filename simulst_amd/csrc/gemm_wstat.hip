@@ -21,7 +21,7 @@
 // read : write mix in 64-byte row pieces is.
 // Arithmetic: the products, their order (k-steps 0..7, weights as the A operand) and the epilogue (fp32 bias, fp32 residual add, one
 // rounding) are those of panel_kernel / panel_wide_kernel: results are bit-identical (tests/test_hip_kernels.py).
-#include "gemm_args.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -126,36 +126,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wstat_kernel(const bf16* __rest
 
 }  // namespace
 
-// column slices of a width-N projection: 256- or 192-column slices, at most 4, preferring a count that divides the 32 CUs of an XCD
-// (768 = 4 x 192 uses every CU; 3 x 256 would leave two of 32 idle)
-static bool wstat_split(int N, int& pairs, int& n_slices) {
-  const bool a = N % 256 == 0 && N / 256 <= 4, b = N % 192 == 0 && N / 192 <= 4;
-  if (!a && !b) return false;
-  const bool use_a = a && (!b || 32 % (N / 256) == 0 || 32 % (N / 192) != 0);      // (QKV as 3 x 256: 357 us against 338)
-  pairs = use_a ? 8 : 6;
-  n_slices = N / (32 * pairs);
-  return true;
-}
-
-// Shapes taken: bf16, fragment-major weights, K == 256, plain row-major output, 16-byte aligned rows; N == 256 (one slice) with the
-// Emformer out-proj epilogue, or a bias-only projection whose width splits into slices over an XCD's CUs.
-bool sl_wstat_wanted(const simulst_handle* h, int dtype, int epi, const LinArgs& p, const void* A, const void* C, const void* R) {
-  if (!h->wstat || dtype != SIMULST_BF16 || !p.w_packed || p.K != 256 || p.M < 8192 || p.c_hd != 0 || p.a_lead != 0 || p.ln_g) return false;
-  if ((((uintptr_t)A | (uintptr_t)C | (uintptr_t)R) & 15) != 0) return false;
-  if (((p.a_rs | p.a_bs | p.c_rs | p.c_bs) & 7) != 0) return false;
-  if (epi == SIMULST_EPI_EMF_OUT) return p.N == 256 && ((p.r_rs | p.r_bs | p.aux_bs) & 7) == 0 && h->n_cus >= 8;
-  if (epi != SIMULST_EPI_BIAS) return false;
-  int pairs, n_slices;
-  // every slice of a row tile needs its own compute unit inside ONE XCD (groups of n_slices workgroups per XCD): a device or partition
-  // with fewer than 8 x n_slices units, or an unknown count (n_cus 0), keeps the row panels (the kernel would return at once)
-  return wstat_split(p.N, pairs, n_slices) && (h->n_cus >> 3) >= n_slices;
-}
-
-int sl_launch_wstat(simulst_handle* h, int epi, const void* A, const void* W, const float* bias, const void* R, void* C, void* aux,
-                    const LinArgs& p) {
-  int pairs = 8, n_slices = 1;
-  (void)wstat_split(p.N, pairs, n_slices);
-  const size_t lds = (size_t)2 * pairs * 8 * 64 * 16 + (size_t)32 * pairs * sizeof(float);
+int sl_launch_wstat(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
   if (!h->wstat_lds_attr_set) {
     hipError_t e = hipFuncSetAttribute((const void*)wstat_kernel<SIMULST_EPI_BIAS, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wstat_kernel<SIMULST_EPI_BIAS, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -163,12 +134,11 @@ int sl_launch_wstat(simulst_handle* h, int epi, const void* A, const void* W, co
     if (e != hipSuccess) { h->err = std::string("simulst_linear(weight-stationary): cannot raise the dynamic LDS limit: ") + hipGetErrorString(e); return (int)e; }
     h->wstat_lds_attr_set = true;
   }
-  KTimer t(h, SIMULST_K_LINEAR);
-  const int grid = h->n_cus & ~7;                                    // one workgroup per CU, whole XCD rounds
-#define WSTAT(E, P) hipLaunchKernelGGL((wstat_kernel<E, P>), dim3(grid), dim3(WS_THREADS), lds, h->stream, (const bf16*)A, (const bf16*)W, bias, \
-                                      (const bf16*)R, (bf16*)C, (bf16*)aux, p, n_slices)
-  if (epi == SIMULST_EPI_EMF_OUT) WSTAT(SIMULST_EPI_EMF_OUT, 8);
-  else if (pairs == 8) WSTAT(SIMULST_EPI_BIAS, 8);
+  KTimer t(h, pl.timer);
+#define WSTAT(E, P) hipLaunchKernelGGL((wstat_kernel<E, P>), dim3(pl.grid[0]), dim3(WS_THREADS), pl.lds, h->stream, (const bf16*)o.A, (const bf16*)o.W, \
+                                      o.bias, (const bf16*)o.R, (bf16*)o.C, (bf16*)o.aux, p, pl.n_slices)
+  if (pl.epi == SIMULST_EPI_EMF_OUT) WSTAT(SIMULST_EPI_EMF_OUT, 8);
+  else if (pl.pairs == 8) WSTAT(SIMULST_EPI_BIAS, 8);
   else WSTAT(SIMULST_EPI_BIAS, 6);
 #undef WSTAT
   return sl_launch_status(h, "simulst_linear(weight-stationary rows)");

@@ -349,9 +349,9 @@ def assert_timed_kernels_selected(ops, enc, B, Te):
     S, R = enc.cfg.S, enc.cfg.R
     N = math.ceil(Te / S)
     rows_z, rows_c = (N - 1) + N * R + Te + N, N * R + Te + N
-    # gemm_tile256.hip sl_tile256_wanted: p.M >= 8192 at the second convolution (B x Te output rows)
+    # gemm_plan.cpp tile256_ok: p.M >= 8192 at the second convolution (B x Te output rows)
     assert B * Te >= 8192
-    # gemm_wstat.hip sl_wstat_wanted: p.M >= 8192 for the Q|K|V product (B x rows_z) and the out-proj (B x rows_c)
+    # gemm_plan.cpp wstat_ok: p.M >= 8192 for the Q|K|V product (B x rows_z) and the out-proj (B x rows_c)
     assert B * rows_z >= 8192 and B * rows_c >= 8192
 
 
