@@ -70,7 +70,9 @@ enum { SIMULST_K_LINEAR = 0, SIMULST_K_LAYERNORM = 1, SIMULST_K_EMF_ATTN = 2, SI
        SIMULST_K_ARGMAX = 7, SIMULST_K_MISC = 8, SIMULST_K_LINEAR_SKINNY = 9, SIMULST_K_LINEAR_TILE64 = 10,
        /* round 4: the row-local layer chains of the decode step, one class per kernel (csrc/dec_chain.hip) */
        SIMULST_K_DEC_QKV_CHAIN = 11, SIMULST_K_DEC_PROJ_CHAIN = 12, SIMULST_K_DEC_FFN_CHAIN = 13,
-       SIMULST_K_DEC_ATTN_CHAIN = 14, SIMULST_K_DEC_VOCAB_CHAIN = 15, SIMULST_K_COUNT = 16 };
+       SIMULST_K_DEC_ATTN_CHAIN = 14, SIMULST_K_DEC_VOCAB_CHAIN = 15,
+       /* the pipelined tile of the decode step's tall GEMMs (fc2 above the feed-forward chain's rows, csrc/dec_gemm_tall.hip) */
+       SIMULST_K_DEC_TALL_GEMM = 16, SIMULST_K_COUNT = 17 };
 
 /* ---- handle ------------------------------------------------------------------ */
 int simulst_create(simulst_handle** out, void* hip_stream);
@@ -138,11 +140,17 @@ int simulst_graph_enable(simulst_handle* h, int on);
  *   DEC_CHAIN_ROWS32        EXPERIMENTS builds only, measured slower; 1 (default 0): the projection / feed-forward / QKV chains of the decode
  *                              loops take 32-row tiles from 256 rows on (a weight fragment serves two row tiles; the 16 MFMAs of a unit
  *                              and row tile are one asm statement, csrc/dec_chain.hip mfma_block; identical results)
+ *   DEC_TALL_FFN            0: above the feed-forward chain's rows the decode loops launch fc2 + residual and LN3 + fc1 + GELU through
+ *                              simulst_linear (its k-interleaved 64 x 32 tile, its split row panel); default 1: fc1 from 2560 rows on its
+ *                              two-stage panel and bf16 rows with fragment-major weights take the pipelined
+ *                              64 x 64 tile of csrc/dec_gemm_tall.hip (two LDS stages of the weight block, the next chunk's loads in
+ *                              flight behind the MFMAs; the same k partition and summation order: identical results)
  * Returns SIMULST_E_ARG for an unknown option or a value outside its range. */
 enum { SIMULST_OPT_VALU_ATTENTION = 0, SIMULST_OPT_UNFUSED_DECODE = 1, SIMULST_OPT_FFN_WAVES = 2, SIMULST_OPT_DEC_CHAIN = 3,
        SIMULST_OPT_DEC_ATTN_CHAIN_MAX_ROWS = 4, SIMULST_OPT_DEC_ATTN_CHAIN_ROWS = 5, SIMULST_OPT_FUSED_ARGMAX = 6,
        SIMULST_OPT_DEC_VOCAB_CHAIN_SPLIT = 7, SIMULST_OPT_DEC_EMBED_QKV_CHAIN = 8, SIMULST_OPT_PANEL_WIDE = 9,
-       SIMULST_OPT_DEC_FUSE_PROJ_CROSS = 10, SIMULST_OPT_WEIGHT_STATIONARY = 11, SIMULST_OPT_CONV_TILE256 = 12, SIMULST_OPT_DEC_FUSE_FFN_QKV = 13, SIMULST_OPT_DEC_CHAIN_ROWS32 = 14 };
+       SIMULST_OPT_DEC_FUSE_PROJ_CROSS = 10, SIMULST_OPT_WEIGHT_STATIONARY = 11, SIMULST_OPT_CONV_TILE256 = 12, SIMULST_OPT_DEC_FUSE_FFN_QKV = 13, SIMULST_OPT_DEC_CHAIN_ROWS32 = 14,
+       SIMULST_OPT_DEC_TALL_FFN = 15 };
 int simulst_set_option(simulst_handle* h, int32_t option, int32_t value);
 /* the value a handle currently runs with (simulst_create's environment overrides included) */
 int simulst_get_option(simulst_handle* h, int32_t option, int32_t* value);
@@ -223,6 +231,18 @@ typedef struct {
 
 int simulst_linear(simulst_handle* h, const simulst_linear_desc* d, const void* A, const void* W,
                    const float* bias, const void* R, void* C, void* aux);
+/* The decode step's tall fc2 launch on its own (csrc/dec_gemm_tall.hip; the decode loops take it above the feed-forward chain's rows,
+ * SIMULST_OPT_DEC_TALL_FFN): C [B][N] = A [B][K] . W^T + bias + R, bf16, W fragment-major (simulst_pack_fragment_major), contiguous
+ * 16-byte aligned operands, C may alias R.  Bit for bit what simulst_linear writes for the same operands with SIMULST_EPI_BIAS_RES; taken
+ * only where that call runs its k-interleaved tile without split-K (N < 512, 256 < K < 4096, N % 16 == 0, K % 32 == 0, up to 8192
+ * rows), else SIMULST_E_SHAPE. */
+int simulst_dec_tall_gemm(simulst_handle* h, const void* A, const void* W, const float* bias, const void* R, void* C,
+                          int32_t B, int32_t N, int32_t K, int32_t dtype);
+/* ... and its fc1 launch: C [B][N] = gelu(LayerNorm(A [B][K]) . W^T + bias), K <= 256, bias (if given) 16-byte aligned.  Bit for bit what
+ * simulst_linear writes with ln_gamma / ln_beta and SIMULST_EPI_BIAS_GELU; taken only where that call runs its split row panel (2560 rows
+ * and more at the defaults, N >= 512), else SIMULST_E_SHAPE. */
+int simulst_dec_tall_fc1(simulst_handle* h, const void* A, const void* W, const float* bias, const float* ln_g, const float* ln_b,
+                         void* C, int32_t B, int32_t N, int32_t K, int32_t dtype);
 
 /* ---- feature front-end -----------------------------------------
  * Kaldi-compatible log-mel filterbank of B waveforms: frame f of row b covers samples [160 f, 160 f + 400) of

@@ -20,10 +20,10 @@ EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_GLU, EPI_EMF_OUT, EPI_BIAS_F32OUT, EP
 ATTN_HARD, ATTN_INFINITE_LOOKBACK, ATTN_WAITK, ATTN_CHUNKWISE, ATTN_FULL = range(5)
 (K_LINEAR, K_LAYERNORM, K_EMF_ATTN, K_CONV_POS, K_DEC_SELF_ATTN, K_DEC_CROSS_ATTN, K_SCAN, K_ARGMAX,
  K_MISC, K_LINEAR_SKINNY, K_LINEAR_TILE64, K_DEC_QKV_CHAIN, K_DEC_PROJ_CHAIN, K_DEC_FFN_CHAIN, K_DEC_ATTN_CHAIN,
- K_DEC_VOCAB_CHAIN, K_COUNT) = range(17)
+ K_DEC_VOCAB_CHAIN, K_DEC_TALL_GEMM, K_COUNT) = range(18)
 KERNEL_CLASS_NAMES = ["linear", "layernorm", "emformer_attention", "conv_pos", "decoder_self_attention",
                       "decoder_cross_attention", "scan", "argmax", "misc", "linear_skinny", "linear_tile64",
-                      "dec_qkv_chain", "dec_proj_chain", "dec_ffn_chain", "dec_attn_proj_chain", "dec_vocab_chain"]
+                      "dec_qkv_chain", "dec_proj_chain", "dec_ffn_chain", "dec_attn_proj_chain", "dec_vocab_chain", "dec_tall_gemm"]
 
 ATTN_ENUM = {"hard_aligned": ATTN_HARD, "infinite_lookback": ATTN_INFINITE_LOOKBACK,
              "waitk": ATTN_WAITK, "chunkwise": ATTN_CHUNKWISE, "full": ATTN_FULL}
@@ -111,6 +111,8 @@ SIGNATURES = {
     "simulst_stream_destroy": [_vp],
     "simulst_pack_fragment_major": [_vp, _vp, _vp, _i32, _i32, _i32],
     "simulst_linear": [_vp, C.POINTER(LinearDesc), _vp, _vp, _vp, _vp, _vp, _vp],
+    "simulst_dec_tall_gemm": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32],
+    "simulst_dec_tall_fc1": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32],
     "simulst_conv_pos": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32],
     "simulst_ctc_best_alignment_scratch_bytes": [_i32, _i32, _i32],
     "simulst_ctc_best_alignment": [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
@@ -194,7 +196,7 @@ DEBUG_SIGNATURES = {
 }
 (OPT_VALU_ATTENTION, OPT_UNFUSED_DECODE, OPT_FFN_WAVES, OPT_DEC_CHAIN, OPT_DEC_ATTN_CHAIN_MAX_ROWS, OPT_DEC_ATTN_CHAIN_ROWS,
  OPT_FUSED_ARGMAX, OPT_DEC_VOCAB_CHAIN_SPLIT, OPT_DEC_EMBED_QKV_CHAIN, OPT_PANEL_WIDE, OPT_DEC_FUSE_PROJ_CROSS,
- OPT_WEIGHT_STATIONARY, OPT_CONV_TILE256, OPT_DEC_FUSE_FFN_QKV, OPT_DEC_CHAIN_ROWS32) = range(15)
+ OPT_WEIGHT_STATIONARY, OPT_CONV_TILE256, OPT_DEC_FUSE_FFN_QKV, OPT_DEC_CHAIN_ROWS32, OPT_DEC_TALL_FFN) = range(16)
 
 _lib = None
 ABI_VERSION = 108          # simulst_version(): bumped whenever a descriptor structure changes (csrc/handle.cpp)

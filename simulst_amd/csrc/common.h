@@ -52,6 +52,8 @@ struct simulst_handle {
   int dec_chain_min_rows;      // rows from which the chains replace the per-GEMM launches (below: head-split block)
   int dec_chain_max_rows;      // rows above which the per-GEMM launches are kept
   int dec_chain_ffn_max_rows;  // rows up to which the feed-forward chain is used as well
+  bool dec_tall_ffn;           // SIMULST_OPT_DEC_TALL_FFN: fc2 of the per-GEMM feed-forward on the pipelined tile (dec_gemm_tall.hip)
+  int dec_tall_min_rows;       //   ... from this many rows on
   bool dec_chain_lds_attr_set;
   int dec_chain_lds_bytes;     // dynamic LDS requested per chain workgroup (0: the default, dec_chain.hip lds_request)
   bool dec_chain_probe_attr_set;

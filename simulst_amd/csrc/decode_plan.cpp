@@ -12,9 +12,41 @@ static constexpr bool HEAD_SPLIT_BUILT = false;
 
 // The row classes of a step, in ascending order of their switch points (handle.cpp): up to fuse_q_max_rows the query projection
 // rides inside the policy launch; from dec_chain_min_rows on sl_dec_chain_ok admits the layer chains; up to dec_chain_ffn_max_rows
-// the feed-forward chain runs as well.  The plan and the retire floor both read them here.
+// the feed-forward chain runs as well; above that the projection chain stays and the feed-forward block is three launches (cross
+// out-proj + residual, LN3 + fc1 + GELU, fc2 + residual) -- the first two through simulst_linear, from dec_tall_min_rows on fc2, and from
+// panel_split_min_rows on fc1 too, on the kernels of dec_gemm_tall.hip (tall_ffn, tall_fc1: the bits of the simulst_linear launches
+// they replace, so no row class of their own and no entry in the retire floor).  The plan and the retire floor both read them here.
 static bool rows_fuse_q(const simulst_handle* h, int B) { return B <= h->fuse_q_max_rows; }
 static bool rows_chain_ffn(const simulst_handle* h, int B) { return B <= h->dec_chain_ffn_max_rows; }
+
+// fc2 + residual as sl_step_ffn hands it to sl_lin: what simulst_linear would launch decides whether the tall tile may stand in
+bool sl_dec_tall_fc2_shape_ok(const simulst_handle* h, int dtype, int B, int N, int K, bool packed) {
+  if (dtype != SIMULST_BF16 || !packed || B <= 0 || N <= 0 || K <= 0) return false;
+  LinArgs p = {};
+  p.M = B; p.rpb = B; p.N = N; p.K = K;
+  p.a_rs = K; p.c_rs = N; p.r_rs = N;
+  p.scale = 1.f; p.w_packed = 1; p.amax_skip_a = p.amax_skip_b = -1;
+  const sl_linear_ops o = {};
+  const sl_linear_plan pl = sl_plan_linear(h, dtype, SIMULST_EPI_BIAS_RES, p, o);
+  return pl.family == SL_LIN_SKINNY && pl.splits == 1;
+}
+bool sl_dec_tall_fc1_shape_ok(const simulst_handle* h, int dtype, int B, int N, int K, bool packed) {
+  if (dtype != SIMULST_BF16 || !packed || B <= 0 || N <= 0 || K <= 0 || K > 256) return false;
+  LinArgs p = {};
+  p.M = B; p.rpb = B; p.N = N; p.K = K;
+  p.a_rs = K; p.c_rs = N; p.r_rs = N;
+  p.scale = 1.f; p.w_packed = 1; p.amax_skip_a = p.amax_skip_b = -1;
+  p.ln_g = p.ln_b = (const float*)h;              // any non-null affine: the prologue is part of the shape test
+  const sl_linear_ops o = {};
+  const sl_linear_plan pl = sl_plan_linear(h, dtype, SIMULST_EPI_BIAS_GELU, p, o);
+  return pl.family == SL_LIN_PANEL_SPLIT;
+}
+bool sl_dec_tall_fc1_ok(const simulst_handle* h, int dtype, int B, int D, int F, bool packed) {
+  return h->dec_tall_ffn && B >= h->dec_tall_min_rows && sl_dec_tall_fc1_shape_ok(h, dtype, B, F, D, packed);
+}
+bool sl_dec_tall_fc2_ok(const simulst_handle* h, int dtype, int B, int D, int F, bool packed) {
+  return h->dec_tall_ffn && B >= h->dec_tall_min_rows && sl_dec_tall_fc2_shape_ok(h, dtype, B, D, F, packed);
+}
 
 sl_decode_plan sl_plan_decode(const simulst_handle* h, const sl_decode_call& c) {
   sl_decode_plan p = {};
@@ -39,6 +71,8 @@ sl_decode_plan sl_plan_decode(const simulst_handle* h, const sl_decode_call& c) 
   p.proj_cross = own_rows && !c.cif && p.chain && !p.attn_chain &&
                  sl_dec_proj_cross_fused_ok(h, c.dtype, c.B, c.H, d, c.S_cap, c.attn_type, lockstep, false);
   p.fuse_ffn_qkv = p.chain_ffn && !p.attn_chain && sl_dec_ffn_qkv_chain_ok(h, c.B, c.F);
+  p.tall_ffn = !p.chain_ffn && !c.force_unfused && sl_dec_tall_fc2_ok(h, c.dtype, c.B, c.D, c.F, c.packed);
+  p.tall_fc1 = !p.chain_ffn && !c.force_unfused && sl_dec_tall_fc1_ok(h, c.dtype, c.B, c.D, c.F, c.packed);
   // Greedy pick fused into the vocabulary projection: the masks must be known when the projection is launched.  Streaming masks
   // nothing, forced decoding masks pad + eos, free offline decoding masks eos only at position 0, which the host can tell only for
   // lockstep rows.
@@ -96,7 +130,16 @@ int sl_step_ffn(simulst_handle* h, const sl_decode_plan& p, const sl_step_bufs& 
                             w.B, w.F);
   int rc;
   if ((rc = sl_lin(h, w.dtype, w.B, w.D, w.D, ctx, f.c_wo, f.c_bo, res, w.x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, w.packed))) return rc;
-  if ((rc = sl_lin(h, w.dtype, w.B, w.F, w.D, w.x, f.fc1, f.b1, nullptr, w.hidden, SIMULST_EPI_BIAS_GELU, f.ln_g, f.ln_b, w.packed))) return rc;
+  // (the workspace rows and packed weights of a decode call are whole allocations or 16-byte multiples into them, and the launches
+  //  around these read the same buffers with 16-byte loads: the alignment test guards the tall tiles' vector accesses of a caller's
+  //  odd buffer, which then takes the simulst_linear launch -- the same bits, its own timer class)
+  if (p.tall_fc1 && f.ln_g && f.ln_b && sl_dec_tall_operands_ok(w.x, f.fc1, w.hidden, f.b1))
+    rc = sl_dec_tall_fc1(h, w.x, f.fc1, f.b1, f.ln_g, f.ln_b, w.hidden, w.B, w.F, w.D);
+  else
+    rc = sl_lin(h, w.dtype, w.B, w.F, w.D, w.x, f.fc1, f.b1, nullptr, w.hidden, SIMULST_EPI_BIAS_GELU, f.ln_g, f.ln_b, w.packed);
+  if (rc) return rc;
+  if (p.tall_ffn && sl_dec_tall_operands_ok(w.hidden, f.fc2, w.x, w.x))
+    return sl_dec_tall_fc2(h, w.hidden, f.fc2, f.b2, w.x, w.x, w.B, w.D, w.F);
   return sl_lin(h, w.dtype, w.B, w.D, w.F, w.hidden, f.fc2, f.b2, w.x, w.x, SIMULST_EPI_BIAS_RES, nullptr, nullptr, w.packed);
 }
 

@@ -44,6 +44,10 @@ extern "C" int simulst_create(simulst_handle** out, void* hip_stream) {
   if (const char* e = getenv("SIMULST_DEC_CHAIN_MAX_ROWS")) h->dec_chain_max_rows = atoi(e);
   h->dec_chain_ffn_max_rows = 1024;     // measured (bench.py --steps 20): 448-row sequences +4 %, 640 +2 %, 1280 -2 %, 4096 -3 %
   if (const char* e = getenv("SIMULST_DEC_CHAIN_FFN_MAX_ROWS")) h->dec_chain_ffn_max_rows = atoi(e);
+  h->dec_tall_ffn = true;
+  if (const char* e = getenv("SIMULST_DEC_TALL_FFN")) h->dec_tall_ffn = atoi(e) != 0;
+  h->dec_tall_min_rows = h->dec_chain_ffn_max_rows + 1;      // where the feed-forward chain ends
+  if (const char* e = getenv("SIMULST_DEC_TALL_MIN_ROWS")) h->dec_tall_min_rows = atoi(e);
   h->dec_chain_lds_attr_set = false;
   h->dec_chain_probe_attr_set = false;
   h->dec_chain_lds_bytes = 0;
@@ -240,6 +244,7 @@ extern "C" int simulst_set_option(simulst_handle* h, int32_t option, int32_t val
     case SIMULST_OPT_FUSED_ARGMAX: h->fused_argmax = value != 0; return SIMULST_OK;
     case SIMULST_OPT_DEC_EMBED_QKV_CHAIN: h->dec_embed_qkv_chain = value != 0; return SIMULST_OK;
     case SIMULST_OPT_WEIGHT_STATIONARY: h->wstat = value != 0; return SIMULST_OK;
+    case SIMULST_OPT_DEC_TALL_FFN: h->dec_tall_ffn = value != 0; return SIMULST_OK;
     case SIMULST_OPT_CONV_TILE256:
       SL_REQUIRE(h, value >= 0 && value <= 2, SIMULST_E_ARG, "simulst_set_option(CONV_TILE256): 0 (128 x 128 tiles), 1 (256 x 256, register stage), 2 (256 x 256, LDS-DMA ring)");
       h->tile256 = value; return SIMULST_OK;
@@ -298,6 +303,7 @@ extern "C" int simulst_get_option(simulst_handle* h, int32_t option, int32_t* va
     case SIMULST_OPT_PANEL_WIDE: *value = h->panel_wide ? (h->panel_wide_plain_stores ? 2 : 1) : 0; return SIMULST_OK;
     case SIMULST_OPT_DEC_VOCAB_CHAIN_SPLIT: *value = h->dec_vocab_chain_split; return SIMULST_OK;
     case SIMULST_OPT_WEIGHT_STATIONARY: *value = h->wstat; return SIMULST_OK;
+    case SIMULST_OPT_DEC_TALL_FFN: *value = h->dec_tall_ffn; return SIMULST_OK;
     case SIMULST_OPT_CONV_TILE256: *value = h->tile256; return SIMULST_OK;
     case SIMULST_OPT_DEC_FUSE_FFN_QKV: *value = h->dec_fuse_ffn_qkv; return SIMULST_OK;
     case SIMULST_OPT_DEC_CHAIN_ROWS32: *value = h->dec_chain_rows32; return SIMULST_OK;
