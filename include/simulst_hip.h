@@ -487,7 +487,14 @@ int simulst_step_p_choose_padded(simulst_handle* h, const void* q, const void* K
  * delays [B][T_cap] fp32, tail_w [B] fp32, alpha_sum [B] fp32.  One wavefront prefix-sum of
  * alpha per utterance, fire index floor(csum/beta), segmented weighted sum.
  * Replaces torch_cif.cif_function as called from models/cif_transformer.py:171-178,228-233
- * (inference form: no target_lengths). */
+ * (inference form: no target_lengths).
+ * src_len [B] or NULL (every row S frames): row b integrates its first min(src_len[b], S) frames; x and alpha at or beyond
+ * src_len[b] are never read, so padded rows may hold anything, NaN included.
+ * T_cap below a row's slot count: the slots below T_cap are written as usual, nothing is written outside out / delays, and
+ * cif_len[b] still reports the row's TRUE count -- cif_len[b] > T_cap is how a caller detects the overflow.
+ * A total that is an exact multiple of beta (0 included) with tail_thres == 0 has a tail of weight 0 >= 0: the tail slot is
+ * 0 * (beta / 0) = NaN, as in cif_function.
+ * SIMULST_E_SHAPE: C % 4 != 0, beta <= 0, or more than 64 KB of LDS (4 S + T_cap + 1 floats). */
 int simulst_cif_integrate(simulst_handle* h, const void* x, const float* alpha, const int32_t* src_len,
                           void* out, int32_t* cif_len, float* delays, float* tail_w, float* alpha_sum,
                           int32_t B, int32_t S, int32_t C, int32_t T_cap, float beta, float tail_thres,

@@ -586,7 +586,8 @@ __global__ __launch_bounds__(256) void cif_kernel(const T* __restrict__ x, const
       continue;
     }
     const int first = t > 0 ? send[t - 1] : 0;       // the frame that closed slot t-1 carries its remainder into t
-    const int last = tail ? S - 1 : send[t];
+    // the tail ends with the row: frames at or beyond src_len weigh 0, but fmaf(0, NaN, acc) is NaN and padded rows need not be finite
+    const int last = tail ? max(min(len, S), 0) - 1 : send[t];
     const bool whole = !tail && fn[last] > 1 && li[last] < t;     // a frame with alpha > beta fills whole slots
     for (int c = l32 * 8; c < C; c += 256) {
       const bool hi = c + 4 < C;                      // second group of 4 channels present (C % 8 may be 4)
