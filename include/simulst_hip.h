@@ -1002,6 +1002,38 @@ int simulst_joiner_emit(simulst_handle* h, const float* P, const float* g, const
  * scatter of :176-180). */
 int simulst_joiner_mask_blank(simulst_handle* h, float* logits, const int32_t* at_eos, int32_t B, int32_t V, int32_t blank);
 
+/* The joiner over a whole target (:143-163 with no incremental state, and what criterion/rnnt_criterion.py:82-147 reads from it):
+ * P fp32 [B][S][D] as above, G fp32 [B][U1][D] = target_projection of the prediction network at every decoder-input position
+ * (U1 = longest target + 1), W_fm as above, labels int32 [B][U1] (labels[b][u] = the token taken from input position u; values
+ * outside [0, V) are clamped), src_len[b] (clamped to [0, S]) and tgt_len[b] = n_b, the target length with its EOS (clamped to
+ * [0, U1 - 1]).  For every cell with s < src_len[b] and u <= tgt_len[b], logits = W . tanh(P[b][s] + G[b][u]) (the tanh rounded to
+ * the model dtype, fp32 accumulation; no forced blank -- that edit is incremental-only) and
+ *   lp_blank[b][s][u] = logits[blank]        - logsumexp(logits)
+ *   lp_label[b][s][u] = logits[labels[b][u]] - logsumexp(logits)      for u < tgt_len[b]
+ * both fp32 [B][S][U1]; other cells are not written.  The [B][S][U1][V] logits never exist: every vocabulary part p of n_split
+ * leaves (max, sum of exp(. - max), blank logit, label logit) in partials, fp32 [B][S][U1][n_split][4] (a part that does not hold
+ * the blank / label column leaves -1e30 there), and a fold kernel of the same call finishes them.  Row tiles that lie wholly
+ * outside the valid cells are skipped.  SIMULST_E_ARG as above and for U1 < 1; SIMULST_E_SHAPE when the row panel
+ * (128 rows bf16 / 64 rows fp32 of D + 8 / D + 4 elements) exceeds 144 KB of LDS. */
+int simulst_joiner_lattice(simulst_handle* h, const float* P, const float* G, const void* W_fm, const int32_t* labels,
+                           const int32_t* src_len, const int32_t* tgt_len, float* partials, float* lp_blank, float* lp_label,
+                           int32_t B, int32_t S, int32_t U1, int32_t D, int32_t V, int32_t blank, int32_t n_split, int32_t dtype);
+
+/* RNN-T forward recursion over lp_blank / lp_label fp32 [B][S][U1] (natural log; warp_rnnt's definition), per row with
+ * S_b = src_len[b], n_b = tgt_len[b] (n_b == 0 is valid: the sum of the blanks):
+ *   alpha[0][0] = 0,  alpha[s][u] = logaddexp(alpha[s-1][u] + lp_blank[s-1][u], alpha[s][u-1] + lp_label[s][u-1])
+ *   ll[b] = alpha[S_b-1][n_b] + lp_blank[S_b-1][n_b]                   (-inf for S_b < 1)
+ * One workgroup per row, anti-diagonals in LDS, fp32.  With best_ll, emit and backptr all non-NULL (all NULL otherwise) the same
+ * recursion runs with max in place of logaddexp: best_ll[b] is the best single alignment's score, backptr (bytes, [B][S][U1],
+ * scratch) holds one move per cell, and emit[b][u] int32 [B][U1] is the frame s at which label u is taken on that alignment, for
+ * u < n_b (other entries are not written).  Tie rule: a cell takes the label move (from (s, u-1)) only when it is STRICTLY better
+ * than the blank move (from (s-1, u)); on equal scores the blank move is kept, so the back-track from (S_b-1, n_b) places a tied
+ * label at the earlier frame.  SIMULST_E_ARG: S < 1, U1 < 1, B < 0; SIMULST_E_SHAPE: U1 > 4096 (the diagonal does not fit in LDS --
+ * refused, not truncated). */
+int simulst_rnnt_forward(simulst_handle* h, const float* lp_blank, const float* lp_label, const int32_t* src_len,
+                         const int32_t* tgt_len, float* ll, float* best_ll, int32_t* emit, uint8_t* backptr, int32_t B, int32_t S,
+                         int32_t U1);
+
 #ifdef __cplusplus
 }
 #endif

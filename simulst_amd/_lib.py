@@ -177,6 +177,8 @@ SIGNATURES = {
     "simulst_joiner_scan": [_vp] * 9 + [_i32] * 7,
     "simulst_joiner_emit": [_vp] * 10 + [_i32] * 7,
     "simulst_joiner_mask_blank": [_vp, _vp, _vp, _i32, _i32, _i32],
+    "simulst_joiner_lattice": [_vp] * 10 + [_i32] * 8,
+    "simulst_rnnt_forward": [_vp] * 9 + [_i32] * 3,
 }
 ENERGY_SOFT, ENERGY_MONOTONIC, ENERGY_WAITK = range(3)
 

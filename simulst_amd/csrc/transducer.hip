@@ -9,6 +9,11 @@
 //   simulst_joiner_emit       first scanned position whose best non-blank beats the blank, -1e4 blank at src_len' - 1 (:170-200);
 //                             prev_emit <- new_emit, z[b] = tanh(P[b, new_emit] + g[b]), at_eos[b]
 //   simulst_joiner_mask_blank logits[b][blank] <- -1e4 where at_eos[b] (the gathered row of :203-206 keeps the scatter of :176-180)
+//   simulst_joiner_lattice    the joiner over a whole target (:143-163 with no incremental state): log p(blank) and log p(label) of
+//                             every (s, u) cell, an online log-sum-exp over vocabulary tiles -- the [B][S'][U + 1][V] logits that
+//                             criterion/rnnt_criterion.py:90-92 normalises are never written
+//   simulst_rnnt_forward      the forward recursion over that lattice (warp_rnnt's log-likelihood, :112-122) and, on request, the
+//                             best single alignment with the frame each label is emitted at
 //
 // The scan is a [16 R positions] x [V] x [D] contraction per workgroup on the matrix cores: the A operand rows are made on the fly
 // (tanh of P + g, rounded to the model dtype) into LDS, the B operand is W_out in fragment-major order (gemv_mfma.h), one 16-byte
@@ -255,6 +260,301 @@ __global__ void joiner_mask_blank_kernel(float* __restrict__ logits, const int32
   if (b < B && at_eos[b]) logits[(long)b * V + blank] = -1e4f;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- lattice
+// The whole-target joiner: rows are the cells (b, s, u).  A row tile is one (b, s) with 16 consecutive u; the list of tiles is
+// [b][s][ut] (ut < u_tiles) and a workgroup takes R consecutive ones as its LDS panel, 16 R rows of tanh(P[b][s] + G[b][u]).
+// The panel is tall (128 rows bf16, 64 rows fp32: about 66 KB at D = 256, two workgroups per compute unit) so that W_out is read
+// from L2 once per 128 rows (by each of a bf16 workgroup's two row groups), and every A fragment read from LDS feeds two
+// vocabulary tiles (2 MFMAs per ds_read_b128: one read per MFMA would need the LDS array's whole 256 B/clk).  Each lane keeps a running (max, sum) of its own column stripe per row;
+// the 16 columns and the 4 waves fold at the end.  The blank and label logits are plain dot products of the same panel (2 of the
+// V columns per row), taken by the vocabulary part that holds the column.
+template <typename T> struct LatCfg;
+// R row tiles per workgroup in THREADS / 256 row groups, each swept by 4 waves that split the vocabulary.  bf16: two groups of 4 tiles
+// (8 waves, 4 per SIMD with two workgroups per compute unit) measured 0.78 ms against 0.90 ms for one group of 8 tiles on 4 waves and
+// 0.95 ms for 6 tiles on 4 waves with three workgroups per compute unit (the bench shape of tools/transducer_score_bench.py)
+template <> struct LatCfg<bf16> { static constexpr int R = 8, THREADS = 512; };
+template <> struct LatCfg<float> { static constexpr int R = 4, THREADS = 256; };
+
+constexpr float LAT_NEG = -1e30f;         // "no column yet": finite, so that max - max never makes a NaN
+
+template <typename T> __device__ __forceinline__ f32x4 lat_mma(const uint4& a, const uint4& w, f32x4 acc) {
+  if constexpr (std::is_same<T, float>::value) {
+    const float* af = reinterpret_cast<const float*>(&a);
+    const float* wf = reinterpret_cast<const float*>(&w);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[e], wf[e], acc, 0, 0, 0);
+    return acc;
+  } else {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(&a), *reinterpret_cast<const bf16x8_t*>(&w),
+                                                   acc, 0, 0, 0);
+  }
+}
+
+// (m, s) <- (m, s) joined with (om, os): s counts exp(x - m)
+__device__ __forceinline__ void lse_join(float& m, float& s, float om, float os) {
+  const float mx = fmaxf(m, om);
+  s = s * __expf(m - mx) + os * __expf(om - mx);
+  m = mx;
+}
+
+// grid (ceil(B * S * u_tiles / R), n_split).  part[cell][p] = (max, sum, blank logit, label logit) of vocabulary part p.
+template <typename T>
+__global__ __launch_bounds__(LatCfg<T>::THREADS, LatCfg<T>::THREADS / 128) void joiner_lattice_kernel(
+    const float* __restrict__ P, const float* __restrict__ Gt, const T* __restrict__ Wp, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ src_len, const int32_t* __restrict__ tgt_len, float* __restrict__ part, int B, int S, int U1, int D,
+    int V, int blank, int n_split, int u_tiles) {
+  constexpr int R = LatCfg<T>::R, ROWS = 16 * R, THREADS = LatCfg<T>::THREADS;
+  constexpr int RW = R / (THREADS / 256);                   // row tiles of one wave
+  constexpr int KS = gemv::MF<T>::KS, G = gemv::MF<T>::G;
+  static_assert(R % (THREADS / 256) == 0 && ROWS <= 256, "row groups");
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int ldz = D + G;
+  T* zs = reinterpret_cast<T*>(smem_raw);
+  __shared__ float red_m[4][ROWS], red_s[4][ROWS];
+  __shared__ float cap[ROWS][2];                            // blank / label logit of the row (LAT_NEG: not in this part)
+  __shared__ int row_lab[ROWS];                             // label column of the row, -1: none
+  __shared__ int tile_b[R], tile_s[R], tile_u0[R], tile_n[R];      // rows u0 .. u0 + n - 1 of (b, s) are valid cells (n == 0: none)
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3, rbase = (tid >> 8) * RW;
+  const long n_tiles = (long)B * S * u_tiles;
+  if (tid < R) {
+    const long gt = (long)blockIdx.x * R + tid;
+    int b = 0, s = 0, u0 = 0, n = 0;
+    if (gt < n_tiles) {
+      b = (int)(gt / ((long)S * u_tiles));
+      const int rem = (int)(gt - (long)b * S * u_tiles);
+      s = rem / u_tiles;
+      u0 = 16 * (rem - s * u_tiles);
+      const int sl = clampi(src_len[b], 0, S), tl = clampi(tgt_len[b], 0, U1 - 1);
+      if (s < sl) n = clampi(tl + 1 - u0, 0, 16);
+    }
+    tile_b[tid] = b; tile_s[tid] = s; tile_u0[tid] = u0; tile_n[tid] = n;
+  }
+  __syncthreads();
+  bool any = false;
+#pragma unroll
+  for (int r = 0; r < R; ++r) any |= tile_n[r] > 0;
+  if (!any) return;                                         // every row tile lies outside the valid cells
+
+  if (tid < ROWS) {
+    const int rt = tid >> 4, i = tid & 15;
+    int lab = -1;
+    if (i < tile_n[rt]) {
+      const int b = tile_b[rt], u = tile_u0[rt] + i;
+      if (u < clampi(tgt_len[b], 0, U1 - 1)) lab = clampi(labels[(long)b * U1 + u], 0, V - 1);
+    }
+    row_lab[tid] = lab;
+    cap[tid][0] = LAT_NEG; cap[tid][1] = LAT_NEG;
+  }
+  const int groups = D / 4;
+  for (int i = tid; i < ROWS * groups; i += THREADS) {
+    const int r = i / groups, c = (i - r * groups) * 4;
+    const int rt = r >> 4;
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+    if ((r & 15) < tile_n[rt]) {
+      const int b = tile_b[rt];
+      float pv[4], gv[4];
+      load4(P + ((long)b * S + tile_s[rt]) * D + c, pv);
+      load4(Gt + ((long)b * U1 + tile_u0[rt] + (r & 15)) * D + c, gv);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = join_act<T>(pv[e] + gv[e]);
+    }
+    store4(zs + (long)r * ldz + c, o);
+  }
+  __syncthreads();
+
+  const int n_vt = (V + 15) / 16;
+  const int per = (n_vt + n_split - 1) / n_split;
+  const int vt0 = blockIdx.y * per, vt1 = min(vt0 + per, n_vt);
+  const int nks = D / KS;
+  const int col = lane & 15, lg = lane >> 4;
+
+  float rm[RW][4], rs[RW][4];
+#pragma unroll
+  for (int r = 0; r < RW; ++r)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { rm[r][e] = LAT_NEG; rs[r][e] = 0.f; }
+
+  // two vocabulary tiles per pass; the weight fragments of the next k-step are loaded while this one's MFMAs run
+  for (int vt = vt0 + 2 * wave; vt < vt1; vt += 8) {
+    const bool two = vt + 1 < vt1;
+    f32x4 acc0[RW], acc1[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) { acc0[r] = f32x4{0.f, 0.f, 0.f, 0.f}; acc1[r] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    const T* w0 = Wp + ((long)vt * nks * 64 + lane) * G;
+    const T* w1 = two ? w0 + (long)nks * 64 * G : w0;
+    uint4 wa = ld16(w0), wb = ld16(w1);
+    for (int ks = 0; ks < nks; ++ks) {
+      const uint4 ca = wa, cb = wb;
+      if (ks + 1 < nks) { wa = ld16(w0 + (long)(ks + 1) * 64 * G); wb = ld16(w1 + (long)(ks + 1) * 64 * G); }
+#pragma unroll
+      for (int r = 0; r < RW; ++r) {
+        if (tile_n[rbase + r] == 0) continue;               // uniform over the wave
+        const uint4 a = *reinterpret_cast<const uint4*>(zs + (long)(16 * (rbase + r) + col) * ldz + ks * KS + lg * G);
+        acc0[r] = lat_mma<T>(a, ca, acc0[r]);
+        acc1[r] = lat_mma<T>(a, cb, acc1[r]);
+      }
+    }
+    const bool ok0 = vt * 16 + col < V, ok1 = two && (vt + 1) * 16 + col < V;
+#pragma unroll
+    for (int r = 0; r < RW; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float x0 = ok0 ? acc0[r][e] : -INFINITY, x1 = ok1 ? acc1[r][e] : -INFINITY;
+        const float mx = fmaxf(rm[r][e], fmaxf(x0, x1));
+        rs[r][e] = rs[r][e] * __expf(rm[r][e] - mx) + __expf(x0 - mx) + __expf(x1 - mx);
+        rm[r][e] = mx;
+      }
+  }
+  // fold the 16 columns of a lane group, then the 4 waves of the row group
+#pragma unroll
+  for (int r = 0; r < RW; ++r)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        const float om = __shfl_xor(rm[r][e], o, 64), os = __shfl_xor(rs[r][e], o, 64);
+        lse_join(rm[r][e], rs[r][e], om, os);
+      }
+      const int row = 16 * (rbase + r) + 4 * lg + e;
+      if (col == 0) { red_m[wave][row] = rm[r][e]; red_s[wave][row] = rs[r][e]; }
+    }
+  // the blank and label logits of every row: thread (row, which) takes one dot product over D if this part holds the column
+  for (int i = tid; i < 2 * ROWS; i += THREADS) {
+    const int r = i >> 1, which = i & 1;
+    const int c = which ? row_lab[r] : ((r & 15) < tile_n[r >> 4] ? blank : -1);
+    if (c < 0 || (c >> 4) < vt0 || (c >> 4) >= vt1) continue;
+    const T* wrow = Wp + ((long)(c >> 4) * nks * 64 + (c & 15)) * G;
+    const T* zrow = zs + (long)r * ldz;
+    float acc = 0.f;
+    for (int ks = 0; ks < nks; ++ks)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float wv[G], zv[G];
+        if constexpr (std::is_same<T, float>::value) {
+          load4(wrow + ((long)ks * 64 + q * 16) * G, wv);
+          load4(zrow + ks * KS + q * G, zv);
+        } else {
+          float t4[4];
+          load4(wrow + ((long)ks * 64 + q * 16) * G, t4); wv[0] = t4[0]; wv[1] = t4[1]; wv[2] = t4[2]; wv[3] = t4[3];
+          load4(wrow + ((long)ks * 64 + q * 16) * G + 4, t4); wv[4] = t4[0]; wv[5] = t4[1]; wv[6] = t4[2]; wv[7] = t4[3];
+          load4(zrow + ks * KS + q * G, t4); zv[0] = t4[0]; zv[1] = t4[1]; zv[2] = t4[2]; zv[3] = t4[3];
+          load4(zrow + ks * KS + q * G + 4, t4); zv[4] = t4[0]; zv[5] = t4[1]; zv[6] = t4[2]; zv[7] = t4[3];
+        }
+#pragma unroll
+        for (int e = 0; e < G; ++e) acc = fmaf(zv[e], wv[e], acc);
+      }
+    cap[r][which] = acc;
+  }
+  __syncthreads();
+  if (tid < ROWS) {
+    const int rt = tid >> 4, i = tid & 15;
+    if (i < tile_n[rt]) {
+      float m = red_m[0][tid], s = red_s[0][tid];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) lse_join(m, s, red_m[w][tid], red_s[w][tid]);
+      const long cell = ((long)tile_b[rt] * S + tile_s[rt]) * U1 + tile_u0[rt] + i;
+      *reinterpret_cast<float4*>(part + (cell * n_split + blockIdx.y) * 4) = make_float4(m, s, cap[tid][0], cap[tid][1]);
+    }
+  }
+}
+
+// one thread per cell: the parts' (max, sum) joined, lp = logit - max - log(sum)
+__global__ void joiner_lattice_fold_kernel(const float* __restrict__ part, const int32_t* __restrict__ src_len,
+                                           const int32_t* __restrict__ tgt_len, float* __restrict__ lp_blank,
+                                           float* __restrict__ lp_label, int B, int S, int U1, int n_split) {
+  const long cell = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (cell >= (long)B * S * U1) return;
+  const int u = (int)(cell % U1);
+  const int s = (int)((cell / U1) % S);
+  const int b = (int)(cell / ((long)U1 * S));
+  const int tl = clampi(tgt_len[b], 0, U1 - 1);
+  if (s >= clampi(src_len[b], 0, S) || u > tl) return;
+  float m = LAT_NEG, sum = 0.f, bl = LAT_NEG, lb = LAT_NEG;
+  for (int p = 0; p < n_split; ++p) {
+    const float4 v = *reinterpret_cast<const float4*>(part + (cell * n_split + p) * 4);
+    lse_join(m, sum, v.x, v.y);
+    bl = fmaxf(bl, v.z);
+    lb = fmaxf(lb, v.w);
+  }
+  const float ls = logf(sum);
+  lp_blank[cell] = (bl - m) - ls;
+  if (u < tl) lp_label[cell] = (lb - m) - ls;
+}
+
+// ---------------------------------------------------------------------------------------------------------- RNN-T forward
+// The differences and sums of two neighbouring cells pass through an opaque register (empty asm with a "+v" operand), the guard of
+// ln_apply in dec_chain.hip: the SLP vectoriser cannot fuse them into a packed fp32 instruction with an op_sel source swizzle.
+__device__ __forceinline__ float opaque(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ float log_add(float a, float b) {
+  const float mx = fmaxf(a, b), mn = fminf(a, b);
+  if (mx == -INFINITY) return -INFINITY;
+  const float d = opaque(mn - mx);
+  return mx + __logf(1.0f + __expf(d));          // 1 + e^d in [1, 2]: v_exp / v_log, absolute error below 2^-22
+}
+
+// One workgroup per batch row; anti-diagonal d holds the cells (s, u) with s + u = d, kept in LDS indexed by u.
+// WITH_BEST: the same recursion with max, one back-pointer byte per cell (1: the label move from (s, u - 1), 0: the blank move
+// from (s - 1, u); the label move is taken only when it is STRICTLY better), back-tracked by thread 0.
+template <bool WITH_BEST>
+__global__ __launch_bounds__(256) void rnnt_forward_kernel(const float* __restrict__ lp_blank, const float* __restrict__ lp_label,
+                                                           const int32_t* __restrict__ src_len, const int32_t* __restrict__ tgt_len,
+                                                           float* __restrict__ ll, float* __restrict__ best_ll,
+                                                           int32_t* __restrict__ emit, unsigned char* __restrict__ bp, int S, int U1) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  float* diag = reinterpret_cast<float*>(smem_raw);         // [2][U1] sum recursion, then [2][U1] max recursion
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Sb = clampi(src_len[b], 0, S), n = clampi(tgt_len[b], 0, U1 - 1);
+  if (Sb < 1) {                                             // no source position: no path
+    if (tid == 0) { ll[b] = -INFINITY; if (WITH_BEST) best_ll[b] = -INFINITY; }
+    return;
+  }
+  const float* lb = lp_blank + (long)b * S * U1;
+  const float* lt = lp_label + (long)b * S * U1;
+  unsigned char* bpb = WITH_BEST ? bp + (long)b * S * U1 : nullptr;
+  float* a0 = diag;
+  float* a1 = diag + U1;
+  float* m0 = diag + 2 * U1;
+  float* m1 = diag + 3 * U1;
+  if (tid == 0) { a0[0] = 0.f; if (WITH_BEST) m0[0] = 0.f; }
+  __syncthreads();
+  for (int d = 1; d <= Sb - 1 + n; ++d) {
+    const int ulo = max(0, d - (Sb - 1)), uhi = min(n, d);
+    for (int u = ulo + tid; u <= uhi; u += blockDim.x) {
+      const int s = d - u;
+      const bool from_blank = s >= 1, from_label = u >= 1;            // (s - 1, u) and (s, u - 1) lie on diagonal d - 1
+      const float pb = from_blank ? lb[(long)(s - 1) * U1 + u] : 0.f;
+      const float pl = from_label ? lt[(long)s * U1 + u - 1] : 0.f;
+      const float sb = opaque(a0[u] + pb), sl = opaque(a0[from_label ? u - 1 : u] + pl);
+      a1[u] = log_add(from_blank ? sb : -INFINITY, from_label ? sl : -INFINITY);
+      if (WITH_BEST) {
+        const float tb = opaque(m0[u] + pb), tl = opaque(m0[from_label ? u - 1 : u] + pl);
+        const float vb = from_blank ? tb : -INFINITY, vl = from_label ? tl : -INFINITY;
+        const bool label = vl > vb;
+        m1[u] = label ? vl : vb;
+        bpb[(long)s * U1 + u] = label ? 1 : 0;
+      }
+    }
+    __syncthreads();
+    float* t = a0; a0 = a1; a1 = t;
+    t = m0; m0 = m1; m1 = t;
+  }
+  if (tid == 0) {
+    const float last = lb[(long)(Sb - 1) * U1 + n];
+    ll[b] = a0[n] + last;
+    if (WITH_BEST) {
+      best_ll[b] = m0[n] + last;
+      int s = Sb - 1, u = n;
+      while (s > 0 || u > 0) {                              // S_b - 1 + n moves
+        if (u > 0 && (s == 0 || bpb[(long)s * U1 + u])) { emit[(long)b * U1 + u - 1] = s; --u; } else { --s; }
+      }
+    }
+  }
+}
+
 // the refusals shared by the joiner entry points, made before any pointer is looked at
 int joiner_check(simulst_handle* h, const char* who, int B, int S, int D, int V, int blank, int n_split, int dtype) {
   const std::string w(who);
@@ -269,6 +569,28 @@ int joiner_check(simulst_handle* h, const char* who, int B, int S, int D, int V,
 }
 
 template <typename T> size_t scan_lds_bytes(int D) { return (size_t)16 * ScanCfg<T>::R * (D + gemv::MF<T>::G) * sizeof(T); }
+template <typename T> size_t lattice_lds_bytes(int D) { return (size_t)16 * LatCfg<T>::R * (D + gemv::MF<T>::G) * sizeof(T); }
+constexpr size_t LATTICE_LDS_MAX = 144 * 1024;      // of the compute unit's 160 KiB; the kernel's static arrays take the rest
+constexpr int RNNT_MAX_U1 = 4096;                   // four diagonals of U1 floats in 64 KB of LDS
+
+template <typename T>
+int lattice_launch(simulst_handle* h, const float* P, const float* G, const void* W_fm, const int32_t* labels, const int32_t* src_len,
+                   const int32_t* tgt_len, float* partials, int B, int S, int U1, int D, int V, int blank, int n_split) {
+  const size_t lds = lattice_lds_bytes<T>(D);
+  static bool raised = false;                       // more than 64 KB of dynamic LDS has to be asked for, once per kernel
+  if (!raised) {
+    const hipError_t e = hipFuncSetAttribute((const void*)joiner_lattice_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)LATTICE_LDS_MAX);
+    if (e != hipSuccess) { h->err = std::string("simulst_joiner_lattice: ") + hipGetErrorString(e); return (int)e; }
+    raised = true;
+  }
+  const int u_tiles = (U1 + 15) / 16;
+  const long n_tiles = (long)B * S * u_tiles;
+  const long wgs = (n_tiles + LatCfg<T>::R - 1) / LatCfg<T>::R;
+  hipLaunchKernelGGL(joiner_lattice_kernel<T>, dim3((unsigned)wgs, n_split), dim3(LatCfg<T>::THREADS), lds, h->stream, P, G, (const T*)W_fm,
+                     labels, src_len, tgt_len, partials, B, S, U1, D, V, blank, n_split, u_tiles);
+  return SIMULST_OK;
+}
 
 }  // namespace
 
@@ -351,4 +673,52 @@ extern "C" int simulst_joiner_mask_blank(simulst_handle* h, float* logits, const
   KTimer t(h, SIMULST_K_MISC);
   hipLaunchKernelGGL(joiner_mask_blank_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, logits, at_eos, B, V, blank);
   return sl_launch_status(h, "simulst_joiner_mask_blank");
+}
+
+extern "C" int simulst_joiner_lattice(simulst_handle* h, const float* P, const float* G, const void* W_fm, const int32_t* labels,
+                                      const int32_t* src_len, const int32_t* tgt_len, float* partials, float* lp_blank,
+                                      float* lp_label, int32_t B, int32_t S, int32_t U1, int32_t D, int32_t V, int32_t blank,
+                                      int32_t n_split, int32_t dtype) {
+  if (!h) return SIMULST_E_NULL;
+  const int rc = joiner_check(h, "simulst_joiner_lattice", B, S, D, V, blank, n_split, dtype);
+  if (rc != SIMULST_OK) return rc;
+  SL_REQUIRE(h, U1 >= 1, SIMULST_E_ARG, "simulst_joiner_lattice: U1 >= 1");
+  const size_t lds = dtype == SIMULST_F32 ? lattice_lds_bytes<float>(D) : lattice_lds_bytes<bf16>(D);
+  SL_REQUIRE(h, lds <= LATTICE_LDS_MAX, SIMULST_E_SHAPE, "simulst_joiner_lattice: D too large for the row panel in LDS");
+  SL_REQUIRE(h, (int64_t)B * S * ((U1 + 15) / 16) < ((int64_t)1 << 31), SIMULST_E_SHAPE, "simulst_joiner_lattice: B * S' * U1 tiles");
+  SL_CHECK_NULL(h, P); SL_CHECK_NULL(h, G); SL_CHECK_NULL(h, W_fm); SL_CHECK_NULL(h, labels); SL_CHECK_NULL(h, src_len);
+  SL_CHECK_NULL(h, tgt_len); SL_CHECK_NULL(h, partials); SL_CHECK_NULL(h, lp_blank); SL_CHECK_NULL(h, lp_label);
+  if (B == 0) return SIMULST_OK;
+  KTimer t(h, SIMULST_K_SCAN);
+  const int lrc = dtype == SIMULST_F32
+                      ? lattice_launch<float>(h, P, G, W_fm, labels, src_len, tgt_len, partials, B, S, U1, D, V, blank, n_split)
+                      : lattice_launch<bf16>(h, P, G, W_fm, labels, src_len, tgt_len, partials, B, S, U1, D, V, blank, n_split);
+  if (lrc != SIMULST_OK) return lrc;
+  const long cells = (long)B * S * U1;
+  hipLaunchKernelGGL(joiner_lattice_fold_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, partials, src_len,
+                     tgt_len, lp_blank, lp_label, B, S, U1, n_split);
+  return sl_launch_status(h, "simulst_joiner_lattice");
+}
+
+extern "C" int simulst_rnnt_forward(simulst_handle* h, const float* lp_blank, const float* lp_label, const int32_t* src_len,
+                                    const int32_t* tgt_len, float* ll, float* best_ll, int32_t* emit, uint8_t* backptr, int32_t B,
+                                    int32_t S, int32_t U1) {
+  if (!h) return SIMULST_E_NULL;
+  SL_REQUIRE(h, S >= 1, SIMULST_E_ARG, "simulst_rnnt_forward: S' >= 1");
+  SL_REQUIRE(h, U1 >= 1, SIMULST_E_ARG, "simulst_rnnt_forward: U1 >= 1");
+  SL_REQUIRE(h, B >= 0, SIMULST_E_ARG, "simulst_rnnt_forward: B");
+  SL_REQUIRE(h, U1 <= RNNT_MAX_U1, SIMULST_E_SHAPE, "simulst_rnnt_forward: the diagonal (U1 floats, four of them) does not fit in LDS");
+  SL_CHECK_NULL(h, lp_blank); SL_CHECK_NULL(h, lp_label); SL_CHECK_NULL(h, src_len); SL_CHECK_NULL(h, tgt_len); SL_CHECK_NULL(h, ll);
+  const bool with_best = best_ll != nullptr || emit != nullptr || backptr != nullptr;
+  if (with_best) { SL_CHECK_NULL(h, best_ll); SL_CHECK_NULL(h, emit); SL_CHECK_NULL(h, backptr); }
+  if (B == 0) return SIMULST_OK;
+  KTimer t(h, SIMULST_K_SCAN);
+  const size_t lds = (size_t)4 * U1 * sizeof(float);
+  if (with_best)
+    hipLaunchKernelGGL(rnnt_forward_kernel<true>, dim3(B), dim3(256), lds, h->stream, lp_blank, lp_label, src_len, tgt_len, ll,
+                       best_ll, emit, backptr, S, U1);
+  else
+    hipLaunchKernelGGL(rnnt_forward_kernel<false>, dim3(B), dim3(256), lds, h->stream, lp_blank, lp_label, src_len, tgt_len, ll,
+                       best_ll, emit, backptr, S, U1);
+  return sl_launch_status(h, "simulst_rnnt_forward");
 }

@@ -547,6 +547,53 @@ class Ops:
                      "simulst_joiner_mask_blank")
         return logits
 
+    @staticmethod
+    def lattice_split(B, S, U1, V, dtype):
+        """column ranges of the lattice kernel: as joiner_split, over its taller row panels (128 rows bf16, 64 rows fp32)"""
+        tiles_per_wg = 8 if dtype == torch.bfloat16 else 4
+        row_wgs = max(1, (B * S * ((U1 + 15) // 16) + tiles_per_wg - 1) // tiles_per_wg)
+        return max(1, min(64, (V + 15) // 16 // 8, (512 + row_wgs - 1) // row_wgs))
+
+    def joiner_lattice(self, P, G, W_fm, labels, src_len, tgt_len, *, V, blank=0, n_split=None, lp_blank=None, lp_label=None):
+        """simulst_joiner_lattice: P [B, S, D] fp32, G [B, U1, D] fp32, W_fm from pack_joiner_weight, labels [B, U1] int32,
+        src_len / tgt_len [B] int32 -> (lp_blank, lp_label) fp32 [B, S, U1], written at the valid cells only (new outputs are
+        zero-filled).  The [B, S, U1, V] logits are never made: the only scratch is the parts' [B, S, U1, n_split, 4] floats."""
+        _chk_contig(P, G, W_fm, labels, src_len, tgt_len, lp_blank, lp_label)
+        B, S, D = P.shape
+        U1 = G.shape[1]
+        assert P.dtype == torch.float32 and G.dtype == torch.float32 and G.shape == (B, U1, D)
+        assert labels.dtype == torch.int32 and labels.shape == (B, U1) and src_len.dtype == torch.int32 and tgt_len.dtype == torch.int32
+        if n_split is None:
+            n_split = Ops.lattice_split(B, S, U1, V, W_fm.dtype)
+        if lp_blank is None:
+            lp_blank = torch.zeros(B, S, U1, device=P.device, dtype=torch.float32)
+        if lp_label is None:
+            lp_label = torch.zeros(B, S, U1, device=P.device, dtype=torch.float32)
+        assert lp_blank.shape == (B, S, U1) and lp_label.shape == (B, S, U1) and lp_blank.dtype == lp_label.dtype == torch.float32
+        partials = torch.empty(B, S, U1, int(n_split), 4, device=P.device, dtype=torch.float32)
+        self.h.check(self.lib.simulst_joiner_lattice(self.h.ptr, _p(P), _p(G), _p(W_fm), _p(labels), _p(src_len), _p(tgt_len),
+                                                     _p(partials), _p(lp_blank), _p(lp_label), B, S, U1, D, int(V), int(blank),
+                                                     int(n_split), dt(W_fm)), "simulst_joiner_lattice")
+        return lp_blank, lp_label
+
+    def rnnt_forward(self, lp_blank, lp_label, src_len, tgt_len, *, want_best=False):
+        """simulst_rnnt_forward: lp_blank / lp_label [B, S, U1] fp32 -> ll [B] fp32; with want_best also (best_ll [B] fp32,
+        emit [B, U1] int32: the frame of label u on the best alignment for u < tgt_len[b], -1 behind it)."""
+        _chk_contig(lp_blank, lp_label, src_len, tgt_len)
+        B, S, U1 = lp_blank.shape
+        assert lp_blank.dtype == torch.float32 and lp_label.dtype == torch.float32 and lp_label.shape == lp_blank.shape
+        assert src_len.dtype == torch.int32 and tgt_len.dtype == torch.int32
+        dev = lp_blank.device
+        ll = torch.empty(B, device=dev, dtype=torch.float32)
+        best_ll = emit = backptr = None
+        if want_best:
+            best_ll = torch.empty(B, device=dev, dtype=torch.float32)
+            emit = torch.full((B, U1), -1, device=dev, dtype=torch.int32)
+            backptr = torch.empty(B, S, U1, device=dev, dtype=torch.uint8)
+        self.h.check(self.lib.simulst_rnnt_forward(self.h.ptr, _p(lp_blank), _p(lp_label), _p(src_len), _p(tgt_len), _p(ll),
+                                                   _p(best_ll), _p(emit), _p(backptr), B, S, U1), "simulst_rnnt_forward")
+        return (ll, best_ll, emit) if want_best else ll
+
     # ------------------------------------------------------------------ beam search (csrc/beam.hip)
     def beam_topk(self, logits, max_len, finished, cand_lp, cand_tok, *, beam, step, pad_idx, eos_idx):
         _chk_contig(logits, max_len, finished, cand_lp, cand_tok)

@@ -11,8 +11,15 @@ at the row's last position), and simulst_linear of the emitted position's tanh r
 
 The module registers nothing at import (the local registries hold the three models of the streaming agents); ``register()`` adds
 ``transducer_model`` / ``transducer_model_s``, and registry.build_model_from_args / checkpoint.load call it when that name is asked
-for.  Training (the [B, S, T, V] lattice, :148-156), beam search and the reference's rollback (:214-239, not callable as written)
-are out of scope.
+for.
+
+Scoring a given translation (the forward value of criterion/rnnt_criterion.py:82-147): ``forward_lattice`` runs the prediction
+network over the whole target at once (``features_teacher_forced``), then simulst_joiner_lattice -- log p(blank) and log p(label) of
+every (source position, target position) cell, the reference's [B, S', U + 1, V] logits never written -- and
+``TransducerModel.score_reference`` adds simulst_rnnt_forward: the log-likelihood summed over all monotonic alignments, the best
+alignment with the frame each token is emitted at, and the "offline path" term.  Gradients (the training criterion), FastEmit (it
+acts on gradients only) and label smoothing are out of scope; so are beam search and the reference's rollback (:214-239, not
+callable as written).
 """
 import math
 from typing import Dict, List, Optional
@@ -104,10 +111,11 @@ class TransducerDecoder:
     STATE_KEY = "simulst_amd.transducer_state"
 
     def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], device="cuda", dtype=torch.float32,
-                 ops: Optional[Ops] = None, prefix="decoder"):
+                 ops: Optional[Ops] = None, prefix="decoder", lattice_logits_cap_bytes: int = 1 << 30):
         if cfg.downsample < 1:
             raise ValueError(f"--downsample {cfg.downsample}: a window of at least 1")
         self.cfg = cfg
+        self.lattice_logits_cap_bytes = int(lattice_logits_cap_bytes)      # forward_lattice(return_logits=True) refuses above it
         self.device, self.dtype = torch.device(device), dtype
         self.ops = ops or Ops()
         self.w = TransducerWeights(weights, cfg, self.device, dtype, self.ops, prefix)
@@ -204,6 +212,70 @@ class TransducerDecoder:
             self.commit(st)
         return out.t().contiguous(), emit.t().contiguous(), st
 
+    # ------------------------------------------------------------------ a whole target in one pass
+    def features_teacher_forced(self, tokens: torch.Tensor) -> torch.Tensor:
+        """the prediction network over every position of tokens [B, U1] (a decoder input: bos first, pads last) at once ->
+        [B, U1, D]: the per-op kernels of features(), with simulst_decoder_self_attention_causal in place of the cached step"""
+        ops, cfg, Wd = self.ops, self.cfg, self.w
+        B, U1 = tokens.shape
+        D, H = cfg.embed_dim, cfg.num_heads
+        ensure_positions(Wd, U1 + cfg.padding_idx + 2)
+        toks = tokens.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
+        pos_row = torch.arange(cfg.padding_idx + 1, cfg.padding_idx + 1 + U1, device=self.device, dtype=torch.int32).repeat(B)
+        x = ops.embed_tokens(toks, Wd.E, Wd.pos, pos_row, self.embed_scale)              # [B * U1, D]
+        for L in Wd.layers:
+            y = ops.layernorm(x, L["ln1_g"], L["ln1_b"])
+            qkv = ops.linear(y, L["wqkv"], L["bqkv"])
+            ctx = ops.decoder_self_attention_causal(qkv.view(B, U1, 3 * D), H=H)
+            x = ops.linear(ctx.view(B * U1, D), L["wo"], L["bo"], epilogue=EPI_BIAS_RES, residual=x)
+            y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
+            hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
+            x = ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+        return ops.layernorm(x, Wd.ln_g, Wd.ln_b).view(B, U1, D)
+
+    def lattice_inputs(self, prev_output_tokens: torch.Tensor):
+        """the decoder input of :143-156: column 0 read as bos, a pad column appended, EOS scattered at each row's non-pad count ->
+        (input [B, U1] int64 = [bos, y_1 .. y_{n-1}, eos, pad ..], labels [B, U1] int32 = input shifted left, tgt_len [B] int32 = n)"""
+        cfg = self.cfg
+        prev = prev_output_tokens.to(device=self.device, dtype=torch.int64).clone()
+        B = prev.size(0)
+        prev[:, 0] = BLANK
+        inp = torch.cat([prev, prev.new_full((B, 1), cfg.padding_idx)], 1)
+        tgt_len = inp.ne(cfg.padding_idx).sum(1, keepdim=True)
+        inp.scatter_(1, tgt_len, cfg.eos)
+        labels = torch.cat([inp[:, 1:], inp.new_full((B, 1), cfg.padding_idx)], 1).to(torch.int32).contiguous()
+        return inp.contiguous(), labels, tgt_len.view(B).to(torch.int32).contiguous()
+
+    def forward_lattice(self, prev_output_tokens: torch.Tensor, enc_btd: torch.Tensor, enc_len: torch.Tensor, *,
+                        T: Optional[int] = None, return_logits: bool = False):
+        """TransducerDecoder.forward (:124-163) WITHOUT an incremental state, reduced to what the RNN-T criterion reads:
+        prev_output_tokens [B, U] = the target with its EOS moved to the front (pads behind), enc_btd [B, S_in, D], enc_len [B].
+        Returns {"lp_blank", "lp_label": fp32 [B, S', U + 1] log-probabilities of the blank and of the row's next token in every
+        cell s < src_len'[b], u <= tgt_len[b] (u < tgt_len[b] for the label; zero elsewhere), "src_len", "tgt_len": [B] int32,
+        "padding_mask": the pooled padding mask [B, S'], "P" / "G": the joiner's fp32 source and target projections [B, S', D] /
+        [B, U + 1, D]}.  The [B, S', U + 1, V] logits are not made (simulst_joiner_lattice);
+        return_logits=True adds them as "logits" (fp32, no forced blank) from the tanh rows and simulst_linear -- for parity and
+        baselines only, refused above lattice_logits_cap_bytes."""
+        ops, V = self.ops, self.cfg.vocab
+        B, _, D = enc_btd.shape
+        inp, labels, tgt_len = self.lattice_inputs(prev_output_tokens)
+        U1 = inp.size(1)
+        pooled, src_len = self.downsample(enc_btd.to(device=self.device, dtype=self.dtype), enc_len, T)
+        S = pooled.size(1)
+        if return_logits and B * S * U1 * V * 4 > self.lattice_logits_cap_bytes:
+            raise ValueError(f"forward_lattice(return_logits=True): the [B, S', U + 1, V] logits take {B * S * U1 * V * 4} bytes, "
+                             f"above lattice_logits_cap_bytes = {self.lattice_logits_cap_bytes}")
+        P = ops.linear(pooled.view(B * S, D), self.w.w_src, self.w.b_src, epilogue=EPI_BIAS_F32OUT).view(B, S, D)
+        feats = self.features_teacher_forced(inp)
+        G = ops.linear(feats.view(B * U1, D), self.w.w_tgt, None, epilogue=EPI_BIAS_F32OUT).view(B, U1, D)
+        lp_blank, lp_label = ops.joiner_lattice(P, G, self.w.out_proj_fm, labels, src_len, tgt_len, V=V, blank=BLANK)
+        out = {"lp_blank": lp_blank, "lp_label": lp_label, "src_len": src_len, "tgt_len": tgt_len, "P": P, "G": G,
+               "padding_mask": torch.arange(S, device=self.device).unsqueeze(0) >= src_len.unsqueeze(1)}
+        if return_logits:
+            z = torch.tanh(P.unsqueeze(2) + G.unsqueeze(1)).to(self.dtype).view(B * S * U1, D)
+            out["logits"] = ops.linear(z, self.w.out_proj, None, epilogue=EPI_BIAS_F32OUT).view(B, S, U1, V)
+        return out
+
     # ------------------------------------------------------------------ the reference's call shape
     def forward(self, prev_output_tokens: torch.Tensor, encoder_out: Optional[Dict[str, List[torch.Tensor]]] = None,
                 incremental_state: Optional[dict] = None, **unused):
@@ -213,8 +285,9 @@ class TransducerDecoder:
         is taken from prev_output_tokens: a call that repeats a prefix (a discarded prediction) restarts from the emit position
         that prefix had, no rollback call is needed."""
         if incremental_state is None:
-            raise NotImplementedError("TransducerDecoder.forward without an incremental state is the training lattice [B, S, T, V] "
-                                      "(models/transducer_model.py:148-156), out of scope here")
+            raise NotImplementedError("TransducerDecoder.forward without an incremental state returns the [B, S, T, V] lattice "
+                                      "(models/transducer_model.py:148-156), which is never materialised here: use forward_lattice "
+                                      "(log p(blank) / log p(label) per cell) or TransducerModel.score_reference")
         enc = encoder_out["encoder_out"][0]
         T, B = enc.shape[0], enc.shape[1]
         n_written = prev_output_tokens.size(1) - 1
@@ -285,6 +358,47 @@ class TransducerModel(FairseqModelSurface):
         T = int(enc["encoder_lengths"].max().item())
         toks, emit, st = self.decoder.greedy_offline(enc["encoder_out_btd"], enc["encoder_lengths"], n_steps, mask_eos, T=T)
         return toks, {"emit": emit, "encoder": enc, "state": st}
+
+    def score_reference(self, src_tokens, src_lengths, targets, *, return_alignments=False):
+        """Score given translations under the transducer (the forward value of criterion/rnnt_criterion.py:82-147): the encoder once,
+        ONE pass of the prediction network and the joiner lattice over every target (TransducerDecoder.forward_lattice), then
+        simulst_rnnt_forward.  targets: one EOS-terminated token list per sentence (n tokens, EOS counted).  Returns per sentence
+        {"tokens", "score": ll / n, "nll": -ll with ll the log-likelihood summed over all monotonic alignments, "nll_offline":
+        -sum_u lp_label[S_b - 1][u] (the criterion's offline-path term at label smoothing 0), "alignment", "positional_scores"};
+        return_alignments fills the last two from the best single alignment: the pooled frame each token is emitted at [n] and the
+        tokens' log-probabilities along it [n] (None otherwise)."""
+        cfg = self.cfg
+        targets = [[int(t) for t in tgt] for tgt in targets]
+        B = len(targets)
+        assert B == src_tokens.size(0) and all(len(t) >= 1 and t[-1] == cfg.eos for t in targets), "one EOS-terminated target per sentence"
+        U = max(len(t) for t in targets)
+        assert U + 1 <= cfg.max_target_positions, "target longer than max_target_positions"
+        prev = torch.full((B, U), cfg.padding_idx, dtype=torch.int64)
+        for b, t in enumerate(targets):
+            prev[b, :len(t)] = torch.tensor([cfg.eos] + t[:-1])
+        enc = self.encoder.forward(src_tokens, src_lengths)
+        T = int(enc["encoder_lengths"].max().item())
+        lat = self.decoder.forward_lattice(prev, enc["encoder_out_btd"], enc["encoder_lengths"], T=T)
+        lp_blank, lp_label, src_len, tgt_len = lat["lp_blank"], lat["lp_label"], lat["src_len"], lat["tgt_len"]
+        if return_alignments:
+            ll, _, emit = self.ops.rnnt_forward(lp_blank, lp_label, src_len, tgt_len, want_best=True)
+            pos = lp_label.gather(1, emit.clamp_min(0).long().unsqueeze(1)).squeeze(1).cpu()          # [B, U1]: lp_label[b, emit[u], u]
+            emit = emit.cpu()
+        else:
+            ll = self.ops.rnnt_forward(lp_blank, lp_label, src_len, tgt_len)
+        last = (src_len.long() - 1).clamp_min(0).view(B, 1, 1).expand(B, 1, lp_label.size(2))
+        at_last = lp_label.gather(1, last).squeeze(1).cpu()                                          # [B, U1]: lp_label[b, S_b - 1, u]
+        ll = ll.cpu()
+        out = []
+        for b, t in enumerate(targets):
+            n = len(t)
+            hyp = {"tokens": torch.tensor(t), "score": ll[b] / n, "nll": -ll[b], "nll_offline": -at_last[b, :n].sum(),
+                   "alignment": None, "positional_scores": None}
+            if return_alignments:
+                hyp["alignment"] = emit[b, :n].clone()
+                hyp["positional_scores"] = pos[b, :n].clone()
+            out.append(hyp)
+        return out
 
 
 def transducer_model_s_arch(args):
