@@ -998,6 +998,36 @@ int simulst_joiner_emit(simulst_handle* h, const float* P, const float* g, const
                         const int32_t* best_idx, int32_t* prev_emit, const int32_t* src_len, void* z, int32_t* at_eos, int32_t B,
                         int32_t S, int32_t D, int32_t V, int32_t blank, int32_t n_split, int32_t dtype);
 
+/* The scan and the emission of one BEAM step: R rows of which every `group` consecutive ones (a sentence's beam rows) share one
+ * source.  P [Bs][S][D], src_len [Bs] and finished [Bs] (int32, may be NULL) are read at r / group, Bs = R / group -- P is never
+ * replicated; g [R][D], prev_emit [R], z [R][D], at_eos [R] and blank_logit [R][S], best / best_idx [R][S][n_split] are the row's.
+ * The arithmetic of every (row, position, column) is simulst_joiner_scan's / simulst_joiner_emit's, and with group 1 and finished
+ * NULL the two calls ARE those.  Rows of a finished sentence (finished[r / group] != 0) scan nothing -- their row tiles are empty
+ * and take no matrix-core work -- and the emission leaves their prev_emit, z and at_eos as they are.  emit_log (int32 [R], one
+ * row of the caller's [L][R] table, may be NULL) also receives the new emit position of every row that ran.  SIMULST_E_ARG as
+ * above, and for group < 1 or R % group != 0. */
+int simulst_joiner_scan_beam(simulst_handle* h, const float* P, const float* g, const void* W_fm, const int32_t* prev_emit,
+                             const int32_t* src_len, const int32_t* finished, float* blank_logit, float* best, int32_t* best_idx,
+                             int32_t R, int32_t group, int32_t S, int32_t D, int32_t V, int32_t blank, int32_t n_split,
+                             int32_t dtype);
+int simulst_joiner_emit_beam(simulst_handle* h, const float* P, const float* g, const float* blank_logit, const float* best,
+                             const int32_t* best_idx, int32_t* prev_emit, const int32_t* src_len, const int32_t* finished, void* z,
+                             int32_t* at_eos, int32_t* emit_log, int32_t R, int32_t group, int32_t S, int32_t D, int32_t V,
+                             int32_t blank, int32_t n_split, int32_t dtype);
+
+/* The transducer's state reorder of beam search (the role of reorder_incremental_state, :241-251), one launch: row r of the second
+ * buffer set takes from row reorder[r] of the first the self-attention K/V positions [0, n_prev) of every layer (k_cache / v_cache
+ * [R][H][cap][d], 16-byte copies, as simulst_beam_reorder) and prev_emit (prev_emit_src [R] -> prev_emit_dst [R]).  d gives
+ * R = d->B, H, D, n_layers, cap and dtype; of the simulst_dec_layer entries only k_cache / v_cache are read.  `block` is the number
+ * of rows a reorder may move within (1 <= block <= R, R % block == 0, no cap at 16): a beam driver passes beam, a driver that
+ * reorders over the whole batch passes R.  Rows of finished blocks (finished [R / block], may be NULL) keep their own prev_emit and
+ * copy no K/V.  A reorder that leaves its block is not performed (the row keeps its own state) and is added to result [1] int32
+ * (device scratch, cleared by the caller).  R == 0 returns 0.  SIMULST_E_ARG: dtype, shape (more than 16 layers, head_dim % 8,
+ * cap < 1), block, n_prev outside [0, cap]. */
+int simulst_transducer_beam_reorder(simulst_handle* h, const simulst_decoder_desc* d, const simulst_dec_layer* src,
+                                    const simulst_dec_layer* dst, const int32_t* prev_emit_src, int32_t* prev_emit_dst,
+                                    const int32_t* reorder, const int32_t* finished, int32_t block, int32_t n_prev, int32_t* result);
+
 /* logits fp32 [B][V]: column `blank` of the rows with at_eos[b] != 0 becomes -1e4 (the row gathered at :203-206 keeps the
  * scatter of :176-180). */
 int simulst_joiner_mask_blank(simulst_handle* h, float* logits, const int32_t* at_eos, int32_t B, int32_t V, int32_t blank);

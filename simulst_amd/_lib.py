@@ -177,6 +177,10 @@ SIGNATURES = {
     "simulst_joiner_scan": [_vp] * 9 + [_i32] * 7,
     "simulst_joiner_emit": [_vp] * 10 + [_i32] * 7,
     "simulst_joiner_mask_blank": [_vp, _vp, _vp, _i32, _i32, _i32],
+    "simulst_joiner_scan_beam": [_vp] * 10 + [_i32] * 8,
+    "simulst_joiner_emit_beam": [_vp] * 12 + [_i32] * 8,
+    "simulst_transducer_beam_reorder": [_vp, C.POINTER(DecoderDesc), C.POINTER(DecLayer), C.POINTER(DecLayer), _vp, _vp, _vp, _vp, _i32,
+                                        _i32, _vp],
     "simulst_joiner_lattice": [_vp] * 10 + [_i32] * 8,
     "simulst_rnnt_forward": [_vp] * 9 + [_i32] * 3,
 }

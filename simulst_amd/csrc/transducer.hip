@@ -9,6 +9,11 @@
 //   simulst_joiner_emit       first scanned position whose best non-blank beats the blank, -1e4 blank at src_len' - 1 (:170-200);
 //                             prev_emit <- new_emit, z[b] = tanh(P[b, new_emit] + g[b]), at_eos[b]
 //   simulst_joiner_mask_blank logits[b][blank] <- -1e4 where at_eos[b] (the gathered row of :203-206 keeps the scatter of :176-180)
+//   simulst_joiner_scan_beam / simulst_joiner_emit_beam   the same two kernels over R beam rows of which every `group` consecutive
+//                             ones share one source (P and src_len are read at r / group, never replicated); the rows of a finished
+//                             sentence scan nothing
+//   simulst_transducer_beam_reorder   beam search's state reorder: a row's self-attention K/V prefix and its prev_emit from its
+//                             parent row into the second buffer set (the role reorder_incremental_state has at :241-251)
 //   simulst_joiner_lattice    the joiner over a whole target (:143-163 with no incremental state): log p(blank) and log p(label) of
 //                             every (s, u) cell, an online log-sum-exp over vocabulary tiles -- the [B][S'][U + 1][V] logits that
 //                             criterion/rnnt_criterion.py:90-92 normalises are never written
@@ -82,12 +87,14 @@ __global__ void transducer_pool_kernel(const T* __restrict__ x, const int32_t* _
 
 // ------------------------------------------------------------------------------------------------------------------- scan
 // grid (ceil(B * tiles_per_row / R), n_split).  Row r of the workgroup: tile gt = blockIdx.x * R + r / 16 of the list
-// [b][t] (t < tiles_per_row), position s = 16 t + r % 16.
+// [b][t] (t < tiles_per_row), position s = 16 t + r % 16.  B counts rows; row b reads the source b / group (P, src_len, finished)
+// and its own g, prev_emit and outputs.  The tiles of a finished source are empty.
 template <typename T>
 __global__ __launch_bounds__(SCAN_THREADS) void joiner_scan_kernel(
     const float* __restrict__ P, const float* __restrict__ g, const T* __restrict__ Wp, const int32_t* __restrict__ prev_emit,
-    const int32_t* __restrict__ src_len, float* __restrict__ blank_out, float* __restrict__ best_out, int32_t* __restrict__ idx_out,
-    int B, int S, int D, int V, int blank, int n_split, int tiles_per_row) {
+    const int32_t* __restrict__ src_len, const int32_t* __restrict__ finished, float* __restrict__ blank_out,
+    float* __restrict__ best_out, int32_t* __restrict__ idx_out, int B, int group, int S, int D, int V, int blank, int n_split,
+    int tiles_per_row) {
   constexpr int R = ScanCfg<T>::R, ROWS = 16 * R;
   constexpr int KS = gemv::MF<T>::KS, G = gemv::MF<T>::G;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -96,20 +103,24 @@ __global__ __launch_bounds__(SCAN_THREADS) void joiner_scan_kernel(
   __shared__ float red_v[4][ROWS];
   __shared__ int red_i[4][ROWS];
   __shared__ int tile_lo[R], tile_hi[R], tile_b[R];         // scanned positions [lo, hi) of each row tile (empty: lo >= hi)
+  __shared__ int tile_src[R];                               // the source the tile's row reads P from
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid < R) {
     const int gt = blockIdx.x * R + tid;
-    int lo = 0, hi = 0, b = 0;
+    int lo = 0, hi = 0, b = 0, src = 0;
     if (gt < B * tiles_per_row) {
       b = gt / tiles_per_row;
       const int t = gt - b * tiles_per_row;
-      const int len = clampi(src_len[b], 0, S);
-      const int pe = clampi(prev_emit[b], 0, len > 0 ? len - 1 : 0);
-      lo = max(pe, 16 * t);
-      hi = min(len, 16 * t + 16);
+      src = b / group;
+      if (!(finished && finished[src])) {
+        const int len = clampi(src_len[src], 0, S);
+        const int pe = clampi(prev_emit[b], 0, len > 0 ? len - 1 : 0);
+        lo = max(pe, 16 * t);
+        hi = min(len, 16 * t + 16);
+      }
     }
-    tile_lo[tid] = lo; tile_hi[tid] = hi; tile_b[tid] = b;
+    tile_lo[tid] = lo; tile_hi[tid] = hi; tile_b[tid] = b; tile_src[tid] = src;
   }
   __syncthreads();
   bool any = false;
@@ -128,7 +139,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void joiner_scan_kernel(
     if (s >= tile_lo[rt] && s < tile_hi[rt]) {
       const int b = tile_b[rt];
       float pv[4], gv[4];
-      load4(P + ((long)b * S + s) * D + c, pv);
+      load4(P + ((long)tile_src[rt] * S + s) * D + c, pv);
       load4(g + (long)b * D + c, gv);
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = join_act<T>(pv[e] + gv[e]);
@@ -226,10 +237,13 @@ template <typename T>
 __global__ __launch_bounds__(64) void joiner_emit_kernel(const float* __restrict__ P, const float* __restrict__ g,
                                                          const float* __restrict__ blank_in, const float* __restrict__ best_in,
                                                          const int32_t* __restrict__ idx_in, int32_t* __restrict__ prev_emit,
-                                                         const int32_t* __restrict__ src_len, T* __restrict__ z,
-                                                         int32_t* __restrict__ at_eos, int S, int D, int blank, int n_split) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int len = clampi(src_len[b], 0, S);
+                                                         const int32_t* __restrict__ src_len, const int32_t* __restrict__ finished,
+                                                         T* __restrict__ z, int32_t* __restrict__ at_eos,
+                                                         int32_t* __restrict__ emit_log, int group, int S, int D, int blank,
+                                                         int n_split) {
+  const int b = blockIdx.x, lane = threadIdx.x, src = b / group;     // row b of source b / group
+  if (finished && finished[src]) return;                             // uniform over the workgroup: the row keeps prev_emit, z, at_eos
+  const int len = clampi(src_len[src], 0, S);
   const int last = len > 0 ? len - 1 : 0;
   const int pe = clampi(prev_emit[b], 0, last);
   int first = 0x7fffffff;
@@ -243,8 +257,12 @@ __global__ __launch_bounds__(64) void joiner_emit_kernel(const float* __restrict
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
   const int ne = first <= last ? first : last;
-  if (lane == 0) { prev_emit[b] = ne; at_eos[b] = ne == last ? 1 : 0; }
-  const float* pr = P + ((long)b * S + ne) * D;
+  if (lane == 0) {
+    prev_emit[b] = ne;
+    at_eos[b] = ne == last ? 1 : 0;
+    if (emit_log) emit_log[b] = ne;
+  }
+  const float* pr = P + ((long)src * S + ne) * D;
   for (int c = lane * 4; c < D; c += 256) {
     float pv[4], gv[4], o[4];
     load4(pr + c, pv);
@@ -555,6 +573,44 @@ __global__ __launch_bounds__(256) void rnnt_forward_kernel(const float* __restri
   }
 }
 
+// -------------------------------------------------------------------------------------------------------- beam reorder
+constexpr int TBR_MAX_LAYERS = 16;
+struct TbrLayers {
+  const char* kc[TBR_MAX_LAYERS];
+  const char* vc[TBR_MAX_LAYERS];
+  char* kc_o[TBR_MAX_LAYERS];
+  char* vc_o[TBR_MAX_LAYERS];
+};
+
+// grid (R, n_layers, H), as beam_reorder_kernel (beam.hip): head (r, l, h) of the second set takes positions [0, n_prev) of head
+// (reorder[r], l, h) of the first in 16-byte copies; workgroup (r, 0, 0) also moves prev_emit.  A reorder stays within the `block`
+// rows of r's block; the rows of a finished block keep their own prev_emit and copy no K/V.
+__global__ __launch_bounds__(256) void transducer_beam_reorder_kernel(TbrLayers L, const int32_t* __restrict__ reorder,
+                                                                      const int32_t* __restrict__ finished,
+                                                                      const int32_t* __restrict__ pe_src, int32_t* __restrict__ pe_dst,
+                                                                      int R, int block, int H, long head_bytes, long prefix_bytes,
+                                                                      int32_t* __restrict__ result) {
+  const int r = blockIdx.x, l = blockIdx.y, h = blockIdx.z, s = r / block;
+  const bool first = l == 0 && h == 0 && threadIdx.x == 0;
+  int src = reorder[r];
+  bool kv = true;
+  if (finished && finished[s]) {
+    src = r;
+    kv = false;
+  } else if (src < 0 || src >= R || src / block != s) {
+    if (first) atomicAdd(result, 1);
+    src = r;
+  }
+  if (first) pe_dst[r] = pe_src[src];
+  if (!kv) return;
+  const long so = ((long)src * H + h) * head_bytes, dof = ((long)r * H + h) * head_bytes;
+  const uint4* ks = reinterpret_cast<const uint4*>(L.kc[l] + so);
+  const uint4* vs = reinterpret_cast<const uint4*>(L.vc[l] + so);
+  uint4* kd = reinterpret_cast<uint4*>(L.kc_o[l] + dof);
+  uint4* vd = reinterpret_cast<uint4*>(L.vc_o[l] + dof);
+  for (long i = threadIdx.x; i < (prefix_bytes >> 4); i += 256) { kd[i] = ks[i]; vd[i] = vs[i]; }
+}
+
 // the refusals shared by the joiner entry points, made before any pointer is looked at
 int joiner_check(simulst_handle* h, const char* who, int B, int S, int D, int V, int blank, int n_split, int dtype) {
   const std::string w(who);
@@ -592,6 +648,60 @@ int lattice_launch(simulst_handle* h, const float* P, const float* G, const void
   return SIMULST_OK;
 }
 
+template <typename T>
+void scan_launch(simulst_handle* h, const float* P, const float* g, const void* W_fm, const int32_t* prev_emit, const int32_t* src_len,
+                 const int32_t* finished, float* blank_logit, float* best, int32_t* best_idx, int R, int group, int S, int D, int V,
+                 int blank, int n_split) {
+  const int tiles_per_row = (S + 15) / 16;
+  constexpr int Rr = ScanCfg<T>::R;
+  hipLaunchKernelGGL(joiner_scan_kernel<T>, dim3((R * tiles_per_row + Rr - 1) / Rr, n_split), dim3(SCAN_THREADS), scan_lds_bytes<T>(D),
+                     h->stream, P, g, (const T*)W_fm, prev_emit, src_len, finished, blank_logit, best, best_idx, R, group, S, D, V,
+                     blank, n_split, tiles_per_row);
+}
+
+// simulst_joiner_scan (group 1, no finished list) and simulst_joiner_scan_beam
+int scan_entry(simulst_handle* h, const char* who, const float* P, const float* g, const void* W_fm, const int32_t* prev_emit,
+               const int32_t* src_len, const int32_t* finished, float* blank_logit, float* best, int32_t* best_idx, int R, int group,
+               int S, int D, int V, int blank, int n_split, int dtype) {
+  const std::string w(who);
+  const int rc = joiner_check(h, who, R, S, D, V, blank, n_split, dtype);
+  if (rc != SIMULST_OK) return rc;
+  SL_REQUIRE(h, group >= 1 && R % group == 0, SIMULST_E_ARG, w + ": group >= 1, rows a multiple of group");
+  const size_t lds = dtype == SIMULST_F32 ? scan_lds_bytes<float>(D) : scan_lds_bytes<bf16>(D);
+  SL_REQUIRE(h, lds <= 48 * 1024, SIMULST_E_SHAPE, w + ": D too large for the row tiles in LDS");
+  SL_REQUIRE(h, (int64_t)R * ((S + 15) / 16) < ((int64_t)1 << 31), SIMULST_E_SHAPE, w + ": rows * S' tiles");
+  SL_CHECK_NULL(h, P); SL_CHECK_NULL(h, g); SL_CHECK_NULL(h, W_fm); SL_CHECK_NULL(h, prev_emit); SL_CHECK_NULL(h, src_len);
+  SL_CHECK_NULL(h, blank_logit); SL_CHECK_NULL(h, best); SL_CHECK_NULL(h, best_idx);
+  if (R == 0) return SIMULST_OK;
+  KTimer t(h, SIMULST_K_SCAN);
+  if (dtype == SIMULST_F32)
+    scan_launch<float>(h, P, g, W_fm, prev_emit, src_len, finished, blank_logit, best, best_idx, R, group, S, D, V, blank, n_split);
+  else
+    scan_launch<bf16>(h, P, g, W_fm, prev_emit, src_len, finished, blank_logit, best, best_idx, R, group, S, D, V, blank, n_split);
+  return sl_launch_status(h, who);
+}
+
+// simulst_joiner_emit (group 1, no finished list, no log) and simulst_joiner_emit_beam
+int emit_entry(simulst_handle* h, const char* who, const float* P, const float* g, const float* blank_logit, const float* best,
+               const int32_t* best_idx, int32_t* prev_emit, const int32_t* src_len, const int32_t* finished, void* z, int32_t* at_eos,
+               int32_t* emit_log, int R, int group, int S, int D, int V, int blank, int n_split, int dtype) {
+  const std::string w(who);
+  const int rc = joiner_check(h, who, R, S, D, V, blank, n_split, dtype);
+  if (rc != SIMULST_OK) return rc;
+  SL_REQUIRE(h, group >= 1 && R % group == 0, SIMULST_E_ARG, w + ": group >= 1, rows a multiple of group");
+  SL_CHECK_NULL(h, P); SL_CHECK_NULL(h, g); SL_CHECK_NULL(h, blank_logit); SL_CHECK_NULL(h, best); SL_CHECK_NULL(h, best_idx);
+  SL_CHECK_NULL(h, prev_emit); SL_CHECK_NULL(h, src_len); SL_CHECK_NULL(h, z); SL_CHECK_NULL(h, at_eos);
+  if (R == 0) return SIMULST_OK;
+  KTimer t(h, SIMULST_K_SCAN);
+  if (dtype == SIMULST_F32)
+    hipLaunchKernelGGL(joiner_emit_kernel<float>, dim3(R), dim3(64), 0, h->stream, P, g, blank_logit, best, best_idx, prev_emit,
+                       src_len, finished, (float*)z, at_eos, emit_log, group, S, D, blank, n_split);
+  else
+    hipLaunchKernelGGL(joiner_emit_kernel<bf16>, dim3(R), dim3(64), 0, h->stream, P, g, blank_logit, best, best_idx, prev_emit,
+                       src_len, finished, (bf16*)z, at_eos, emit_log, group, S, D, blank, n_split);
+  return sl_launch_status(h, who);
+}
+
 }  // namespace
 
 extern "C" int simulst_transducer_pool(simulst_handle* h, const void* x, const int32_t* lengths, void* y, int32_t* new_len,
@@ -622,46 +732,66 @@ extern "C" int simulst_joiner_scan(simulst_handle* h, const float* P, const floa
                                    const int32_t* src_len, float* blank_logit, float* best, int32_t* best_idx, int32_t B, int32_t S,
                                    int32_t D, int32_t V, int32_t blank, int32_t n_split, int32_t dtype) {
   if (!h) return SIMULST_E_NULL;
-  const int rc = joiner_check(h, "simulst_joiner_scan", B, S, D, V, blank, n_split, dtype);
-  if (rc != SIMULST_OK) return rc;
-  const size_t lds = dtype == SIMULST_F32 ? scan_lds_bytes<float>(D) : scan_lds_bytes<bf16>(D);
-  SL_REQUIRE(h, lds <= 48 * 1024, SIMULST_E_SHAPE, "simulst_joiner_scan: D too large for the row tiles in LDS");
-  SL_CHECK_NULL(h, P); SL_CHECK_NULL(h, g); SL_CHECK_NULL(h, W_fm); SL_CHECK_NULL(h, prev_emit); SL_CHECK_NULL(h, src_len);
-  SL_CHECK_NULL(h, blank_logit); SL_CHECK_NULL(h, best); SL_CHECK_NULL(h, best_idx);
-  if (B == 0) return SIMULST_OK;
-  const int tiles_per_row = (S + 15) / 16;
-  KTimer t(h, SIMULST_K_SCAN);
-  if (dtype == SIMULST_F32) {
-    const int Rr = ScanCfg<float>::R;
-    hipLaunchKernelGGL(joiner_scan_kernel<float>, dim3((B * tiles_per_row + Rr - 1) / Rr, n_split), dim3(SCAN_THREADS), lds, h->stream,
-                       P, g, (const float*)W_fm, prev_emit, src_len, blank_logit, best, best_idx, B, S, D, V, blank, n_split,
-                       tiles_per_row);
-  } else {
-    const int Rr = ScanCfg<bf16>::R;
-    hipLaunchKernelGGL(joiner_scan_kernel<bf16>, dim3((B * tiles_per_row + Rr - 1) / Rr, n_split), dim3(SCAN_THREADS), lds, h->stream,
-                       P, g, (const bf16*)W_fm, prev_emit, src_len, blank_logit, best, best_idx, B, S, D, V, blank, n_split,
-                       tiles_per_row);
-  }
-  return sl_launch_status(h, "simulst_joiner_scan");
+  return scan_entry(h, "simulst_joiner_scan", P, g, W_fm, prev_emit, src_len, nullptr, blank_logit, best, best_idx, B, 1, S, D, V,
+                    blank, n_split, dtype);
+}
+
+extern "C" int simulst_joiner_scan_beam(simulst_handle* h, const float* P, const float* g, const void* W_fm, const int32_t* prev_emit,
+                                        const int32_t* src_len, const int32_t* finished, float* blank_logit, float* best,
+                                        int32_t* best_idx, int32_t R, int32_t group, int32_t S, int32_t D, int32_t V, int32_t blank,
+                                        int32_t n_split, int32_t dtype) {
+  if (!h) return SIMULST_E_NULL;
+  return scan_entry(h, "simulst_joiner_scan_beam", P, g, W_fm, prev_emit, src_len, finished, blank_logit, best, best_idx, R, group, S,
+                    D, V, blank, n_split, dtype);
 }
 
 extern "C" int simulst_joiner_emit(simulst_handle* h, const float* P, const float* g, const float* blank_logit, const float* best,
                                    const int32_t* best_idx, int32_t* prev_emit, const int32_t* src_len, void* z, int32_t* at_eos,
                                    int32_t B, int32_t S, int32_t D, int32_t V, int32_t blank, int32_t n_split, int32_t dtype) {
   if (!h) return SIMULST_E_NULL;
-  const int rc = joiner_check(h, "simulst_joiner_emit", B, S, D, V, blank, n_split, dtype);
-  if (rc != SIMULST_OK) return rc;
-  SL_CHECK_NULL(h, P); SL_CHECK_NULL(h, g); SL_CHECK_NULL(h, blank_logit); SL_CHECK_NULL(h, best); SL_CHECK_NULL(h, best_idx);
-  SL_CHECK_NULL(h, prev_emit); SL_CHECK_NULL(h, src_len); SL_CHECK_NULL(h, z); SL_CHECK_NULL(h, at_eos);
-  if (B == 0) return SIMULST_OK;
-  KTimer t(h, SIMULST_K_SCAN);
-  if (dtype == SIMULST_F32)
-    hipLaunchKernelGGL(joiner_emit_kernel<float>, dim3(B), dim3(64), 0, h->stream, P, g, blank_logit, best, best_idx, prev_emit,
-                       src_len, (float*)z, at_eos, S, D, blank, n_split);
-  else
-    hipLaunchKernelGGL(joiner_emit_kernel<bf16>, dim3(B), dim3(64), 0, h->stream, P, g, blank_logit, best, best_idx, prev_emit,
-                       src_len, (bf16*)z, at_eos, S, D, blank, n_split);
-  return sl_launch_status(h, "simulst_joiner_emit");
+  return emit_entry(h, "simulst_joiner_emit", P, g, blank_logit, best, best_idx, prev_emit, src_len, nullptr, z, at_eos, nullptr, B, 1,
+                    S, D, V, blank, n_split, dtype);
+}
+
+extern "C" int simulst_joiner_emit_beam(simulst_handle* h, const float* P, const float* g, const float* blank_logit, const float* best,
+                                        const int32_t* best_idx, int32_t* prev_emit, const int32_t* src_len, const int32_t* finished,
+                                        void* z, int32_t* at_eos, int32_t* emit_log, int32_t R, int32_t group, int32_t S, int32_t D,
+                                        int32_t V, int32_t blank, int32_t n_split, int32_t dtype) {
+  if (!h) return SIMULST_E_NULL;
+  return emit_entry(h, "simulst_joiner_emit_beam", P, g, blank_logit, best, best_idx, prev_emit, src_len, finished, z, at_eos, emit_log,
+                    R, group, S, D, V, blank, n_split, dtype);
+}
+
+extern "C" int simulst_transducer_beam_reorder(simulst_handle* h, const simulst_decoder_desc* dd, const simulst_dec_layer* src,
+                                               const simulst_dec_layer* dst, const int32_t* prev_emit_src, int32_t* prev_emit_dst,
+                                               const int32_t* reorder, const int32_t* finished, int32_t block, int32_t n_prev,
+                                               int32_t* result) {
+  if (!h) return SIMULST_E_NULL;
+  SL_CHECK_NULL(h, dd);
+  const int R = dd->B;
+  SL_REQUIRE(h, dd->dtype == SIMULST_F32 || dd->dtype == SIMULST_BF16, SIMULST_E_ARG, "simulst_transducer_beam_reorder: dtype");
+  SL_REQUIRE(h, R >= 0, SIMULST_E_ARG, "simulst_transducer_beam_reorder: rows B");
+  SL_REQUIRE(h, dd->n_layers > 0 && dd->n_layers <= TBR_MAX_LAYERS && dd->H > 0 && dd->D > 0 && dd->D % dd->H == 0 &&
+                (dd->D / dd->H) % 8 == 0 && dd->cap > 0,
+             SIMULST_E_ARG, "simulst_transducer_beam_reorder: shape (at most 16 layers, head_dim a multiple of 8, cap > 0)");
+  SL_REQUIRE(h, block >= 1 && (R == 0 || (block <= R && R % block == 0)), SIMULST_E_ARG,
+             "simulst_transducer_beam_reorder: 1 <= block <= rows, rows a multiple of block");
+  SL_REQUIRE(h, n_prev >= 0 && n_prev <= dd->cap, SIMULST_E_ARG, "simulst_transducer_beam_reorder: 0 <= n_prev <= cap");
+  if (R == 0) return SIMULST_OK;
+  SL_CHECK_NULL(h, src); SL_CHECK_NULL(h, dst); SL_CHECK_NULL(h, prev_emit_src); SL_CHECK_NULL(h, prev_emit_dst);
+  SL_CHECK_NULL(h, reorder); SL_CHECK_NULL(h, result);
+  TbrLayers L = {};
+  for (int l = 0; l < dd->n_layers; ++l) {
+    SL_CHECK_NULL(h, src[l].k_cache); SL_CHECK_NULL(h, src[l].v_cache); SL_CHECK_NULL(h, dst[l].k_cache); SL_CHECK_NULL(h, dst[l].v_cache);
+    L.kc[l] = (const char*)src[l].k_cache; L.vc[l] = (const char*)src[l].v_cache;
+    L.kc_o[l] = (char*)dst[l].k_cache; L.vc_o[l] = (char*)dst[l].v_cache;
+  }
+  const int H = dd->H, d = dd->D / dd->H, esz = dd->dtype == SIMULST_F32 ? 4 : 2;
+  const long pos_bytes = (long)d * esz;                                  // one position of one head: a multiple of 16 bytes
+  KTimer t(h, SIMULST_K_MISC);
+  hipLaunchKernelGGL(transducer_beam_reorder_kernel, dim3(R, dd->n_layers, H), dim3(256), 0, h->stream, L, reorder, finished,
+                     prev_emit_src, prev_emit_dst, R, block, H, (long)dd->cap * pos_bytes, (long)n_prev * pos_bytes, result);
+  return sl_launch_status(h, "simulst_transducer_beam_reorder");
 }
 
 extern "C" int simulst_joiner_mask_blank(simulst_handle* h, float* logits, const int32_t* at_eos, int32_t B, int32_t V,

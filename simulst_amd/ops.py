@@ -539,6 +539,48 @@ class Ops:
                                                   _p(src_len), _p(z), _p(at_eos), B, S, D, int(V), int(blank), best.shape[2], dt(z)),
                      "simulst_joiner_emit")
 
+    def joiner_scan_beam(self, P, g, W_fm, prev_emit, src_len, finished, blank_logit, best, best_idx, *, group, V, blank=0):
+        """simulst_joiner_scan_beam: joiner_scan over R = g.shape[0] rows of which every `group` consecutive ones share a source:
+        P [Bs, S, D], src_len [Bs], finished [Bs] int32 or None; g [R, D], prev_emit [R], blank_logit [R, S], best / best_idx
+        [R, S, n_split]"""
+        _chk_contig(P, g, W_fm, prev_emit, src_len, finished, blank_logit, best, best_idx)
+        Bs, S, D = P.shape
+        R = g.shape[0]
+        assert P.dtype == torch.float32 and g.dtype == torch.float32 and best_idx.dtype == torch.int32
+        assert group >= 1 and R == Bs * group and src_len.numel() == Bs and prev_emit.numel() == R and best.shape[:2] == (R, S)
+        assert finished is None or (finished.dtype == torch.int32 and finished.numel() == Bs)
+        self.h.check(self.lib.simulst_joiner_scan_beam(self.h.ptr, _p(P), _p(g), _p(W_fm), _p(prev_emit), _p(src_len), _p(finished),
+                                                       _p(blank_logit), _p(best), _p(best_idx), R, int(group), S, D, int(V), int(blank),
+                                                       best.shape[2], dt(W_fm)), "simulst_joiner_scan_beam")
+
+    def joiner_emit_beam(self, P, g, blank_logit, best, best_idx, prev_emit, src_len, finished, z, at_eos, emit_log, *, group, V,
+                         blank=0):
+        """simulst_joiner_emit_beam: joiner_emit with joiner_scan_beam's row-to-source map; emit_log [R] int32 or None"""
+        _chk_contig(P, g, blank_logit, best, best_idx, prev_emit, src_len, finished, z, at_eos, emit_log)
+        Bs, S, D = P.shape
+        R = g.shape[0]
+        assert group >= 1 and R == Bs * group and src_len.numel() == Bs and prev_emit.numel() == R and z.shape == (R, D)
+        assert at_eos.numel() == R and best.shape[:2] == (R, S) and prev_emit.dtype == torch.int32
+        assert finished is None or (finished.dtype == torch.int32 and finished.numel() == Bs)
+        assert emit_log is None or (emit_log.dtype == torch.int32 and emit_log.numel() == R)
+        self.h.check(self.lib.simulst_joiner_emit_beam(self.h.ptr, _p(P), _p(g), _p(blank_logit), _p(best), _p(best_idx), _p(prev_emit),
+                                                       _p(src_len), _p(finished), _p(z), _p(at_eos), _p(emit_log), R, int(group), S, D,
+                                                       int(V), int(blank), best.shape[2], dt(z)), "simulst_joiner_emit_beam")
+
+    def transducer_beam_reorder(self, desc, src_layers, dst_layers, prev_emit_src, prev_emit_dst, reorder, finished, result, *, block,
+                                n_prev):
+        """simulst_transducer_beam_reorder: desc a _lib.DecoderDesc with B (rows), D, H, n_layers, cap and dtype set; src_layers /
+        dst_layers: _lib.DecLayer arrays whose k_cache / v_cache point at the two buffer sets; prev_emit_src / prev_emit_dst /
+        reorder [R] int32, finished [R / block] int32 or None, result [1] int32"""
+        _chk_contig(prev_emit_src, prev_emit_dst, reorder, finished, result)
+        R = desc.B
+        assert prev_emit_src.dtype == prev_emit_dst.dtype == reorder.dtype == result.dtype == torch.int32
+        assert prev_emit_src.numel() == prev_emit_dst.numel() == reorder.numel() == R and result.numel() >= 1
+        assert finished is None or (finished.dtype == torch.int32 and finished.numel() * block == R)
+        self.h.check(self.lib.simulst_transducer_beam_reorder(self.h.ptr, C.byref(desc), src_layers, dst_layers, _p(prev_emit_src),
+                                                              _p(prev_emit_dst), _p(reorder), _p(finished), int(block), int(n_prev),
+                                                              _p(result)), "simulst_transducer_beam_reorder")
+
     def joiner_mask_blank(self, logits, at_eos, *, blank=0):
         _chk_contig(logits, at_eos)
         B, V = logits.shape

@@ -9,6 +9,13 @@ per-op kernels, ``g = target_projection(features)``, simulst_joiner_scan (blank 
 the matrix cores, never the [B, S, V] tensor), simulst_joiner_emit (the first position whose non-blank wins, the blank forced out
 at the row's last position), and simulst_linear of the emitted position's tanh row.
 
+Beam search (``beam_offline``, ``TransducerModel.generate``): simulst_amd/beam.py's loop over that step, every one of the
+Bs * beam rows with its own prev_emit and prediction-network K/V prefix.  P stays [Bs, S', D]: simulst_joiner_scan_beam /
+simulst_joiner_emit_beam read it at row / beam and skip finished sentences, and simulst_transducer_beam_reorder moves the K/V
+prefixes and prev_emit behind every selection.  The blank (bos) is an ordinary candidate token wherever it is not forced out, as
+fairseq's SequenceGenerator over the reference's decoder treats it.  ``forward`` + ``reorder_incremental_state`` are that
+decoder's call shape for an outside generator.
+
 The module registers nothing at import (the local registries hold the three models of the streaming agents); ``register()`` adds
 ``transducer_model`` / ``transducer_model_s``, and registry.build_model_from_args / checkpoint.load call it when that name is asked
 for.
@@ -18,8 +25,8 @@ network over the whole target at once (``features_teacher_forced``), then simuls
 every (source position, target position) cell, the reference's [B, S', U + 1, V] logits never written -- and
 ``TransducerModel.score_reference`` adds simulst_rnnt_forward: the log-likelihood summed over all monotonic alignments, the best
 alignment with the frame each token is emitted at, and the "offline path" term.  Gradients (the training criterion), FastEmit (it
-acts on gradients only) and label smoothing are out of scope; so are beam search and the reference's rollback (:214-239, not
-callable as written).
+acts on gradients only) and label smoothing are out of scope; so is the reference's rollback (:214-239, not callable as
+written).
 """
 import math
 from typing import Dict, List, Optional
@@ -84,6 +91,8 @@ class TransducerState:
         self.v_cache = [torch.zeros(B, H, cap, d, device=device, dtype=dtype) for _ in range(cfg.decoder_layers)]
         self.n_prev = torch.zeros(B, device=device, dtype=torch.int32)
         self.n_prev_host = 0
+        self.kv_rows = 0                 # K/V positions written so far, the uncommitted newest one included (forward())
+        self.alt = None                  # second K/V + prev_emit set of the beam reorder
         self.P = None                    # [B, S', D] fp32
         self.pooled = None               # [B, S', D] model dtype
         self.src_len = None              # [B] int32 (src_len')
@@ -103,6 +112,20 @@ class TransducerState:
             return out
         if cap > self.cap:
             self.k_cache, self.v_cache, self.cap = regrow(self.k_cache), regrow(self.v_cache), cap
+            if self.alt is not None:
+                self.alt["k"], self.alt["v"] = regrow(self.alt["k"]), regrow(self.alt["v"])
+
+    def ensure_alt(self):
+        if self.alt is None:
+            self.alt = {"k": [torch.zeros_like(t) for t in self.k_cache], "v": [torch.zeros_like(t) for t in self.v_cache],
+                        "pe": torch.zeros_like(self.prev_emit)}
+        return self.alt
+
+    def swap_alt(self):
+        a = self.alt
+        self.k_cache, a["k"] = a["k"], self.k_cache
+        self.v_cache, a["v"] = a["v"], self.v_cache
+        self.prev_emit, a["pe"] = a["pe"], self.prev_emit
 
 
 class TransducerDecoder:
@@ -140,12 +163,15 @@ class TransducerDecoder:
         T = max(1, min(int(T), enc_btd.size(1)))
         return self.ops.transducer_pool(enc_btd, lens, T_max=T, k=self.cfg.downsample)
 
-    def set_source(self, st: TransducerState, enc_btd: torch.Tensor, enc_len: torch.Tensor, T: Optional[int] = None):
-        """pool the encoder states and project them once per utterance: P = source_projection(pooled) (:64), fp32"""
-        B, _, D = enc_btd.shape
+    def set_source(self, st: TransducerState, enc_btd: torch.Tensor, enc_len: torch.Tensor, T: Optional[int] = None,
+                   rows: Optional[int] = None):
+        """pool the encoder states and project them once per utterance: P = source_projection(pooled) (:64), fp32.  rows: the
+        state's row count when several rows share an utterance (beam search: P stays per utterance, the step's buffers are per row)"""
+        Bs, _, D = enc_btd.shape
         st.pooled, st.src_len = self.downsample(enc_btd.to(self.dtype), enc_len, T)
         S = st.pooled.size(1)
-        st.P = self.ops.linear(st.pooled.view(B * S, D), self.w.w_src, self.w.b_src, epilogue=EPI_BIAS_F32OUT).view(B, S, D)
+        st.P = self.ops.linear(st.pooled.view(Bs * S, D), self.w.w_src, self.w.b_src, epilogue=EPI_BIAS_F32OUT).view(Bs, S, D)
+        B = Bs if rows is None else int(rows)
         n_split = Ops.joiner_split(B, S, self.cfg.vocab, self.dtype)
         st.blank_logit = torch.empty(B, S, device=self.device, dtype=torch.float32)
         st.best = torch.empty(B, S, n_split, device=self.device, dtype=torch.float32)
@@ -211,6 +237,94 @@ class TransducerDecoder:
             emit[s].copy_(st.prev_emit)
             self.commit(st)
         return out.t().contiguous(), emit.t().contiguous(), st
+
+    # ------------------------------------------------------------------ beam search
+    def _reorder_args(self, st: TransducerState):
+        """the descriptor and the two layer arrays (current set, second set) simulst_transducer_beam_reorder reads"""
+        from . import _lib
+        cfg = self.cfg
+        alt = st.ensure_alt()
+        desc = _lib.DecoderDesc()
+        desc.B, desc.D, desc.H, desc.n_layers, desc.cap = st.B, cfg.embed_dim, cfg.num_heads, cfg.decoder_layers, st.cap
+        desc.dtype = _lib.F32 if self.dtype == torch.float32 else _lib.BF16
+
+        def layer_structs(k, v):
+            arr = (_lib.DecLayer * cfg.decoder_layers)()
+            for l in range(cfg.decoder_layers):
+                arr[l].k_cache, arr[l].v_cache = k[l].data_ptr(), v[l].data_ptr()
+            return arr
+
+        return desc, layer_structs(st.k_cache, st.v_cache), layer_structs(alt["k"], alt["v"])
+
+    def beam_offline(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, max_len, *, beam: int, lenpen: float = 1.0, nbest: int = 1,
+                     chunk: int = 8, T: Optional[int] = None):
+        """Beam search with fairseq's SequenceGenerator semantics (simulst_amd/beam.py, DESIGN.md "Beam search") over the
+        reference's incremental transducer step: enc_btd [Bs, S_in, D], enc_len [Bs], max_len an int or one cap per sentence (at
+        most max_len[s] tokens and EOS).  Row s * beam + j carries its own prev_emit and prediction-network K/V prefix; its logits
+        row is the joiner's row at the position it emits at, the blank forced to -1e4 at the sentence's last pooled position and an
+        ordinary candidate everywhere else.  The source is set once for the Bs sentences (P is not replicated); behind every
+        selection the step is committed and simulst_transducer_beam_reorder moves K/V prefixes and prev_emit into the state's
+        second set, and the sets swap.  Returns (tokens [Bs, nbest, L] int64, lengths [Bs, nbest] int32, scores [Bs, nbest] fp32,
+        positional scores [Bs, nbest, L] fp32, emit [Bs, nbest, L] int32 -- the pooled frame each token of the hypothesis (its EOS
+        included) was emitted at, -1 behind it --, stats {"steps"}), on the device; L = max(max_len) + 1."""
+        from .beam import BeamSearch, check_args
+        cfg, ops, V = self.cfg, self.ops, self.cfg.vocab
+        Bs = enc_btd.size(0)
+        caps = [int(max_len)] * Bs if isinstance(max_len, int) else [int(x) for x in max_len]
+        assert len(caps) == Bs, "one cap per sentence"
+        check_args(beam, nbest, V)
+        R = Bs * beam
+        bs = BeamSearch(ops, caps, beam=beam, V=V, eos=cfg.eos, pad=cfg.padding_idx, lenpen=lenpen, nbest=nbest, device=self.device)
+        st = self.new_state(R, cap=bs.L + 2)
+        self.set_source(st, enc_btd.to(self.device), enc_len, T, rows=R)
+        desc, cur, alt = self._reorder_args(st)
+        sets = [cur, alt]
+        cap0 = st.cap
+        emit_log = torch.full((bs.L, R), -1, device=self.device, dtype=torch.int32)
+
+        def logits_fn(t, toks):
+            feats = self.features(st, toks)
+            st.g = ops.linear(feats, self.w.w_tgt, None, epilogue=EPI_BIAS_F32OUT)
+            ops.joiner_scan_beam(st.P, st.g, self.w.out_proj_fm, st.prev_emit, st.src_len, bs.finished, st.blank_logit, st.best,
+                                 st.best_idx, group=beam, V=V, blank=BLANK)
+            ops.joiner_emit_beam(st.P, st.g, st.blank_logit, st.best, st.best_idx, st.prev_emit, st.src_len, bs.finished, st.z,
+                                 st.at_eos, emit_log[t], group=beam, V=V, blank=BLANK)
+            logits = ops.linear(st.z, self.w.out_proj, None, epilogue=EPI_BIAS_F32OUT)
+            return ops.joiner_mask_blank(logits, st.at_eos, blank=BLANK)
+
+        def after_select(t):
+            self.commit(st)
+            assert st.cap == cap0, "beam state outgrew its capacity"
+            ops.transducer_beam_reorder(desc, sets[0], sets[1], st.prev_emit, st.alt["pe"], bs.reorder, bs.finished, bs.result[2:3],
+                                        block=beam, n_prev=st.n_prev_host)
+            st.swap_alt()
+            sets.reverse()
+
+        tokens, lengths, scores, pos = bs.run(logits_fn, after_select, chunk=chunk)
+        emit = self._hypothesis_emit(bs, emit_log).to(self.device)
+        return tokens, lengths, scores, pos, emit, {"steps": bs.steps}
+
+    @staticmethod
+    def _hypothesis_emit(bs, emit_log: torch.Tensor) -> torch.Tensor:
+        """the emit positions of the returned hypotheses [Bs, nbest, L] int32 (CPU): the finalised hypotheses ranked as
+        simulst_beam_backtrack ranks them (descending fin_score, equal scores in finalisation order), each walked back from
+        (fin_step, fin_row) through bp_parent; the row that computed step p of a hypothesis is the PARENT of its step-p entry"""
+        n = bs.steps
+        fin_step, fin_row, fin_score, fin_count = (x.cpu().tolist() for x in (bs.fin_step, bs.fin_row, bs.fin_score, bs.fin_count))
+        parent, log = bs.bp_parent[:n].cpu().tolist(), emit_log[:n].cpu().tolist()
+        out = [[[-1] * bs.L for _ in range(bs.nbest)] for _ in range(bs.Bs)]
+        for s in range(bs.Bs):
+            cnt = min(max(fin_count[s], 0), bs.beam)
+            order = sorted(range(cnt), key=lambda k: (-fin_score[s][k], k))[:bs.nbest]
+            for rank, k in enumerate(order):
+                t, row = min(max(fin_step[s][k], 0), n - 1), min(max(fin_row[s][k], 0), bs.R - 1)
+                e = out[s][rank]
+                e[t] = log[t][row]
+                for p in range(t - 1, -1, -1):
+                    row = min(max(parent[p][row], 0), bs.R - 1)
+                    e[p] = log[p][row]
+        emit = torch.tensor(out, dtype=torch.int32).view(bs.Bs, bs.nbest, bs.L)
+        return emit
 
     # ------------------------------------------------------------------ a whole target in one pass
     def features_teacher_forced(self, tokens: torch.Tensor) -> torch.Tensor:
@@ -311,18 +425,46 @@ class TransducerDecoder:
             st.n_prev_host = n_written
         st.emit_before.append(st.prev_emit.clone())
         logits = self.step(st, prev_output_tokens[:, -1])
+        st.kv_rows = n_written + 1
         S = st.P.size(1)
         padding_mask = torch.arange(S, device=self.device).unsqueeze(0) >= st.src_len.unsqueeze(1)
         return logits.unsqueeze(1), {"padding_mask": padding_mask, "attn": [None], "inner_states": None}
 
     def reorder_incremental_state(self, incremental_state, new_order):
-        raise NotImplementedError("beam search for the transducer is not implemented (prev_emit would have to be carried through "
-                                  "simulst_beam_reorder)")
+        """TransducerDecoder.reorder_incremental_state (:241-251): row r of the caller's state becomes row new_order[r] -- the
+        prediction network's K/V prefix and prev_emit through simulst_transducer_beam_reorder (block = all rows: any new_order over
+        the state's rows), the emit positions forward() keeps for repeated prefixes, and the source rows (the caller reorders its
+        encoder output the same way).  A state that has taken no step has nothing to reorder.  new_order lives on the decoder's
+        device, where fairseq's generator makes it: the reorder kernel reads it on the handle's stream, and as everywhere in this
+        package nothing is copied from the host on the caller's behalf -- a host index is not implemented."""
+        if not torch.is_tensor(new_order) or new_order.device.type != self.device.type:
+            raise NotImplementedError("reorder_incremental_state with new_order on the host is not implemented: pass it on the "
+                                      "decoder's device (the reorder kernel reads it on the handle's stream; no host copies are made)")
+        st = None if incremental_state is None else incremental_state.get(self.STATE_KEY)
+        if st is None:
+            return
+        R = st.B
+        order = new_order.to(device=self.device, dtype=torch.int32).contiguous().view(-1)
+        if order.numel() != R:
+            raise ValueError(f"reorder_incremental_state: new_order holds {order.numel()} rows, the state {R} (the state's row count "
+                             "is fixed; finished rows stay in the batch)")
+        desc, cur, alt = self._reorder_args(st)
+        result = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self.ops.transducer_beam_reorder(desc, cur, alt, st.prev_emit, st.alt["pe"], order, None, result, block=R,
+                                         n_prev=min(st.kv_rows, st.cap))
+        st.swap_alt()
+        idx = order.long()
+        st.emit_before = [e.index_select(0, idx) for e in st.emit_before]
+        if st.P is not None and st.P.size(0) == R:
+            st.P, st.pooled, st.src_len = st.P.index_select(0, idx), st.pooled.index_select(0, idx), st.src_len.index_select(0, idx)
+        if int(result.item()) != 0:
+            raise ValueError("reorder_incremental_state: new_order names a row outside the state")
 
 
 class TransducerModel(FairseqModelSurface):
     """models/transducer_model.py:271-300: S2TEmformerModel's encoder with the TransducerDecoder.  An offline model:
-    generate_offline (greedy); no streaming agent exists for it."""
+    generate_offline (greedy, or beam search with beam / nbest / lenpen) and generate (beam search); no streaming agent exists
+    for it."""
 
     def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], device="cuda", dtype=torch.float32,
                  ops: Optional[Ops] = None):
@@ -348,16 +490,41 @@ class TransducerModel(FairseqModelSurface):
     def max_decoder_positions(self):
         return self.cfg.max_target_positions
 
-    def generate_offline(self, src_tokens, src_lengths, n_steps=None, mask_eos=False):
+    def generate_offline(self, src_tokens, src_lengths, n_steps=None, mask_eos=False, *, beam=1, lenpen=1.0, nbest=1):
         """the encoder once, then greedy transducer steps.  Returns tokens [B, n] and a dict with "emit" [B, n] (the pooled frame
         each token was emitted at), the encoder output and the state.  T = max(encoder_lengths) is read once per batch: the pooled
-        states of a row depend on it (AvgPool1dTBCPad)."""
+        states of a row depend on it (AvgPool1dTBCPad).  With beam > 1 (or nbest / lenpen away from their defaults): beam search,
+        generate()'s hypothesis lists, n_steps (when given) the cap of every sentence."""
+        if beam != 1 or nbest != 1 or lenpen != 1.0:
+            assert not mask_eos, "mask_eos is a greedy-decode option"
+            return self.generate(src_tokens, src_lengths, beam=beam, lenpen=lenpen, nbest=nbest, max_len=n_steps)
         enc = self.encoder.forward(src_tokens, src_lengths)
         if n_steps is None:
             n_steps = int(0.1 * src_tokens.size(1) + 10)
         T = int(enc["encoder_lengths"].max().item())
         toks, emit, st = self.decoder.greedy_offline(enc["encoder_out_btd"], enc["encoder_lengths"], n_steps, mask_eos, T=T)
         return toks, {"emit": emit, "encoder": enc, "state": st}
+
+    def generate(self, src_tokens, src_lengths, *, beam=5, lenpen=1.0, nbest=1, max_len_a=0.1, max_len_b=10, max_len=None):
+        """SimulSTModel.generate's surface (eval/generate.py --beam / --lenpen / --nbest) over the transducer: sentence s decodes at
+        most max_len[s] = min(int(max_len_a T_s + max_len_b), max_target_positions - 1) tokens and EOS, T_s its own frame count
+        (max_len: one cap for every sentence instead).  Returns per sentence a list of at most nbest {"tokens" (EOS included),
+        "score", "positional_scores", "alignment": the pooled frame each token was emitted at (int32, one per token),
+        "attention": None}, best first."""
+        from .beam import hypotheses
+        enc = self.encoder.forward(src_tokens, src_lengths)
+        lens = [int(t) for t in torch.as_tensor(src_lengths).tolist()]
+        top = self.cfg.max_target_positions - 1
+        caps = [min(int(max_len_a * t + max_len_b) if max_len is None else int(max_len), top) for t in lens]
+        T = int(enc["encoder_lengths"].max().item())
+        toks, lengths, scores, pos, emit, _ = self.decoder.beam_offline(enc["encoder_out_btd"], enc["encoder_lengths"], caps, beam=beam,
+                                                                        lenpen=lenpen, nbest=nbest, T=T)
+        hyps = hypotheses(toks, lengths, scores, pos)
+        emit, lengths = emit.cpu(), lengths.cpu()
+        for s, sent in enumerate(hyps):
+            for k, h in enumerate(sent):               # hypotheses() drops only empty trailing slots: index k is slot k
+                h["alignment"] = emit[s, k, :int(lengths[s, k])].clone()
+        return hyps
 
     def score_reference(self, src_tokens, src_lengths, targets, *, return_alignments=False):
         """Score given translations under the transducer (the forward value of criterion/rnnt_criterion.py:82-147): the encoder once,
