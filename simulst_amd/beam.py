@@ -7,10 +7,15 @@ decoder (MMADecoder.beam_offline) or a scripted model in a test.  Per step, on t
 simulst_beam_topk, simulst_beam_select, then the caller's after_select (the decoder commits the step and reorders its incremental
 state, simulst_beam_reorder); once at the end simulst_beam_backtrack.  Every `chunk` steps the count of unfinished sentences is read
 back on the handle's stream, and the loop ends when it is zero.
+
+ReorderBuffers is the double buffer that reorder works on, for the MMA decoder's state and the transducer's alike.
 """
 from typing import Callable, List, Optional, Sequence
 
 import torch
+
+from . import _lib
+from .decoder import regrow
 
 MAX_BEAM = 16
 
@@ -22,6 +27,66 @@ def check_args(beam: int, nbest: int, V: int):
         raise ValueError(f"nbest must be in [1, beam = {beam}], got {nbest}")
     if 2 * beam > V - 1:
         raise ValueError(f"2 beam must be at most V - 1 = {V - 1}, got beam {beam}")
+
+
+def sentence_caps(max_len, Bs: int) -> List[int]:
+    """max_len of a beam_offline call, an int or one cap per sentence, as one cap per sentence"""
+    caps = [int(max_len)] * Bs if isinstance(max_len, int) else [int(x) for x in max_len]
+    assert len(caps) == Bs, "one cap per sentence"
+    return caps
+
+
+class ReorderBuffers:
+    """The double buffer of the beam-state reorder (simulst_beam_reorder, simulst_transducer_beam_reorder) of one decoder state `st`:
+    the second set of its self-attention caches st.k_cache / st.v_cache ([R, H, cap, d] per layer) and of the attributes `extra`
+    names (a tensor per row set, or one per layer: head_step for the MMA decoder, prev_emit for the transducer), the two
+    _lib.DecLayer arrays (src: the set the state holds, dst: the second one, self.other[name]) and the descriptor the entry points
+    read.  It lives on the state (st.reorder_buf), so the addresses last as long as the state does."""
+
+    def __init__(self, st, extra: Sequence[str] = ()):
+        self.st, self.names = st, ("k_cache", "v_cache") + tuple(extra)
+
+        def second(v):
+            return [torch.zeros_like(t) for t in v] if isinstance(v, list) else torch.zeros_like(v)
+        self.other = {n: second(getattr(st, n)) for n in self.names}
+        R, H, cap, d = st.k_cache[0].shape
+        self.desc = desc = _lib.DecoderDesc()
+        desc.B, desc.D, desc.H, desc.n_layers, desc.cap = R, H * d, H, len(st.k_cache), cap
+        desc.dtype = _lib.F32 if st.k_cache[0].dtype == torch.float32 else _lib.BF16
+        self._point()
+
+    @classmethod
+    def of(cls, st, extra: Sequence[str] = ()):
+        """the state's own, made on first use"""
+        if getattr(st, "reorder_buf", None) is None:
+            st.reorder_buf = cls(st, extra)
+        return st.reorder_buf
+
+    def _point(self):
+        def layers(get):
+            arr = (_lib.DecLayer * self.desc.n_layers)()
+            for n in self.names:
+                if isinstance(get(n), list):                    # per layer: the _lib.DecLayer field of that name
+                    for l, t in enumerate(get(n)):
+                        setattr(arr[l], n, t.data_ptr())
+            return arr
+        self.src, self.dst = layers(lambda n: getattr(self.st, n)), layers(self.other.__getitem__)
+
+    def swap(self):
+        """behind a reorder: the set it wrote becomes the state's"""
+        for n in self.names:
+            cur = getattr(self.st, n)
+            setattr(self.st, n, self.other[n])
+            self.other[n] = cur
+        self.src, self.dst = self.dst, self.src
+
+    def grow(self, cap: int):
+        """the caches of both sets to `cap` positions, contents kept"""
+        for n in ("k_cache", "v_cache"):
+            setattr(self.st, n, regrow(getattr(self.st, n), cap))
+            self.other[n] = regrow(self.other[n], cap)
+        self.desc.cap = cap
+        self._point()
 
 
 class BeamSearch:

@@ -404,13 +404,6 @@ class CIFTransformerModel(FairseqModelSurface):
         self.encoder = CIFEncoder(cfg, weights, device, dtype, self.ops)
         self.decoder = CIFDecoder(cfg, weights, device, dtype, self.ops)
 
-    def get_normalized_probs(self, net_output, log_probs=True):
-        lg = net_output[0].float()
-        return torch.log_softmax(lg, -1) if log_probs else torch.softmax(lg, -1)
-
-    def max_decoder_positions(self):
-        return self.cfg.max_target_positions
-
     def generate_offline(self, src_tokens, src_lengths, n_steps=None, mask_eos=False, overshoot_weight=1.0, fused=True):
         """task.inference_step with beam 1 for the CIF model (eval/generate.py:200-209; exp/infer_st.yaml:2-5): encoder +
         integrate-and-fire once, then the position-synchronous greedy loop on the device.  Returns tokens [B, n] and the

@@ -5,7 +5,8 @@
 //   beam_select_kernel    wave per sentence: merge of the beam candidate lists into the sentence's top K, finalisation of EOS
 //                         candidates, the next rows (reorder index, input token, cumulative score) and the step's back-pointers
 //   beam_reorder_kernel   workgroup per (row, layer, head): the parent row's self-attention K/V prefix and monotonic step (and
-//                         head_read) into the second buffer set, in 16-byte copies
+//                         head_read) into the second buffer set, in 16-byte copies; the transducer's reorder
+//                         (simulst_transducer_beam_reorder) is the same kernel with a per-row prev_emit in place of the steps
 // and once at the end
 //   beam_backtrack_kernel wave per sentence: the finalised hypotheses by descending score, walked back through the back-pointers.
 // Order of candidates everywhere: descending score, equal scores to the lower flat index j * V + token.
@@ -16,7 +17,6 @@
 namespace {
 
 constexpr int BM_MAX_BEAM = 16;
-constexpr int BM_MAX_LAYERS = 16;
 constexpr int BM_TOPK_THREADS = 256;
 
 // a before b in candidate order
@@ -206,43 +206,48 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
 }
 
 struct BeamLayers {
-  const char* kc[BM_MAX_LAYERS];
-  const char* vc[BM_MAX_LAYERS];
-  const long* hs[BM_MAX_LAYERS];
-  const unsigned char* hr[BM_MAX_LAYERS];    // may be null
-  char* kc_o[BM_MAX_LAYERS];
-  char* vc_o[BM_MAX_LAYERS];
-  long* hs_o[BM_MAX_LAYERS];
-  unsigned char* hr_o[BM_MAX_LAYERS];
+  const char* kc[SL_REORDER_MAX_LAYERS];
+  const char* vc[SL_REORDER_MAX_LAYERS];
+  const long* hs[SL_REORDER_MAX_LAYERS];            // null: the layer carries no monotonic step (the transducer's prediction network)
+  const unsigned char* hr[SL_REORDER_MAX_LAYERS];   // may be null
+  char* kc_o[SL_REORDER_MAX_LAYERS];
+  char* vc_o[SL_REORDER_MAX_LAYERS];
+  long* hs_o[SL_REORDER_MAX_LAYERS];
+  unsigned char* hr_o[SL_REORDER_MAX_LAYERS];
 };
 
-__device__ __forceinline__ void bm_copy(char* __restrict__ dst, const char* __restrict__ src, long bytes) {
-  uint4* d = reinterpret_cast<uint4*>(dst);
-  const uint4* s = reinterpret_cast<const uint4*>(src);
-  for (long i = threadIdx.x; i < (bytes >> 4); i += 256) d[i] = s[i];
-}
-
+// grid (R, n_layers, H): head (r, l, h) of the second set takes positions [0, n_prev) of head (reorder[r], l, h) of the first in
+// 16-byte copies, then the payload: the head's monotonic step (and head_read) where the layer has one, and, by workgroup (r, 0, 0),
+// the row's int32 of pe_src / pe_dst (the transducer's prev_emit; null: none).  A reorder stays within the `block` rows of r's
+// block; the rows of a finished block keep their own payload and copy no K/V.
 __global__ __launch_bounds__(256) void beam_reorder_kernel(BeamLayers L, const int* __restrict__ reorder, const int* __restrict__ finished,
-                                                           int R, int beam, int H, long head_bytes, long prefix_bytes,
-                                                           int* __restrict__ result) {
-  const int r = blockIdx.x, l = blockIdx.y, h = blockIdx.z, s = r / beam;
+                                                           const int* __restrict__ pe_src, int* __restrict__ pe_dst, int R, int block,
+                                                           int H, long head_bytes, long prefix_bytes, int* __restrict__ result) {
+  const int r = blockIdx.x, l = blockIdx.y, h = blockIdx.z, s = r / block;
+  const bool first = l == 0 && h == 0 && threadIdx.x == 0;
   int src = reorder[r];
   bool kv = true;
   if (finished && finished[s]) {                                     // a finished sentence's rows: their K/V are never read again
     src = r;
     kv = false;
-  } else if (src < 0 || src >= R || src / beam != s) {               // reorders never leave a sentence's block
-    if (threadIdx.x == 0 && l == 0 && h == 0) atomicAdd(result, 1);
+  } else if (src < 0 || src >= R || src / block != s) {              // reorders never leave a row's block
+    if (first) atomicAdd(result, 1);
     src = r;
   }
-  const long so = ((long)src * H + h) * head_bytes, dof = ((long)r * H + h) * head_bytes;
   if (kv) {
-    bm_copy(L.kc_o[l] + dof, L.kc[l] + so, prefix_bytes);
-    bm_copy(L.vc_o[l] + dof, L.vc[l] + so, prefix_bytes);
+    const long so = ((long)src * H + h) * head_bytes, dof = ((long)r * H + h) * head_bytes;
+    const uint4* ks = reinterpret_cast<const uint4*>(L.kc[l] + so);
+    const uint4* vs = reinterpret_cast<const uint4*>(L.vc[l] + so);
+    uint4* kd = reinterpret_cast<uint4*>(L.kc_o[l] + dof);
+    uint4* vd = reinterpret_cast<uint4*>(L.vc_o[l] + dof);
+    for (long i = threadIdx.x; i < (prefix_bytes >> 4); i += 256) { kd[i] = ks[i]; vd[i] = vs[i]; }
   }
   if (threadIdx.x == 0) {
-    L.hs_o[l][r * H + h] = L.hs[l][src * H + h];
-    if (L.hr[l]) L.hr_o[l][r * H + h] = L.hr[l][src * H + h];
+    if (L.hs[l]) {
+      L.hs_o[l][r * H + h] = L.hs[l][src * H + h];
+      if (L.hr[l]) L.hr_o[l][r * H + h] = L.hr[l][src * H + h];
+    }
+    if (first && pe_dst) pe_dst[r] = pe_src[src];
   }
 }
 
@@ -343,6 +348,27 @@ extern "C" int simulst_beam_select(simulst_handle* h, const float* cand_lp, cons
   return sl_launch_status(h, "simulst_beam_select");
 }
 
+// The launch behind simulst_beam_reorder and simulst_transducer_beam_reorder, whose refusals have passed: every layer's K/V pointers
+// are set, head_step in all layers of both sets or (head_step false) read in none, pe_src / pe_dst both set or both null.
+int sl_beam_reorder(simulst_handle* h, const char* who, const simulst_dec_layer* src, const simulst_dec_layer* dst, bool head_step,
+                    const int32_t* pe_src, int32_t* pe_dst, const int32_t* reorder, const int32_t* finished, int32_t* result, int R,
+                    int block, int n_layers, int H, int head_dim, int dtype, int cap, int n_prev) {
+  BeamLayers L = {};
+  for (int l = 0; l < n_layers; ++l) {
+    L.kc[l] = (const char*)src[l].k_cache; L.vc[l] = (const char*)src[l].v_cache;
+    L.kc_o[l] = (char*)dst[l].k_cache; L.vc_o[l] = (char*)dst[l].v_cache;
+    if (head_step) {
+      L.hs[l] = (const long*)src[l].head_step; L.hr[l] = src[l].head_read;
+      L.hs_o[l] = (long*)dst[l].head_step; L.hr_o[l] = dst[l].head_read;
+    }
+  }
+  const long pos_bytes = (long)head_dim * (dtype == SIMULST_F32 ? 4 : 2);     // one position of one head: a multiple of 16 bytes
+  KTimer t(h, SIMULST_K_MISC);
+  hipLaunchKernelGGL(beam_reorder_kernel, dim3(R, n_layers, H), dim3(256), 0, h->stream, L, (const int*)reorder, (const int*)finished,
+                     (const int*)pe_src, (int*)pe_dst, R, block, H, (long)cap * pos_bytes, (long)n_prev * pos_bytes, (int*)result);
+  return sl_launch_status(h, who);
+}
+
 extern "C" int simulst_beam_reorder(simulst_handle* h, const simulst_decoder_desc* dd, const simulst_dec_layer* src,
                                     const simulst_dec_layer* dst, const int32_t* reorder, const int32_t* finished, int32_t beam,
                                     int32_t n_prev, int32_t* result) {
@@ -351,26 +377,17 @@ extern "C" int simulst_beam_reorder(simulst_handle* h, const simulst_decoder_des
   SL_REQUIRE(h, beam >= 1 && beam <= BM_MAX_BEAM, SIMULST_E_SHAPE, "simulst_beam_reorder: beam must be in [1, 16]");
   SL_REQUIRE(h, dd->B > 0 && dd->B % beam == 0, SIMULST_E_SHAPE, "simulst_beam_reorder: rows B a positive multiple of beam");
   SL_REQUIRE(h, dd->dtype == SIMULST_F32 || dd->dtype == SIMULST_BF16, SIMULST_E_DTYPE, "simulst_beam_reorder: dtype");
-  SL_REQUIRE(h, dd->n_layers > 0 && dd->n_layers <= BM_MAX_LAYERS && dd->H > 0 && dd->D % dd->H == 0 && (dd->D / dd->H) % 8 == 0 &&
-                dd->cap > 0,
+  SL_REQUIRE(h, dd->n_layers > 0 && dd->n_layers <= SL_REORDER_MAX_LAYERS && dd->H > 0 && dd->D % dd->H == 0 &&
+                (dd->D / dd->H) % 8 == 0 && dd->cap > 0,
              SIMULST_E_SHAPE, "simulst_beam_reorder: shape (at most 16 layers, head_dim a multiple of 8)");
   SL_REQUIRE(h, n_prev >= 0 && n_prev <= dd->cap, SIMULST_E_SHAPE, "simulst_beam_reorder: 0 <= n_prev <= cap");
-  BeamLayers L = {};
   for (int l = 0; l < dd->n_layers; ++l) {
     SL_CHECK_NULL(h, src[l].k_cache); SL_CHECK_NULL(h, src[l].v_cache); SL_CHECK_NULL(h, src[l].head_step);
     SL_CHECK_NULL(h, dst[l].k_cache); SL_CHECK_NULL(h, dst[l].v_cache); SL_CHECK_NULL(h, dst[l].head_step);
     SL_REQUIRE(h, !src[l].head_read == !dst[l].head_read, SIMULST_E_SHAPE, "simulst_beam_reorder: head_read in both sets or in neither");
-    L.kc[l] = (const char*)src[l].k_cache; L.vc[l] = (const char*)src[l].v_cache; L.hs[l] = (const long*)src[l].head_step;
-    L.hr[l] = src[l].head_read;
-    L.kc_o[l] = (char*)dst[l].k_cache; L.vc_o[l] = (char*)dst[l].v_cache; L.hs_o[l] = (long*)dst[l].head_step;
-    L.hr_o[l] = dst[l].head_read;
   }
-  const int H = dd->H, d = dd->D / dd->H, esz = dd->dtype == SIMULST_F32 ? 4 : 2;
-  const long pos_bytes = (long)d * esz;                                  // one position of one head: a multiple of 16 bytes
-  KTimer t(h, SIMULST_K_MISC);
-  hipLaunchKernelGGL(beam_reorder_kernel, dim3(dd->B, dd->n_layers, H), dim3(256), 0, h->stream, L, (const int*)reorder,
-                     (const int*)finished, dd->B, beam, H, (long)dd->cap * pos_bytes, (long)n_prev * pos_bytes, (int*)result);
-  return sl_launch_status(h, "simulst_beam_reorder");
+  return sl_beam_reorder(h, "simulst_beam_reorder", src, dst, true, nullptr, nullptr, reorder, finished, result, dd->B, beam,
+                         dd->n_layers, dd->H, dd->D / dd->H, dd->dtype, dd->cap, n_prev);
 }
 
 extern "C" int simulst_beam_backtrack(simulst_handle* h, int32_t Bs, int32_t beam, int32_t nbest, int32_t L, const int32_t* bp_parent,

@@ -344,6 +344,13 @@ int sl_self_attention_fused(simulst_handle* h, const void* x, const float* ln_g,
                             int np_uniform, float* partial, int32_t B, int32_t H, int32_t d, int32_t cap,
                             int32_t dtype);
 
+// beam-state reorder (beam.hip): the launch shared by simulst_beam_reorder (head_step: the layers' head_step / head_read move per
+// head) and simulst_transducer_beam_reorder (pe_src / pe_dst: one int32 per row moves); each front end makes its own refusals
+constexpr int SL_REORDER_MAX_LAYERS = 16;
+int sl_beam_reorder(simulst_handle* h, const char* who, const simulst_dec_layer* src, const simulst_dec_layer* dst, bool head_step,
+                    const int32_t* pe_src, int32_t* pe_dst, const int32_t* reorder, const int32_t* finished, int32_t* result, int R,
+                    int block, int n_layers, int H, int head_dim, int dtype, int cap, int n_prev);
+
 int sl_emformer_attention_mfma(simulst_handle* h, const simulst_emf_attn_desc* d, const void* QKV,
                                const int32_t* lengths, const void* lc_k, const void* lc_v, const int32_t* lc_valid,
                                const int32_t* n_mem_valid, void* CTX);

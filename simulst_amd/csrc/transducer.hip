@@ -13,7 +13,8 @@
 //                             ones share one source (P and src_len are read at r / group, never replicated); the rows of a finished
 //                             sentence scan nothing
 //   simulst_transducer_beam_reorder   beam search's state reorder: a row's self-attention K/V prefix and its prev_emit from its
-//                             parent row into the second buffer set (the role reorder_incremental_state has at :241-251)
+//                             parent row into the second buffer set (the role reorder_incremental_state has at :241-251), on
+//                             beam.hip's beam_reorder_kernel
 //   simulst_joiner_lattice    the joiner over a whole target (:143-163 with no incremental state): log p(blank) and log p(label) of
 //                             every (s, u) cell, an online log-sum-exp over vocabulary tiles -- the [B][S'][U + 1][V] logits that
 //                             criterion/rnnt_criterion.py:90-92 normalises are never written
@@ -573,44 +574,6 @@ __global__ __launch_bounds__(256) void rnnt_forward_kernel(const float* __restri
   }
 }
 
-// -------------------------------------------------------------------------------------------------------- beam reorder
-constexpr int TBR_MAX_LAYERS = 16;
-struct TbrLayers {
-  const char* kc[TBR_MAX_LAYERS];
-  const char* vc[TBR_MAX_LAYERS];
-  char* kc_o[TBR_MAX_LAYERS];
-  char* vc_o[TBR_MAX_LAYERS];
-};
-
-// grid (R, n_layers, H), as beam_reorder_kernel (beam.hip): head (r, l, h) of the second set takes positions [0, n_prev) of head
-// (reorder[r], l, h) of the first in 16-byte copies; workgroup (r, 0, 0) also moves prev_emit.  A reorder stays within the `block`
-// rows of r's block; the rows of a finished block keep their own prev_emit and copy no K/V.
-__global__ __launch_bounds__(256) void transducer_beam_reorder_kernel(TbrLayers L, const int32_t* __restrict__ reorder,
-                                                                      const int32_t* __restrict__ finished,
-                                                                      const int32_t* __restrict__ pe_src, int32_t* __restrict__ pe_dst,
-                                                                      int R, int block, int H, long head_bytes, long prefix_bytes,
-                                                                      int32_t* __restrict__ result) {
-  const int r = blockIdx.x, l = blockIdx.y, h = blockIdx.z, s = r / block;
-  const bool first = l == 0 && h == 0 && threadIdx.x == 0;
-  int src = reorder[r];
-  bool kv = true;
-  if (finished && finished[s]) {
-    src = r;
-    kv = false;
-  } else if (src < 0 || src >= R || src / block != s) {
-    if (first) atomicAdd(result, 1);
-    src = r;
-  }
-  if (first) pe_dst[r] = pe_src[src];
-  if (!kv) return;
-  const long so = ((long)src * H + h) * head_bytes, dof = ((long)r * H + h) * head_bytes;
-  const uint4* ks = reinterpret_cast<const uint4*>(L.kc[l] + so);
-  const uint4* vs = reinterpret_cast<const uint4*>(L.vc[l] + so);
-  uint4* kd = reinterpret_cast<uint4*>(L.kc_o[l] + dof);
-  uint4* vd = reinterpret_cast<uint4*>(L.vc_o[l] + dof);
-  for (long i = threadIdx.x; i < (prefix_bytes >> 4); i += 256) { kd[i] = ks[i]; vd[i] = vs[i]; }
-}
-
 // the refusals shared by the joiner entry points, made before any pointer is looked at
 int joiner_check(simulst_handle* h, const char* who, int B, int S, int D, int V, int blank, int n_split, int dtype) {
   const std::string w(who);
@@ -771,7 +734,7 @@ extern "C" int simulst_transducer_beam_reorder(simulst_handle* h, const simulst_
   const int R = dd->B;
   SL_REQUIRE(h, dd->dtype == SIMULST_F32 || dd->dtype == SIMULST_BF16, SIMULST_E_ARG, "simulst_transducer_beam_reorder: dtype");
   SL_REQUIRE(h, R >= 0, SIMULST_E_ARG, "simulst_transducer_beam_reorder: rows B");
-  SL_REQUIRE(h, dd->n_layers > 0 && dd->n_layers <= TBR_MAX_LAYERS && dd->H > 0 && dd->D > 0 && dd->D % dd->H == 0 &&
+  SL_REQUIRE(h, dd->n_layers > 0 && dd->n_layers <= SL_REORDER_MAX_LAYERS && dd->H > 0 && dd->D > 0 && dd->D % dd->H == 0 &&
                 (dd->D / dd->H) % 8 == 0 && dd->cap > 0,
              SIMULST_E_ARG, "simulst_transducer_beam_reorder: shape (at most 16 layers, head_dim a multiple of 8, cap > 0)");
   SL_REQUIRE(h, block >= 1 && (R == 0 || (block <= R && R % block == 0)), SIMULST_E_ARG,
@@ -780,18 +743,11 @@ extern "C" int simulst_transducer_beam_reorder(simulst_handle* h, const simulst_
   if (R == 0) return SIMULST_OK;
   SL_CHECK_NULL(h, src); SL_CHECK_NULL(h, dst); SL_CHECK_NULL(h, prev_emit_src); SL_CHECK_NULL(h, prev_emit_dst);
   SL_CHECK_NULL(h, reorder); SL_CHECK_NULL(h, result);
-  TbrLayers L = {};
   for (int l = 0; l < dd->n_layers; ++l) {
     SL_CHECK_NULL(h, src[l].k_cache); SL_CHECK_NULL(h, src[l].v_cache); SL_CHECK_NULL(h, dst[l].k_cache); SL_CHECK_NULL(h, dst[l].v_cache);
-    L.kc[l] = (const char*)src[l].k_cache; L.vc[l] = (const char*)src[l].v_cache;
-    L.kc_o[l] = (char*)dst[l].k_cache; L.vc_o[l] = (char*)dst[l].v_cache;
   }
-  const int H = dd->H, d = dd->D / dd->H, esz = dd->dtype == SIMULST_F32 ? 4 : 2;
-  const long pos_bytes = (long)d * esz;                                  // one position of one head: a multiple of 16 bytes
-  KTimer t(h, SIMULST_K_MISC);
-  hipLaunchKernelGGL(transducer_beam_reorder_kernel, dim3(R, dd->n_layers, H), dim3(256), 0, h->stream, L, reorder, finished,
-                     prev_emit_src, prev_emit_dst, R, block, H, (long)dd->cap * pos_bytes, (long)n_prev * pos_bytes, result);
-  return sl_launch_status(h, "simulst_transducer_beam_reorder");
+  return sl_beam_reorder(h, "simulst_transducer_beam_reorder", src, dst, false, prev_emit_src, prev_emit_dst, reorder, finished, result,
+                         R, block, dd->n_layers, dd->H, dd->D / dd->H, dd->dtype, dd->cap, n_prev);
 }
 
 extern "C" int simulst_joiner_mask_blank(simulst_handle* h, float* logits, const int32_t* at_eos, int32_t B, int32_t V,

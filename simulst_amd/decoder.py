@@ -34,37 +34,47 @@ def sinusoidal_table(n: int, dim: int, padding_idx: int) -> torch.Tensor:
     return tab
 
 
+def load_decoder_stack(dst, w: Dict[str, torch.Tensor], cfg: ModelConfig, device, dtype, prefix="decoder"):
+    """What every fairseq TransformerDecoder stack holds, onto `dst`: embedding, output projection, position table, final LN and per
+    layer (dst.layers[l]) the fused QKV, out-proj, self-attention LN (ln1), feed-forward LN (ln3), fc1 and fc2.  Returns the
+    converters (W: a matrix in the model dtype, Bv: a vector in fp32) with which the caller adds what is its own."""
+    f32 = dict(device=device, dtype=torch.float32)
+    act = dict(device=device, dtype=dtype)
+    p = prefix
+
+    def W(name):
+        return w[name].contiguous().to(**act)
+
+    def Bv(name):
+        return w[name].float().contiguous().to(**f32)
+
+    dst.E = W(f"{p}.embed_tokens.weight")
+    dst.out_proj = W(f"{p}.output_projection.weight")
+    dst.pos = sinusoidal_table(cfg.max_target_positions + cfg.padding_idx + 2, cfg.embed_dim, cfg.padding_idx).to(**f32)
+    dst._pos_args = (cfg.embed_dim, cfg.padding_idx, f32)
+    dst.ln_g, dst.ln_b = Bv(f"{p}.layer_norm.weight"), Bv(f"{p}.layer_norm.bias")
+    dst.layers = []
+    for l in range(cfg.decoder_layers):
+        lp = f"{p}.layers.{l}"
+        L = {}
+        L["wqkv"] = torch.cat([w[f"{lp}.self_attn.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0).contiguous().to(**act)
+        L["bqkv"] = torch.cat([w[f"{lp}.self_attn.{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0).float().to(**f32)
+        L["wo"], L["bo"] = W(f"{lp}.self_attn.out_proj.weight"), Bv(f"{lp}.self_attn.out_proj.bias")
+        for n, key in (("self_attn_layer_norm", "ln1"), ("final_layer_norm", "ln3")):
+            L[key + "_g"], L[key + "_b"] = Bv(f"{lp}.{n}.weight"), Bv(f"{lp}.{n}.bias")
+        L["fc1"], L["b1"] = W(f"{lp}.fc1.weight"), Bv(f"{lp}.fc1.bias")
+        L["fc2"], L["b2"] = W(f"{lp}.fc2.weight"), Bv(f"{lp}.fc2.bias")
+        dst.layers.append(L)
+    return W, Bv
+
+
 class DecoderWeights:
     def __init__(self, w: Dict[str, torch.Tensor], cfg: ModelConfig, device, dtype, prefix="decoder"):
-        f32 = dict(device=device, dtype=torch.float32)
-        act = dict(device=device, dtype=dtype)
-        p = prefix
-
-        def W(name):
-            return w[name].contiguous().to(**act)
-
-        def Bv(name):
-            return w[name].float().contiguous().to(**f32)
-
-        self.E = W(f"{p}.embed_tokens.weight")
-        self.out_proj = W(f"{p}.output_projection.weight")
-        self.pos = sinusoidal_table(cfg.max_target_positions + cfg.padding_idx + 2, cfg.embed_dim,
-                                    cfg.padding_idx).to(**f32)
-        self._pos_args = (cfg.embed_dim, cfg.padding_idx, f32)
-        self.ln_g, self.ln_b = Bv(f"{p}.layer_norm.weight"), Bv(f"{p}.layer_norm.bias")
-        self.layers = []
+        W, Bv = load_decoder_stack(self, w, cfg, device, dtype, prefix)
         cif = cfg.model == "cif_transformer"
-        for l in range(cfg.decoder_layers):
-            lp = f"{p}.layers.{l}"
-            L = {}
-            L["wqkv"] = torch.cat([w[f"{lp}.self_attn.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")],
-                                  0).contiguous().to(**act)
-            L["bqkv"] = torch.cat([w[f"{lp}.self_attn.{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")],
-                                  0).float().to(**f32)
-            L["wo"], L["bo"] = W(f"{lp}.self_attn.out_proj.weight"), Bv(f"{lp}.self_attn.out_proj.bias")
-            for n, key in (("self_attn_layer_norm", "ln1"), ("encoder_attn_layer_norm", "ln2"),
-                           ("final_layer_norm", "ln3")):
-                L[key + "_g"], L[key + "_b"] = Bv(f"{lp}.{n}.weight"), Bv(f"{lp}.{n}.bias")
+        for l, L in enumerate(self.layers):
+            lp = f"{prefix}.layers.{l}"
+            L["ln2_g"], L["ln2_b"] = Bv(f"{lp}.encoder_attn_layer_norm.weight"), Bv(f"{lp}.encoder_attn_layer_norm.bias")
             ea = f"{lp}.encoder_attn"
             if cif:
                 L["c_wq"] = W(f"{ea}.q_proj.weight")
@@ -79,9 +89,6 @@ class DecoderWeights:
                     L["c_wq_soft"], L["c_bq_soft"] = W(f"{ea}.q_proj_soft.weight"), Bv(f"{ea}.q_proj_soft.bias")
                     L["c_wk_soft"], L["c_bk_soft"] = W(f"{ea}.k_proj_soft.weight"), Bv(f"{ea}.k_proj_soft.bias")
                 L["energy_bias"] = float(w[f"{ea}.energy_bias"][0]) if cfg.energy_bias and cfg.attn_type != "full" else 0.0
-            L["fc1"], L["b1"] = W(f"{lp}.fc1.weight"), Bv(f"{lp}.fc1.bias")
-            L["fc2"], L["b2"] = W(f"{lp}.fc2.weight"), Bv(f"{lp}.fc2.bias")
-            self.layers.append(L)
 
 
 def ensure_positions(w: "DecoderWeights", n_rows: int):
@@ -93,6 +100,44 @@ def ensure_positions(w: "DecoderWeights", n_rows: int):
         w.__dict__.setdefault("_pos_retired", []).append(w.pos)     # launches of other streams may still read the old one
         w.pos = sinusoidal_table(max(n_rows, 2 * w.pos.size(0)), D, pad).to(**f32)
     return w.pos
+
+
+def self_attention_block(ops: Ops, L: dict, x: torch.Tensor, attend, l: int) -> torch.Tensor:
+    """The self-attention block of fairseq's pre-norm decoder layer l over the rows x [rows, D]: LN, QKV, ctx = attend(qkv, l)
+    [rows, D] (the cached step, or causal attention over a whole target), out-proj + residual."""
+    y = ops.layernorm(x, L["ln1_g"], L["ln1_b"])
+    qkv = ops.linear(y, L["wqkv"], L["bqkv"])
+    ctx = attend(qkv, l)
+    return ops.linear(ctx, L["wo"], L["bo"], epilogue=EPI_BIAS_RES, residual=x)
+
+
+def feed_forward_block(ops: Ops, L: dict, x: torch.Tensor) -> torch.Tensor:
+    """The feed-forward block of the same layer: LN, fc1 + GELU, fc2 + residual."""
+    y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
+    hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
+    return ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+
+
+def regrow(lst: List[torch.Tensor], dim_new: int) -> List[torch.Tensor]:
+    """the [B, H, n, d] caches of a list re-allocated with dim_new >= n positions, contents kept"""
+    out = []
+    for t in lst:
+        n = torch.zeros(t.shape[0], t.shape[1], dim_new, t.shape[3], device=t.device, dtype=t.dtype)
+        n[:, :, :t.shape[2]] = t
+        out.append(n)
+    return out
+
+
+def source_padding(encoder_out) -> Optional[torch.Tensor]:
+    """the encoder's padding mask [B, T], None when it carries none (the agents pass an empty list)"""
+    pad = encoder_out.get("encoder_padding_mask") or []
+    return pad[0] if len(pad) > 0 and pad[0] is not None and pad[0].numel() > 0 else None
+
+
+def source_lengths(encoder_out, B: int, T: int) -> torch.Tensor:
+    """valid source rows per batch row: from the padding mask, T where there is none"""
+    pad = source_padding(encoder_out)
+    return torch.full((B,), T) if pad is None else (~pad).sum(1)
 
 
 class DecoderState:
@@ -128,13 +173,6 @@ class DecoderState:
     def grow(self, cap: Optional[int] = None, S_cap: Optional[int] = None):
         """Re-allocate the caches with larger capacities, keeping their contents (a streaming source of unknown
         length: the reference's caches grow by concatenation, modules/monotonic_multihead_attention.py:401)."""
-        def regrow(lst, dim_new):
-            out = []
-            for t in lst:
-                n = torch.zeros(t.shape[0], t.shape[1], dim_new, t.shape[3], device=t.device, dtype=t.dtype)
-                n[:, :, :t.shape[2]] = t
-                out.append(n)
-            return out
         if cap is not None and cap > self.cap:
             self.k_cache, self.v_cache, self.cap = regrow(self.k_cache, cap), regrow(self.v_cache, cap), cap
         if S_cap is not None and S_cap > self.S_cap:
@@ -317,11 +355,12 @@ class MMADecoder:
         pos_row = (st.n_prev + (cfg.padding_idx + 1)).contiguous()
         x = ops.embed_tokens(last_tokens, Wd.E, Wd.pos, pos_row, self.embed_scale)
         incremental = True
+
+        def attend(qkv, l):
+            return ops.decoder_self_attention(qkv, st.k_cache[l], st.v_cache[l], st.n_prev)
+
         for l, L in enumerate(Wd.layers):
-            y = ops.layernorm(x, L["ln1_g"], L["ln1_b"])
-            qkv = ops.linear(y, L["wqkv"], L["bqkv"])
-            ctx = ops.decoder_self_attention(qkv, st.k_cache[l], st.v_cache[l], st.n_prev)
-            x = ops.linear(ctx, L["wo"], L["bo"], epilogue=EPI_BIAS_RES, residual=x)
+            x = self_attention_block(ops, L, x, attend, l)
             y = ops.layernorm(x, L["ln2_g"], L["ln2_b"])
             q = None
             if self.full:              # plain encoder-decoder attention: softmax over [0, enc_len), no policy
@@ -329,9 +368,7 @@ class MMADecoder:
                 ctx, _ = ops.decoder_cross_attention(q, st.Kmono[l], st.V[l], None, H=H, attn_type=self.attn_enum,
                                                      mass_preservation=False, key_len=st.enc_len)
                 x = ops.linear(ctx, L["c_wo"], L["c_bo"], epilogue=EPI_BIAS_RES, residual=x)
-                y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
-                hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
-                x = ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+                x = feed_forward_block(ops, L, x)
                 continue
             p = torch.empty(B * H, st.S_cap, device=self.device, dtype=torch.float32)
             if cfg.attn_type == "waitk":
@@ -354,9 +391,7 @@ class MMADecoder:
             ctx, _ = ops.decoder_cross_attention(q, Ks, st.V[l], st.head_step[l], H=H, attn_type=self.attn_enum,
                                                  mass_preservation=cfg.mass_preservation, key_len=st.enc_len)
             x = ops.linear(ctx, L["c_wo"], L["c_bo"], epilogue=EPI_BIAS_RES, residual=x)
-            y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
-            hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
-            x = ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+            x = feed_forward_block(ops, L, x)
             if stop_on_read and st.online and bool(head_read.any()):
                 return None, 0          # n_prev not advanced == clear_cache(i + 1)
         y = ops.layernorm(x, Wd.ln_g, Wd.ln_b)
@@ -403,10 +438,7 @@ class MMADecoder:
             st.grow(S_cap=max(2 * st.S_cap, T + 32))
         if T > st.enc_rows:
             new = enc[st.enc_rows:T].to(device=self.device, dtype=self.dtype).transpose(0, 1).contiguous()
-            pad = encoder_out.get("encoder_padding_mask") or []
-            lens = (~pad[0]).sum(1) if len(pad) > 0 and pad[0] is not None and pad[0].numel() > 0 \
-                else torch.full((B,), T)
-            self.append_encoder_out(st, new, lens)
+            self.append_encoder_out(st, new, source_lengths(encoder_out, B, T))
         if st.n_prev_host != n_written:
             st.n_prev.fill_(n_written)
             st.n_prev_host = n_written
@@ -425,13 +457,11 @@ class MMADecoder:
         reference passes no self-attention padding mask, so the outputs at and behind a row's own target length are unspecified."""
         enc = encoder_out["encoder_out"][0]
         T, B = enc.shape[0], enc.shape[1]
-        pad = encoder_out.get("encoder_padding_mask") or []
-        has_pad = len(pad) > 0 and pad[0] is not None and pad[0].numel() > 0
-        lens = (~pad[0]).sum(1) if has_pad else torch.full((B,), T)
+        lens = source_lengths(encoder_out, B, T)
         enc_btd = enc.to(device=self.device, dtype=self.dtype).transpose(0, 1).contiguous()
         out, attn_list = self.forward_teacher_forced(prev_output_tokens, enc_btd, lens, features_only=features_only)
         return out, {"action": 1, "attn": [None], "attn_list": attn_list, "encoder_out": encoder_out,
-                     "encoder_padding_mask": pad[0] if has_pad else None}
+                     "encoder_padding_mask": source_padding(encoder_out)}
 
     def forward_teacher_forced(self, prev_output_tokens: torch.Tensor, enc_btd: torch.Tensor, enc_len: torch.Tensor, *,
                                features_only: bool = False, want_attn: bool = True):
@@ -458,11 +488,12 @@ class MMADecoder:
         thr = cfg.fixed_pre_decision_pad_threshold
         chunk = cfg.mocha_chunk_size if cfg.attn_type == "chunkwise" else None
         attn_list, bufs = ([] if want_attn else None), None
+
+        def attend(qkv, l):
+            return ops.decoder_self_attention_causal(qkv.view(B, U, 3 * D), H=H).view(B * U, D)
+
         for l, L in enumerate(Wd.layers):
-            y = ops.layernorm(x, L["ln1_g"], L["ln1_b"])
-            qkv = ops.linear(y, L["wqkv"], L["bqkv"])
-            ctx = ops.decoder_self_attention_causal(qkv.view(B, U, 3 * D), H=H)
-            x = ops.linear(ctx.view(B * U, D), L["wo"], L["bo"], epilogue=EPI_BIAS_RES, residual=x)
+            x = self_attention_block(ops, L, x, attend, l)
             y = ops.layernorm(x, L["ln2_g"], L["ln2_b"])
             if want_attn or bufs is None:
                 bufs = [torch.empty(B * H, U, S, device=self.device, dtype=torch.float32) for _ in range(4)]
@@ -495,9 +526,7 @@ class MMADecoder:
                                                          "beta": beta.view(B, H, U, S)})
             ctx = ops.mma_context(beta, st.V[l])
             x = ops.linear(ctx.view(B * U, D), L["c_wo"], L["c_bo"], epilogue=EPI_BIAS_RES, residual=x)
-            y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
-            hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
-            x = ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+            x = feed_forward_block(ops, L, x)
         y = ops.layernorm(x, Wd.ln_g, Wd.ln_b)
         if features_only:
             return y.view(B, U, D), attn_list
@@ -721,35 +750,21 @@ class MMADecoder:
         gathers each row's self-attention prefix and monotonic step from its parent row into the state's second buffer set, and the
         two sets swap.  Returns (tokens [Bs, nbest, L] int64 with padding_idx behind each hypothesis, lengths [Bs, nbest] int32 (EOS
         included), scores [Bs, nbest] fp32, positional scores [Bs, nbest, L] fp32, stats {"steps"}), on the device; L = max(max_len) + 1."""
-        from .beam import BeamSearch, check_args
+        from .beam import BeamSearch, ReorderBuffers, check_args, sentence_caps
         cfg = self.cfg
         Bs, S, D = enc_btd.shape
-        caps = [int(max_len)] * Bs if isinstance(max_len, int) else [int(x) for x in max_len]
-        assert len(caps) == Bs, "one cap per sentence"
+        caps = sentence_caps(max_len, Bs)
         check_args(beam, nbest, cfg.vocab)
         R = Bs * beam
         bs = BeamSearch(self.ops, caps, beam=beam, V=cfg.vocab, eos=cfg.eos, pad=cfg.padding_idx, lenpen=lenpen, nbest=nbest,
                         device=self.device)
         st = self._offline_state(R, bs.L, S, s_cap, None, cache="_beam_states")
-        if getattr(st, "alt", None) is None:
-            # the second buffer set of the reorder: self-attention K/V and head_step; the cross-attention buffers are per sentence
-            st.alt = {"k": [torch.zeros_like(t) for t in st.k_cache], "v": [torch.zeros_like(t) for t in st.v_cache],
-                      "hs": [torch.zeros_like(t) for t in st.head_step]}
-        for hs in st.alt["hs"]:
+        # the second buffer set of the reorder: self-attention K/V and head_step; the cross-attention buffers are per sentence
+        buf = ReorderBuffers.of(st, extra=("head_step",))
+        for hs in buf.other["head_step"]:
             hs.zero_()
         self.append_encoder_out(st, enc_btd.repeat_interleave(beam, 0), enc_len.to(self.device).repeat_interleave(beam))
         cap0 = st.cap
-        desc = _lib.DecoderDesc()
-        desc.B, desc.D, desc.H, desc.n_layers, desc.cap = R, cfg.embed_dim, cfg.num_heads, cfg.decoder_layers, st.cap
-        desc.dtype = _lib.F32 if self.dtype == torch.float32 else _lib.BF16
-
-        def layer_structs(k, v, hs):
-            arr = (_lib.DecLayer * cfg.decoder_layers)()
-            for l in range(cfg.decoder_layers):
-                arr[l].k_cache, arr[l].v_cache, arr[l].head_step = k[l].data_ptr(), v[l].data_ptr(), hs[l].data_ptr()
-            return arr
-
-        sets = [layer_structs(st.k_cache, st.v_cache, st.head_step), layer_structs(st.alt["k"], st.alt["v"], st.alt["hs"])]
 
         def logits_fn(t, toks):
             logits, _ = self.step(st, toks)
@@ -758,11 +773,8 @@ class MMADecoder:
         def after_select(t):
             self.commit(st)
             assert st.cap == cap0, "beam state outgrew its capacity"
-            self.ops.beam_reorder(desc, sets[0], sets[1], bs.reorder, bs.finished, bs.result[2:3], beam=beam, n_prev=st.n_prev_host)
-            st.k_cache, st.alt["k"] = st.alt["k"], st.k_cache
-            st.v_cache, st.alt["v"] = st.alt["v"], st.v_cache
-            st.head_step, st.alt["hs"] = st.alt["hs"], st.head_step
-            sets.reverse()
+            self.ops.beam_reorder(buf.desc, buf.src, buf.dst, bs.reorder, bs.finished, bs.result[2:3], beam=beam, n_prev=st.n_prev_host)
+            buf.swap()
 
         tokens, lengths, scores, pos = bs.run(logits_fn, after_select, chunk=chunk)
         return tokens, lengths, scores, pos, {"steps": bs.steps}

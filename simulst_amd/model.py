@@ -98,6 +98,17 @@ class FairseqModelSurface:
     def max_positions(self):
         return (self.cfg.max_source_positions, self.cfg.max_target_positions)
 
+    def max_decoder_positions(self):
+        return self.cfg.max_target_positions
+
+    def get_normalized_probs(self, net_output, log_probs=True):
+        logits = net_output[0].float()
+        return torch.log_softmax(logits, -1) if log_probs else torch.softmax(logits, -1)
+
+    def target_cap(self, T: int, max_len_a: float = 0.1, max_len_b: float = 10) -> int:
+        """the tokens a sentence of T source frames may decode before its EOS (eval/generate.py --max-len-a / --max-len-b)"""
+        return min(int(max_len_a * T + max_len_b), self.cfg.max_target_positions - 1)
+
 
 class SimulSTModel(FairseqModelSurface):
     """encoder/decoder holder with the attributes the agents use (agents/default_agent.py:157-175,
@@ -115,13 +126,6 @@ class SimulSTModel(FairseqModelSurface):
                                           shared_weights=share_with.encoder.w if share_with else None)
         self.decoder = MMADecoder(cfg, weights, device, dtype, self.ops,
                                   shared_weights=share_with.decoder.w if share_with else None)
-
-    def get_normalized_probs(self, net_output, log_probs=True):
-        logits = net_output[0]
-        return torch.log_softmax(logits.float(), -1) if log_probs else torch.softmax(logits.float(), -1)
-
-    def max_decoder_positions(self):
-        return self.cfg.max_target_positions
 
     def generate_offline(self, src_tokens, src_lengths, n_steps=None, mask_eos=False, fused=True):
         """task.inference_step with beam 1 (eval/generate.py:200-209; exp/infer_st.yaml:2-5):
@@ -142,7 +146,7 @@ class SimulSTModel(FairseqModelSurface):
         from .beam import hypotheses
         enc = self.encoder.forward(src_tokens, src_lengths)
         lens = [int(t) for t in torch.as_tensor(src_lengths).tolist()]
-        max_len = [min(int(max_len_a * t + max_len_b), self.cfg.max_target_positions - 1) for t in lens]
+        max_len = [self.target_cap(t, max_len_a, max_len_b) for t in lens]
         toks, lengths, scores, pos, _ = self.decoder.beam_offline(enc["encoder_out_btd"], enc["encoder_lengths"], max_len, beam=beam,
                                                                   lenpen=lenpen, nbest=nbest)
         return hypotheses(toks, lengths, scores, pos)

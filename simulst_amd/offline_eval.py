@@ -134,7 +134,7 @@ def decode_batch(model, batch, retire=True, stop_at_eos=False, beam=1, lenpen=1.
     fb, Ld, L, steps, Tpad = batch
     enc = model.encoder.forward(fb, Ld)
     if beam > 1:
-        caps = [min(max_steps(int(t)), model.cfg.max_target_positions - 1) for t in L.tolist()]
+        caps = [model.target_cap(int(t)) for t in L.tolist()]
         toks, _, _, _, _ = model.decoder.beam_offline(enc["encoder_out_btd"], enc["encoder_lengths"], caps, beam=beam, lenpen=lenpen,
                                                       nbest=1, s_cap=Tpad // 4 + 1)
         return toks[:, 0]

@@ -34,10 +34,11 @@ from typing import Dict, List, Optional
 import torch
 
 from .config import ModelConfig
-from .decoder import _DecoderLayerView, _Dictionary, ensure_positions, sinusoidal_table
+from .decoder import (_DecoderLayerView, _Dictionary, ensure_positions, feed_forward_block, load_decoder_stack, regrow,
+                      self_attention_block, source_lengths)
 from .encoder import S2TEmformerEncoder
 from .model import FairseqModelSurface, _default, s2t_emformer_s
-from .ops import EPI_BIAS_F32OUT, EPI_BIAS_GELU, EPI_BIAS_RES, Ops
+from .ops import EPI_BIAS_F32OUT, Ops
 
 BLANK = 0          # the blank is bos (models/transducer_model.py:140,176,195)
 BLANK_AT_EOS = -1e4
@@ -47,33 +48,8 @@ class TransducerWeights:
     """prediction network + joiner weights on the device"""
 
     def __init__(self, w: Dict[str, torch.Tensor], cfg: ModelConfig, device, dtype, ops: Ops, prefix="decoder"):
-        f32 = dict(device=device, dtype=torch.float32)
-        act = dict(device=device, dtype=dtype)
+        W, Bv = load_decoder_stack(self, w, cfg, device, dtype, prefix)
         p = prefix
-
-        def W(name):
-            return w[name].contiguous().to(**act)
-
-        def Bv(name):
-            return w[name].float().contiguous().to(**f32)
-
-        self.E = W(f"{p}.embed_tokens.weight")
-        self.out_proj = W(f"{p}.output_projection.weight")
-        self.pos = sinusoidal_table(cfg.max_target_positions + cfg.padding_idx + 2, cfg.embed_dim, cfg.padding_idx).to(**f32)
-        self._pos_args = (cfg.embed_dim, cfg.padding_idx, f32)
-        self.ln_g, self.ln_b = Bv(f"{p}.layer_norm.weight"), Bv(f"{p}.layer_norm.bias")
-        self.layers = []
-        for l in range(cfg.decoder_layers):
-            lp = f"{p}.layers.{l}"
-            L = {}
-            L["wqkv"] = torch.cat([w[f"{lp}.self_attn.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0).contiguous().to(**act)
-            L["bqkv"] = torch.cat([w[f"{lp}.self_attn.{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0).float().to(**f32)
-            L["wo"], L["bo"] = W(f"{lp}.self_attn.out_proj.weight"), Bv(f"{lp}.self_attn.out_proj.bias")
-            L["ln1_g"], L["ln1_b"] = Bv(f"{lp}.self_attn_layer_norm.weight"), Bv(f"{lp}.self_attn_layer_norm.bias")
-            L["ln3_g"], L["ln3_b"] = Bv(f"{lp}.final_layer_norm.weight"), Bv(f"{lp}.final_layer_norm.bias")
-            L["fc1"], L["b1"] = W(f"{lp}.fc1.weight"), Bv(f"{lp}.fc1.bias")
-            L["fc2"], L["b2"] = W(f"{lp}.fc2.weight"), Bv(f"{lp}.fc2.bias")
-            self.layers.append(L)
         # joiner (:28-58)
         self.w_src, self.b_src = W(f"{p}.joiner.source_projection.weight"), Bv(f"{p}.joiner.source_projection.bias")
         self.w_tgt = W(f"{p}.joiner.target_projection.weight")
@@ -92,7 +68,7 @@ class TransducerState:
         self.n_prev = torch.zeros(B, device=device, dtype=torch.int32)
         self.n_prev_host = 0
         self.kv_rows = 0                 # K/V positions written so far, the uncommitted newest one included (forward())
-        self.alt = None                  # second K/V + prev_emit set of the beam reorder
+        self.reorder_buf = None          # beam.ReorderBuffers: second K/V + prev_emit set of the beam reorder
         self.P = None                    # [B, S', D] fp32
         self.pooled = None               # [B, S', D] model dtype
         self.src_len = None              # [B] int32 (src_len')
@@ -103,29 +79,12 @@ class TransducerState:
         self.emit_before: List[torch.Tensor] = []
 
     def grow(self, cap: int):
-        def regrow(lst):
-            out = []
-            for t in lst:
-                n = torch.zeros(t.shape[0], t.shape[1], cap, t.shape[3], device=t.device, dtype=t.dtype)
-                n[:, :, :t.shape[2]] = t
-                out.append(n)
-            return out
         if cap > self.cap:
-            self.k_cache, self.v_cache, self.cap = regrow(self.k_cache), regrow(self.v_cache), cap
-            if self.alt is not None:
-                self.alt["k"], self.alt["v"] = regrow(self.alt["k"]), regrow(self.alt["v"])
-
-    def ensure_alt(self):
-        if self.alt is None:
-            self.alt = {"k": [torch.zeros_like(t) for t in self.k_cache], "v": [torch.zeros_like(t) for t in self.v_cache],
-                        "pe": torch.zeros_like(self.prev_emit)}
-        return self.alt
-
-    def swap_alt(self):
-        a = self.alt
-        self.k_cache, a["k"] = a["k"], self.k_cache
-        self.v_cache, a["v"] = a["v"], self.v_cache
-        self.prev_emit, a["pe"] = a["pe"], self.prev_emit
+            if self.reorder_buf is not None:
+                self.reorder_buf.grow(cap)           # both sets
+            else:
+                self.k_cache, self.v_cache = regrow(self.k_cache, cap), regrow(self.v_cache, cap)
+            self.cap = cap
 
 
 class TransducerDecoder:
@@ -192,14 +151,13 @@ class TransducerDecoder:
             last_tokens = torch.full_like(last_tokens, BLANK)
         pos_row = (st.n_prev + (cfg.padding_idx + 1)).contiguous()
         x = ops.embed_tokens(last_tokens, Wd.E, Wd.pos, pos_row, self.embed_scale)
+
+        def attend(qkv, l):
+            return ops.decoder_self_attention(qkv, st.k_cache[l], st.v_cache[l], st.n_prev)
+
         for l, L in enumerate(Wd.layers):
-            y = ops.layernorm(x, L["ln1_g"], L["ln1_b"])
-            qkv = ops.linear(y, L["wqkv"], L["bqkv"])
-            ctx = ops.decoder_self_attention(qkv, st.k_cache[l], st.v_cache[l], st.n_prev)
-            x = ops.linear(ctx, L["wo"], L["bo"], epilogue=EPI_BIAS_RES, residual=x)
-            y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
-            hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
-            x = ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+            x = self_attention_block(ops, L, x, attend, l)
+            x = feed_forward_block(ops, L, x)
         return ops.layernorm(x, Wd.ln_g, Wd.ln_b)
 
     def step(self, st: TransducerState, last_tokens: torch.Tensor) -> torch.Tensor:
@@ -239,23 +197,6 @@ class TransducerDecoder:
         return out.t().contiguous(), emit.t().contiguous(), st
 
     # ------------------------------------------------------------------ beam search
-    def _reorder_args(self, st: TransducerState):
-        """the descriptor and the two layer arrays (current set, second set) simulst_transducer_beam_reorder reads"""
-        from . import _lib
-        cfg = self.cfg
-        alt = st.ensure_alt()
-        desc = _lib.DecoderDesc()
-        desc.B, desc.D, desc.H, desc.n_layers, desc.cap = st.B, cfg.embed_dim, cfg.num_heads, cfg.decoder_layers, st.cap
-        desc.dtype = _lib.F32 if self.dtype == torch.float32 else _lib.BF16
-
-        def layer_structs(k, v):
-            arr = (_lib.DecLayer * cfg.decoder_layers)()
-            for l in range(cfg.decoder_layers):
-                arr[l].k_cache, arr[l].v_cache = k[l].data_ptr(), v[l].data_ptr()
-            return arr
-
-        return desc, layer_structs(st.k_cache, st.v_cache), layer_structs(alt["k"], alt["v"])
-
     def beam_offline(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, max_len, *, beam: int, lenpen: float = 1.0, nbest: int = 1,
                      chunk: int = 8, T: Optional[int] = None):
         """Beam search with fairseq's SequenceGenerator semantics (simulst_amd/beam.py, DESIGN.md "Beam search") over the
@@ -267,18 +208,16 @@ class TransducerDecoder:
         second set, and the sets swap.  Returns (tokens [Bs, nbest, L] int64, lengths [Bs, nbest] int32, scores [Bs, nbest] fp32,
         positional scores [Bs, nbest, L] fp32, emit [Bs, nbest, L] int32 -- the pooled frame each token of the hypothesis (its EOS
         included) was emitted at, -1 behind it --, stats {"steps"}), on the device; L = max(max_len) + 1."""
-        from .beam import BeamSearch, check_args
+        from .beam import BeamSearch, ReorderBuffers, check_args, sentence_caps
         cfg, ops, V = self.cfg, self.ops, self.cfg.vocab
         Bs = enc_btd.size(0)
-        caps = [int(max_len)] * Bs if isinstance(max_len, int) else [int(x) for x in max_len]
-        assert len(caps) == Bs, "one cap per sentence"
+        caps = sentence_caps(max_len, Bs)
         check_args(beam, nbest, V)
         R = Bs * beam
         bs = BeamSearch(ops, caps, beam=beam, V=V, eos=cfg.eos, pad=cfg.padding_idx, lenpen=lenpen, nbest=nbest, device=self.device)
         st = self.new_state(R, cap=bs.L + 2)
         self.set_source(st, enc_btd.to(self.device), enc_len, T, rows=R)
-        desc, cur, alt = self._reorder_args(st)
-        sets = [cur, alt]
+        buf = ReorderBuffers.of(st, extra=("prev_emit",))
         cap0 = st.cap
         emit_log = torch.full((bs.L, R), -1, device=self.device, dtype=torch.int32)
 
@@ -295,10 +234,9 @@ class TransducerDecoder:
         def after_select(t):
             self.commit(st)
             assert st.cap == cap0, "beam state outgrew its capacity"
-            ops.transducer_beam_reorder(desc, sets[0], sets[1], st.prev_emit, st.alt["pe"], bs.reorder, bs.finished, bs.result[2:3],
-                                        block=beam, n_prev=st.n_prev_host)
-            st.swap_alt()
-            sets.reverse()
+            ops.transducer_beam_reorder(buf.desc, buf.src, buf.dst, st.prev_emit, buf.other["prev_emit"], bs.reorder, bs.finished,
+                                        bs.result[2:3], block=beam, n_prev=st.n_prev_host)
+            buf.swap()
 
         tokens, lengths, scores, pos = bs.run(logits_fn, after_select, chunk=chunk)
         emit = self._hypothesis_emit(bs, emit_log).to(self.device)
@@ -337,14 +275,13 @@ class TransducerDecoder:
         toks = tokens.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
         pos_row = torch.arange(cfg.padding_idx + 1, cfg.padding_idx + 1 + U1, device=self.device, dtype=torch.int32).repeat(B)
         x = ops.embed_tokens(toks, Wd.E, Wd.pos, pos_row, self.embed_scale)              # [B * U1, D]
-        for L in Wd.layers:
-            y = ops.layernorm(x, L["ln1_g"], L["ln1_b"])
-            qkv = ops.linear(y, L["wqkv"], L["bqkv"])
-            ctx = ops.decoder_self_attention_causal(qkv.view(B, U1, 3 * D), H=H)
-            x = ops.linear(ctx.view(B * U1, D), L["wo"], L["bo"], epilogue=EPI_BIAS_RES, residual=x)
-            y = ops.layernorm(x, L["ln3_g"], L["ln3_b"])
-            hdn = ops.linear(y, L["fc1"], L["b1"], epilogue=EPI_BIAS_GELU)
-            x = ops.linear(hdn, L["fc2"], L["b2"], epilogue=EPI_BIAS_RES, residual=x)
+
+        def attend(qkv, l):
+            return ops.decoder_self_attention_causal(qkv.view(B, U1, 3 * D), H=H).view(B * U1, D)
+
+        for l, L in enumerate(Wd.layers):
+            x = self_attention_block(ops, L, x, attend, l)
+            x = feed_forward_block(ops, L, x)
         return ops.layernorm(x, Wd.ln_g, Wd.ln_b).view(B, U1, D)
 
     def lattice_inputs(self, prev_output_tokens: torch.Tensor):
@@ -412,9 +349,8 @@ class TransducerDecoder:
         if n_written + 2 > st.cap:
             st.grow(max(2 * st.cap, n_written + 8))
         if st.enc_rows != T:
-            pad = encoder_out.get("encoder_padding_mask") or []
-            lens = (~pad[0]).sum(1) if len(pad) > 0 and pad[0] is not None and pad[0].numel() > 0 else torch.full((B,), T)
-            self.set_source(st, enc.to(device=self.device, dtype=self.dtype).transpose(0, 1).contiguous(), lens, T=T)
+            self.set_source(st, enc.to(device=self.device, dtype=self.dtype).transpose(0, 1).contiguous(),
+                            source_lengths(encoder_out, B, T), T=T)
         if n_written > len(st.emit_before):
             raise ValueError(f"TransducerDecoder.forward: {n_written} tokens written but only {len(st.emit_before)} steps were taken")
         if n_written < len(st.emit_before):                      # a repeated prefix: back to where its last step started
@@ -448,11 +384,12 @@ class TransducerDecoder:
         if order.numel() != R:
             raise ValueError(f"reorder_incremental_state: new_order holds {order.numel()} rows, the state {R} (the state's row count "
                              "is fixed; finished rows stay in the batch)")
-        desc, cur, alt = self._reorder_args(st)
+        from .beam import ReorderBuffers
+        buf = ReorderBuffers.of(st, extra=("prev_emit",))
         result = torch.zeros(1, device=self.device, dtype=torch.int32)
-        self.ops.transducer_beam_reorder(desc, cur, alt, st.prev_emit, st.alt["pe"], order, None, result, block=R,
-                                         n_prev=min(st.kv_rows, st.cap))
-        st.swap_alt()
+        self.ops.transducer_beam_reorder(buf.desc, buf.src, buf.dst, st.prev_emit, buf.other["prev_emit"], order, None, result,
+                                         block=R, n_prev=min(st.kv_rows, st.cap))
+        buf.swap()
         idx = order.long()
         st.emit_before = [e.index_select(0, idx) for e in st.emit_before]
         if st.P is not None and st.P.size(0) == R:
@@ -483,13 +420,6 @@ class TransducerModel(FairseqModelSurface):
         FairseqModelSurface.add_args(parser)
         parser.add_argument("--downsample", type=int)
 
-    def get_normalized_probs(self, net_output, log_probs=True):
-        logits = net_output[0]
-        return torch.log_softmax(logits.float(), -1) if log_probs else torch.softmax(logits.float(), -1)
-
-    def max_decoder_positions(self):
-        return self.cfg.max_target_positions
-
     def generate_offline(self, src_tokens, src_lengths, n_steps=None, mask_eos=False, *, beam=1, lenpen=1.0, nbest=1):
         """the encoder once, then greedy transducer steps.  Returns tokens [B, n] and a dict with "emit" [B, n] (the pooled frame
         each token was emitted at), the encoder output and the state.  T = max(encoder_lengths) is read once per batch: the pooled
@@ -514,8 +444,8 @@ class TransducerModel(FairseqModelSurface):
         from .beam import hypotheses
         enc = self.encoder.forward(src_tokens, src_lengths)
         lens = [int(t) for t in torch.as_tensor(src_lengths).tolist()]
-        top = self.cfg.max_target_positions - 1
-        caps = [min(int(max_len_a * t + max_len_b) if max_len is None else int(max_len), top) for t in lens]
+        a, b = (max_len_a, max_len_b) if max_len is None else (0, max_len)
+        caps = [self.target_cap(t, a, b) for t in lens]
         T = int(enc["encoder_lengths"].max().item())
         toks, lengths, scores, pos, emit, _ = self.decoder.beam_offline(enc["encoder_out_btd"], enc["encoder_lengths"], caps, beam=beam,
                                                                         lenpen=lenpen, nbest=nbest, T=T)

@@ -238,6 +238,58 @@ def test_reorder_gathers_the_parent_prefix(dtype):
     assert torch.equal(hso[0].cpu().view(R, H)[4], hs[0].cpu().view(R, H)[4])
 
 
+@pytest.mark.parametrize("with_head_read", [True, False])
+@pytest.mark.parametrize("n_prev", [0, 1, 5])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_reorder_at_the_copy_edges(dtype, n_prev, with_head_read):
+    """the smallest heads: in bf16 one position of one head (d = 8) is exactly one 16-byte piece; no prefix, one position, the whole
+    cache (n_prev == cap); head_read in both sets or null in both"""
+    from simulst_amd import _lib
+    from simulst_amd.ops import Ops
+    ops = Ops()
+    g = torch.Generator().manual_seed(40 + n_prev)
+    Bs, beam, H, d, cap, Ld = 2, 3, 2, 8, 5, 2
+    R = Bs * beam
+    k = [torch.randn(R, H, cap, d, generator=g).to(dtype).cuda() for _ in range(Ld)]
+    v = [torch.randn(R, H, cap, d, generator=g).to(dtype).cuda() for _ in range(Ld)]
+    hs = [torch.randint(0, 50, (R * H,), generator=g).cuda() for _ in range(Ld)]
+    hr = [torch.randint(0, 2, (R * H,), generator=g).to(torch.uint8).cuda() for _ in range(Ld)]
+    ko, vo = [torch.full_like(x, 7.0) for x in k], [torch.full_like(x, 7.0) for x in v]
+    hso, hro = [torch.full_like(x, -5) for x in hs], [torch.full_like(x, 9) for x in hr]
+    reorder = torch.tensor([2, 0, 0, 4, 5, 3], dtype=torch.int32)
+    finished = torch.tensor([0, 1], dtype=torch.int32)            # sentence 1: its rows keep their own step, no K/V copy
+    desc = _lib.DecoderDesc()
+    desc.B, desc.D, desc.H, desc.n_layers, desc.cap = R, H * d, H, Ld, cap
+    desc.dtype = _lib.F32 if dtype == torch.float32 else _lib.BF16
+
+    def structs(kk, vv, ss, rr):
+        arr = (_lib.DecLayer * Ld)()
+        for l in range(Ld):
+            arr[l].k_cache, arr[l].v_cache, arr[l].head_step = kk[l].data_ptr(), vv[l].data_ptr(), ss[l].data_ptr()
+            if with_head_read:
+                arr[l].head_read = rr[l].data_ptr()
+        return arr
+
+    result = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ops.beam_reorder(desc, structs(k, v, hs, hr), structs(ko, vo, hso, hro), reorder.cuda(), finished.cuda(), result, beam=beam,
+                     n_prev=n_prev)
+    torch.cuda.synchronize()
+    assert int(result[0]) == 0
+    src = torch.tensor([2, 0, 0, 3, 4, 5])
+    live = torch.tensor([True] * beam + [False] * beam)
+    for l in range(Ld):
+        for a, o in ((k[l], ko[l]), (v[l], vo[l])):
+            exp = a.cpu().index_select(0, src)
+            assert torch.equal(o.cpu()[live, :, :n_prev], exp[live, :, :n_prev])
+            assert bool((o.cpu()[live, :, n_prev:] == 7.0).all())          # nothing beyond the prefix is written
+            assert bool((o.cpu()[~live] == 7.0).all())                     # a finished sentence copies no K/V
+        assert torch.equal(hso[l].cpu().view(R, H), hs[l].cpu().view(R, H).index_select(0, src))
+        if with_head_read:
+            assert torch.equal(hro[l].cpu().view(R, H), hr[l].cpu().view(R, H).index_select(0, src))
+        else:
+            assert bool((hro[l] == 9).all())
+
+
 # ---------------------------------------------------------------------------------------------------- the full model
 def _model_inputs(L=(400, 399, 250, 97)):
     g = torch.Generator().manual_seed(1234)

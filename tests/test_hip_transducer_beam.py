@@ -178,6 +178,55 @@ def test_reorder_against_index_select(ops, dtype, n_prev):
     assert _reorder_case(ops, dtype, R, beam, n_prev, bad)[6] == 2
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_both_reorder_entry_points_move_the_same_bytes(ops, dtype):
+    """simulst_beam_reorder and simulst_transducer_beam_reorder launch one kernel: the same K/V sets, reorder (one index out of its
+    block, one negative), finished list and block = beam give the same K/V bytes and the same count; each call moves its own
+    payload and nothing of the other's"""
+    from simulst_amd import _lib
+    Bs, beam, H, d, cap, Ld, n_prev = 3, 3, 2, 8, 5, 2, 3
+    R = Bs * beam
+    gen = torch.Generator().manual_seed(29)
+    mk = lambda: [torch.randn(R, H, cap, d, generator=gen).to(dtype).to(DEV) for _ in range(Ld)]    # noqa: E731
+    k, v = mk(), mk()
+    hs = [torch.randint(0, 50, (R * H,), generator=gen).to(DEV) for _ in range(Ld)]
+    pe = torch.randint(0, 50, (R,), generator=gen, dtype=torch.int32).to(DEV)
+    order = torch.tensor([1, 1, 5, 4, 3, 3, 8, -1, 6], dtype=torch.int32, device=DEV)          # row 2: out of its block; row 7: negative
+    fin = torch.tensor([0, 1, 0], dtype=torch.int32, device=DEV)
+    desc = _lib.DecoderDesc()
+    desc.B, desc.D, desc.H, desc.n_layers, desc.cap = R, H * d, H, Ld, cap
+    desc.dtype = _lib.F32 if dtype == torch.float32 else _lib.BF16
+
+    def structs(ks, vs, ss=None):
+        arr = (_lib.DecLayer * Ld)()
+        for l in range(Ld):
+            arr[l].k_cache, arr[l].v_cache = ks[l].data_ptr(), vs[l].data_ptr()
+            if ss is not None:
+                arr[l].head_step = ss[l].data_ptr()
+        return arr
+
+    sentinel = lambda ts: [torch.full_like(t, 7.0) for t in ts]                                   # noqa: E731
+    ko_m, vo_m, ko_t, vo_t = sentinel(k), sentinel(v), sentinel(k), sentinel(v)
+    hso = [torch.full_like(t, -5) for t in hs]
+    peo = torch.full((R,), SENT_I, dtype=torch.int32, device=DEV)      # the guard of the MMA call: where a per-row int32 would land
+    res_m, res_t = (torch.zeros(1, dtype=torch.int32, device=DEV) for _ in range(2))
+    ops.beam_reorder(desc, structs(k, v, hs), structs(ko_m, vo_m, hso), order, fin, res_m, beam=beam, n_prev=n_prev)
+    torch.cuda.synchronize()
+    assert bool((peo == SENT_I).all()), "the MMA call writes no per-row int32"
+    hso_m = [t.clone() for t in hso]
+    ops.transducer_beam_reorder(desc, structs(k, v), structs(ko_t, vo_t), pe, peo, order, fin, res_t, block=beam, n_prev=n_prev)
+    torch.cuda.synchronize()
+    for a, b in zip(ko_m + vo_m, ko_t + vo_t):
+        assert torch.equal(a, b)
+    assert int(res_m.item()) == int(res_t.item()) == 2
+    expect = [1, 1, 2, 3, 4, 5, 8, 7, 6]
+    _check_reorder(k, v, ko_t, vo_t, pe.cpu(), peo.cpu(), expect, [True] * 3 + [False] * 3 + [True] * 3, n_prev)
+    idx = torch.tensor(expect, device=DEV)
+    for l in range(Ld):
+        assert torch.equal(hso_m[l].view(R, H), hs[l].view(R, H).index_select(0, idx))
+        assert torch.equal(hso[l], hso_m[l]), "the transducer call moves no head_step"
+
+
 # ------------------------------------------------------------------------------------------------------------ decoder
 SEED, CAPS, BEAM = 83, [12, 10, 8, 6], 4
 
