@@ -14,73 +14,107 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
+// The three builds of the library (Makefile: plain, EXPERIMENTS=1, DEBUG_HOOKS=1) as bits: what a tunable, an option value or a
+// kernel instantiation needs in order to exist (handle.cpp's option table, ffn_variant.h)
+enum { SL_PRODUCT = 0, SL_EXPERIMENTS_BUILD = 1, SL_DEBUG_HOOKS_BUILD = 2 };
+#ifdef SL_EXPERIMENTS
+constexpr int SL_FLAVOUR_EXP = SL_EXPERIMENTS_BUILD;
+#else
+constexpr int SL_FLAVOUR_EXP = 0;
+#endif
+#ifdef SL_DEBUG_HOOKS
+constexpr int SL_FLAVOUR_DBG = SL_DEBUG_HOOKS_BUILD;
+#else
+constexpr int SL_FLAVOUR_DBG = 0;
+#endif
+constexpr int SL_BUILD_FLAVOUR = SL_FLAVOUR_EXP | SL_FLAVOUR_DBG;
+
+// One slot per family of kernels whose dynamic-LDS limit has to be raised before the first launch (sl_raise_lds below)
+enum sl_lds_slot {
+  SL_LDS_FFN,               // ffn_fused.hip: the block form of the fused feed-forward
+  SL_LDS_FFN_PIPE,          // ffn_pipe.hip: its software-pipelined form
+  SL_LDS_QKV_ROWS,          // ffn_pipe.hip qkv_rows_kernel
+  SL_LDS_CONV_POS,          // rowops.hip conv_pos_kernel
+  SL_LDS_CTC,               // ctc_align.hip
+  SL_LDS_DEC_CHAIN,         // dec_chain.hip: the layer chains (and experiments/dec_chain_launch.inc)
+  SL_LDS_DEC_CHAIN_PROBE,   // dec_chain.hip: the chain-race probe kernels (DEBUG_HOOKS builds)
+  SL_LDS_TILE256,           // gemm_tile256.hip: register-staged form
+  SL_LDS_TILE256_RING,      //   ... and the LDS-DMA ring
+  SL_LDS_WSTAT,             // gemm_wstat.hip
+  SL_LDS_JOINER_LATTICE,    // transducer.hip joiner_lattice_kernel
+  SL_LDS_COUNT
+};
+
+// The tunables state their own defaults; simulst_create (handle.cpp) applies the environment on top.  A tunable that the option
+// table of handle.cpp addresses is an int, flags included (one member-pointer type for the table).
 struct simulst_handle {
-  hipStream_t stream;
+  hipStream_t stream = nullptr;
   std::string err;
-  bool timer_on[SIMULST_K_COUNT];
-  double timer_ms[SIMULST_K_COUNT];
-  int64_t timer_n[SIMULST_K_COUNT];
+  bool timer_on[SIMULST_K_COUNT] = {};
+  double timer_ms[SIMULST_K_COUNT] = {};
+  int64_t timer_n[SIMULST_K_COUNT] = {};
   struct EvPair { hipEvent_t a, b; int cls; };
   std::vector<EvPair> ev_pool;   // pooled event pairs of the timed launches since the last read
-  int ev_used;
-  void* ws;            // library-owned scratch (split-K partial tiles), grown on demand
-  size_t ws_bytes;
+  int ev_used = 0;
+  void* ws = nullptr;  // library-owned scratch (split-K partial tiles), grown on demand
+  size_t ws_bytes = 0;
   // cached hipGraph of the last simulst_mma_decode call (replayed when the call repeats exactly)
-  bool graph_on;
-  bool capturing;
-  bool force_valu_attention;   // test hook: route bf16 Emformer attention through the VALU kernel
-  int panel_split_min_rows;    // co-scheduled decode GEMMs (K <= 256, N >= 512): rows from which the row-panel kernel with
-  int panel_split_blocks;      //   split column ranges replaces the 64 x 64 tile kernel, and its target workgroup count
-  int mid_min_blocks;          // 64 x 64 tiles from which the tile kernel takes N >= 512 decode GEMMs (QKV, fc1, vocabulary)
-  int mid_narrow_min_rows;     // rows from which N < 512, K <= 256 decode GEMMs (out-proj, q-proj) take the 64 x 64 tile kernel
-  int skinny_min_blocks_tall;  // k-split decode GEMM with more rows than columns (fc2 of co-scheduled batches): workgroups
-                               //   down to which the tile chooser keeps the 64 x 32 tile
-  int fuse_q_max_rows;         // decode loop: rows up to which LN2 + q-proj ride inside the policy/cross-attention launch
-  bool force_unfused_decode;   // test hook: 7-launch decoder layer even when the head-split workspace is given
-  hipGraphExec_t graph_exec;
-  uint64_t graph_key;
-  bool ffn_lds_attr_set;       // simulst_emformer_ffn did the same for the fused feed-forward kernel
-  bool ffn_pipe_lds_attr_set;  // ... and for its software-pipelined form (ffn_pipe.hip)
-  bool qkv_rows_lds_attr_set;  // ... and for qkv_rows_kernel (ffn_pipe.hip)
-  bool ea_general_only;        // SIMULST_EA_GENERAL=1: expected alignment through the chunked log-space kernel for every S (A/B measurements)
-  int ffn_variant;             // simulst_debug_ffn_variant (DEBUG_HOOKS builds: timing ablations of the fused feed-forward launch)
-  int ffn_waves;               // SIMULST_OPT_FFN_WAVES: 0 the library's choice, 4 / 8 force that geometry of the fused feed-forward
-  bool conv_pos_lds_attr_set;  // simulst_conv_pos raised its kernels' dynamic-LDS limit through this handle
-  bool ctc_lds_attr_set;       // simulst_ctc_best_alignment raised its kernel's dynamic-LDS limit through this handle
+  bool graph_on = false;
+  bool capturing = false;
+  hipGraphExec_t graph_exec = nullptr;
+  uint64_t graph_key = 0;
+  bool lds_raised[SL_LDS_COUNT] = {};   // sl_raise_lds: this handle raised the slot's kernels' dynamic-LDS limit (no process globals)
+  int force_valu_attention = 0;         // test hook: route bf16 Emformer attention through the VALU kernel
+  int force_unfused_decode = 0;         // test hook: 7-launch decoder layer even when the head-split workspace is given
+  int panel_split_min_rows = 2560;      // co-scheduled decode GEMMs (K <= 256, N >= 512): rows from which the row-panel kernel with
+  int panel_split_blocks = 256;         //   split column ranges replaces the 64 x 64 tile kernel, and its target workgroup count
+  int mid_min_blocks = 48;              // 64 x 64 tiles from which the tile kernel takes N >= 512 decode GEMMs (QKV, fc1, vocabulary)
+                                        //   measured with three 448-row sequences in flight (bench.py --steps 20): 192 -> 1.25 M, <= 64 -> 1.29-1.30 M tokens/s
+  int mid_narrow_min_rows = 3072;       // rows from which N < 512, K <= 256 decode GEMMs (out-proj, q-proj) take the 64 x 64 tile kernel
+  int skinny_min_blocks_tall = 192;     // k-split decode GEMM with more rows than columns (fc2 of co-scheduled batches): workgroups
+                                        //   down to which the tile chooser keeps the 64 x 32 tile
+  int fuse_q_max_rows = 128;            // decode loop: rows up to which LN2 + q-proj ride inside the policy/cross-attention launch
+  int ea_general_only = 0;              // SIMULST_EA_GENERAL=1: expected alignment through the chunked log-space kernel for every S (A/B measurements)
+  int ffn_variant = 0;                  // simulst_debug_ffn_variant (DEBUG_HOOKS builds: timing ablations of the fused feed-forward launch)
+  int ffn_waves = 0;                    // SIMULST_OPT_FFN_WAVES: 0 the library's choice, else a code of ffn_variant.h
   // row-local chains of the decoder layer (dec_chain.hip) for co-scheduled bf16 batches
-  bool dec_chain_on;
-  int dec_chain_min_rows;      // rows from which the chains replace the per-GEMM launches (below: head-split block)
-  int dec_chain_max_rows;      // rows above which the per-GEMM launches are kept
-  int dec_chain_ffn_max_rows;  // rows up to which the feed-forward chain is used as well
-  bool dec_tall_ffn;           // SIMULST_OPT_DEC_TALL_FFN: fc2 of the per-GEMM feed-forward on the pipelined tile (dec_gemm_tall.hip)
-  int dec_tall_min_rows;       //   ... from this many rows on
-  bool dec_chain_lds_attr_set;
-  int dec_chain_lds_bytes;     // dynamic LDS requested per chain workgroup (0: the default, dec_chain.hip lds_request)
-  bool dec_chain_probe_attr_set;
-  void* dec_chain_tail;        // investigation: the projection chain dumps its two LDS row buffers here at its end (null: off)
-  int dec_chain_xmode;         // how the chains' MFMAs get their activation fragments (dec_chain.hip mma_unit)
-  int dec_attn_chain_max_rows; // rows up to which self-attention rides inside the projection chain (dec_attn_proj_chain_kernel)
-  int dec_attn_chain_rows;     // rows per workgroup of that launch (0: chosen from the row count)
-  bool dec_embed_qkv_chain;    // offline lockstep decode: commit + embedding inside the next step's first launch (dec_embed_qkv_chain_kernel)
-  bool panel_wide_plain_stores;   // experiment: default-policy stores instead of streaming ones in panel_wide_kernel
-  bool dec_chain_rows32;       // projection / feed-forward / QKV chains on 32-row tiles (dec_chain.hip mfma_block, round 5)
-  int dec_chain_rows32_min;    //   ... from this many rows on
-  bool dec_fuse_ffn_qkv;       // decode loops: feed-forward chain of layer l + LN / QKV of layer l + 1 in one launch (dec_chain.hip, round 5)
-  int* chain_sem;              // its ticket words (one per row tile), device memory, lazily allocated
-  int chain_sem_splits;
-  int tile256;                 // bf16 GLU contractions (the subsampler) on 256 x 256 tiles, one 8-wave workgroup per CU (gemm_tile256.hip):
-                               //   0 off (128 x 128 tiles), 1 register-staged 128-deep k-tiles (round 5), 2 LDS-DMA ring of 64-deep k-tiles (round 6)
-  bool tile256_lds_attr_set, tile256_ring_attr_set;
-  bool wstat;                  // tall K = 256 projections of the encoder on the weight-stationary kernel (gemm_wstat.hip)
-  bool wstat_lds_attr_set;
-  int n_cus;                   // compute units of the device (persistent one-workgroup-per-CU launches)
-  bool panel_wide;             // tall bias-only K = 256 projections on the 64-rows-per-wave panel kernel (gemm_panel.hip panel_wide_kernel)
-  int policy_lds_bytes;        // policy / cross-attention launch of co-scheduled batches: minimum dynamic LDS request (occupancy cap), 0: none
-  int dec_vocab_chain_split;   // workgroups per row tile of the step's closing launch (dec_vocab_chain_kernel); 0: off
-  bool fused_argmax;           // decode loops: per-tile (max, index) partials out of the vocabulary projection instead of fp32 logits
-  bool dec_fuse_proj_cross;    // experiment: projection chain + wait-k cross-attention of a layer in ONE launch (dec_chain.hip)
-  int* fuse_flags;             // its tile flags (1024 words: [1023] = the bounded spin ran out), made on first use
-  int fuse_epoch;              // one per fused launch, monotonic
+  int dec_chain_on = 1;
+  int dec_chain_min_rows = 129;         // rows from which the chains replace the per-GEMM launches (below: head-split block)
+  int dec_chain_max_rows = 1 << 30;     // rows above which the per-GEMM launches are kept
+  int dec_chain_ffn_max_rows = 1024;    // rows up to which the feed-forward chain is used as well
+                                        //   measured (bench.py --steps 20): 448-row sequences +4 %, 640 +2 %, 1280 -2 %, 4096 -3 %
+  int dec_tall_ffn = 1;                 // SIMULST_OPT_DEC_TALL_FFN: fc2 of the per-GEMM feed-forward on the pipelined tile (dec_gemm_tall.hip)
+  int dec_tall_min_rows = 1025;         //   ... from this many rows on: where the feed-forward chain ends (simulst_create: dec_chain_ffn_max_rows + 1)
+  int dec_chain_lds_bytes = 0;          // dynamic LDS requested per chain workgroup (0: the default, dec_chain.hip lds_request)
+  void* dec_chain_tail = nullptr;       // investigation: the projection chain dumps its two LDS row buffers here at its end (null: off)
+  int dec_chain_xmode = 3;              // how the chains' MFMAs get their activation fragments (dec_chain.hip mma_unit); 3: fragments hoisted +
+                                        //   LayerNorm reductions on the DPP path: 1.378 -> 1.401 M tokens/s in the driver form
+  int dec_attn_chain_max_rows = 0;      // rows up to which self-attention rides inside the projection chain (dec_attn_proj_chain_kernel)
+                                        //   OFF: measured slower than the two launches at every cache length (dec_chain.hip)
+  int dec_attn_chain_rows = 0;          // rows per workgroup of that launch (0: chosen from the row count)
+  int dec_embed_qkv_chain = 1;          // offline lockstep decode: commit + embedding inside the next step's first launch (dec_embed_qkv_chain_kernel)
+  int dec_chain_rows32 = 0;             // experiment, off: projection / feed-forward / QKV chains on 32-row tiles (dec_chain.hip mfma_block, chain_rtl, round 5)
+  int dec_chain_rows32_min = 256;       //   ... from this many rows on
+  int dec_fuse_ffn_qkv = 0;             // experiment, off: decode loops: feed-forward chain of layer l + LN / QKV of
+                                        //   layer l + 1 in one launch (dec_chain.hip)
+  int* chain_sem = nullptr;             // its ticket words (one per row tile), device memory, lazily allocated
+  int chain_sem_splits = 0;
+  int tile256 = 2;                      // bf16 GLU contractions (the subsampler) on 256 x 256 tiles, one 8-wave workgroup per CU (gemm_tile256.hip):
+                                        //   0 off (128 x 128 tiles), 1 register-staged 128-deep k-tiles (round 5), 2 LDS-DMA ring of 64-deep k-tiles (round 6)
+  int wstat = 1;                        // tall K = 256 projections of the encoder on the weight-stationary kernel (gemm_wstat.hip)
+  int n_cus = 0;                        // compute units of the device (persistent one-workgroup-per-CU launches)
+  bool panel_wide = true;               // tall bias-only K = 256 projections on the 64-rows-per-wave panel kernel (gemm_panel.hip panel_wide_kernel)
+  bool panel_wide_plain_stores = false; // experiment: default-policy stores instead of streaming ones in panel_wide_kernel
+  int policy_lds_bytes = 0;             // policy / cross-attention launch of co-scheduled batches: minimum dynamic LDS request (occupancy cap), 0: none
+  // the decode step's closing launch (dec_chain.hip dec_vocab_chain_kernel), workgroups per 16-row tile; 0: off.  Driver form at 448-row sequences
+  // (bench.py --steps 20, two rounds each): off 1.490 / 1.497 M tokens/s, 1: 1.474, 2: 1.500 / 1.492, 4: 1.515 / 1.514 / 1.504, 8: 1.498 / 1.504 /
+  // 1.503, 16: 1.500; one sequence alone 50.2-50.4 ms with 4 or 8 against 50.6-50.7 ms
+  int dec_vocab_chain_split = 4;
+  int fused_argmax = 1;                 // decode loops: per-tile (max, index) partials out of the vocabulary projection's epilogue instead of fp32
+                                        //   logits (greedy pick, bf16, co-scheduled rows)
+  int dec_fuse_proj_cross = 0;          // experiment, off: projection chain + wait-k cross-attention of a layer in ONE launch (dec_chain.hip)
+  int* fuse_flags = nullptr;            // its tile flags (1024 words: [1023] = the bounded spin ran out), made on first use
+  int fuse_epoch = 0;                   // one per fused launch, monotonic
 };
 
 #define SL_CHECK_NULL(h, p)                                   \
@@ -136,6 +170,16 @@ static inline int sl_launch_status(simulst_handle* h, const char* what) {
     return (int)e;
   }
   return SIMULST_OK;
+}
+
+// Kernels that ask for more dynamic LDS than the default limit: raised once per handle and slot, before the slot's first launch.
+// The caller's list is a `static const` array (kernel addresses and byte counts are constants: nothing is built per call); the flag
+// test is all a later call pays.  On failure h->err names the caller and the positive hipError_t comes back.
+struct sl_lds_limit { const void* kernel; int bytes; };
+int sl_raise_lds_limits(simulst_handle* h, sl_lds_slot slot, const sl_lds_limit* list, int n, const char* who);      // handle.cpp
+template <int N>
+static inline int sl_raise_lds(simulst_handle* h, sl_lds_slot slot, const sl_lds_limit (&list)[N], const char* who) {
+  return h->lds_raised[slot] ? SIMULST_OK : sl_raise_lds_limits(h, slot, list, N, who);
 }
 
 // ---- fixed pre-decision pooling (modules/fixed_pre_decision.py:23-52,97-131) ------------------------------------

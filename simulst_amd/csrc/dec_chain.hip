@@ -932,32 +932,7 @@ static int lds_request(const simulst_handle* h, int rtl = 1) {
 #endif
 }
 
-template <int XM> static hipError_t exp_raise_lds_limits();
-
-template <int XM>
-static hipError_t raise_lds_limits_mode() {
-  hipError_t e = hipFuncSetAttribute((const void*)dec_proj_chain_kernel<1, XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_ffn_chain_kernel<1, true, XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_ffn_chain_kernel<1, false, XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_qkv_chain_kernel<1, XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_vocab_chain_kernel<XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_embed_qkv_chain_kernel<XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  if (e == hipSuccess) e = exp_raise_lds_limits<XM>();       // (EXPERIMENTS builds: the measured-slower forms; else nothing)
-  return e;
-}
-
-static int raise_lds_limits(simulst_handle* h) {
-  if (h->dec_chain_lds_attr_set) return SIMULST_OK;
-  hipError_t e = raise_lds_limits_mode<3>();
-#ifdef SL_DEBUG_HOOKS
-  if (e == hipSuccess) e = raise_lds_limits_mode<0>();
-  if (e == hipSuccess) e = raise_lds_limits_mode<1>();
-  if (e == hipSuccess) e = raise_lds_limits_mode<2>();
-#endif
-  if (e != hipSuccess) { h->err = "simulst_mma_decode: cannot raise the dynamic LDS limit of the layer chains"; return (int)e; }
-  h->dec_chain_lds_attr_set = true;
-  return SIMULST_OK;
-}
+static int raise_lds_limits(simulst_handle* h);      // below, behind the experiments' part of its list
 
 // the fragment-read mode of the handle (mma_unit) selects the instantiation
 // (a DEBUG_HOOKS build keeps the three other instantiations for the round-3 A/B experiments; the product has mode 3 only:
@@ -979,7 +954,7 @@ static int raise_lds_limits(simulst_handle* h) {
 #ifdef SL_EXPERIMENTS
 #include "experiments/dec_chain_launch.inc"
 #else
-template <int XM> static hipError_t exp_raise_lds_limits() { return hipSuccess; }
+#define SL_EXP_CHAIN_LDS_LIMITS(XM)
 static bool exp_proj_chain_rows32(simulst_handle*, const void*, void*, const void*, const float*, const float*, const float*, const void*,
                                   const float*, void*, const void*, const float*, void*, int, const void*) { return false; }
 static bool exp_ffn_chain_rows32(simulst_handle*, const void*, void*, const void*, const float*, const float*, const float*, const void*,
@@ -1008,6 +983,21 @@ int sl_dec_attn_proj_chain(simulst_handle* h, const void*, void*, void*, const i
   return SIMULST_E_ARG;
 }
 #endif
+
+// every chain kernel of one fragment-read mode asks for up to the whole CU's LDS (lds_request)
+#define SL_CHAIN_LDS_LIMITS(XM)                                                                                        \
+  {(const void*)dec_proj_chain_kernel<1, XM>, LDS_WHOLE_CU}, {(const void*)dec_ffn_chain_kernel<1, true, XM>, LDS_WHOLE_CU},          \
+  {(const void*)dec_ffn_chain_kernel<1, false, XM>, LDS_WHOLE_CU}, {(const void*)dec_qkv_chain_kernel<1, XM>, LDS_WHOLE_CU},          \
+  {(const void*)dec_vocab_chain_kernel<XM>, LDS_WHOLE_CU}, {(const void*)dec_embed_qkv_chain_kernel<XM>, LDS_WHOLE_CU},               \
+  SL_EXP_CHAIN_LDS_LIMITS(XM)
+static int raise_lds_limits(simulst_handle* h) {
+  static const sl_lds_limit limits[] = {SL_CHAIN_LDS_LIMITS(3)
+#ifdef SL_DEBUG_HOOKS
+                                        SL_CHAIN_LDS_LIMITS(0) SL_CHAIN_LDS_LIMITS(1) SL_CHAIN_LDS_LIMITS(2)
+#endif
+  };
+  return sl_raise_lds(h, SL_LDS_DEC_CHAIN, limits, "simulst_mma_decode(layer chains)");
+}
 
 int sl_dec_proj_chain(simulst_handle* h, const void* ctx, void* x, const void* Wo, const float* bo, const float* ln_g,
                       const float* ln_b, const void* Wq, const float* bq, void* q, const void* Wq2, const float* bq2,
@@ -1196,14 +1186,9 @@ extern "C" int simulst_debug_chain_probe(simulst_handle* h, const void* ctx, voi
   SL_CHECK_NULL(h, ctx); SL_CHECK_NULL(h, x); SL_CHECK_NULL(h, wo_fm); SL_CHECK_NULL(h, bo); SL_CHECK_NULL(h, ln_g);
   SL_CHECK_NULL(h, ln_b); SL_CHECK_NULL(h, wq_fm); SL_CHECK_NULL(h, bq); SL_CHECK_NULL(h, q); SL_CHECK_NULL(h, dbg);
   SL_REQUIRE(h, B > 0 && variant >= 0 && variant <= 3, SIMULST_E_ARG, "simulst_debug_chain_probe: variant 0..3");
-  if (!h->dec_chain_probe_attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)dec_proj_chain_probe_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_proj_chain_probe_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_proj_chain_probe_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_proj_chain_probe_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-    if (e != hipSuccess) { h->err = "simulst_debug_chain_probe: cannot raise the dynamic LDS limit"; return (int)e; }
-    h->dec_chain_probe_attr_set = true;
-  }
+  static const sl_lds_limit limits[] = {{(const void*)dec_proj_chain_probe_kernel<0>, LDS_WHOLE_CU}, {(const void*)dec_proj_chain_probe_kernel<1>, LDS_WHOLE_CU},
+                                        {(const void*)dec_proj_chain_probe_kernel<2>, LDS_WHOLE_CU}, {(const void*)dec_proj_chain_probe_kernel<3>, LDS_WHOLE_CU}};
+  if (int rc = sl_raise_lds(h, SL_LDS_DEC_CHAIN_PROBE, limits, "simulst_debug_chain_probe")) return rc;
 #define PK(V)                                                                                                          \
   hipLaunchKernelGGL((dec_proj_chain_probe_kernel<V>), dim3((B + 15) / 16), dim3(256), lds_request(h), h->stream,      \
                      (const bf16*)ctx, (bf16*)x, (const uint4*)wo_fm, bo, ln_g, ln_b, (const uint4*)wq_fm, bq, (bf16*)q, \

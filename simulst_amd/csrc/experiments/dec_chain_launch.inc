@@ -1,5 +1,5 @@
 // Launchers of csrc/dec_chain.hip's measured-slower forms (`make EXPERIMENTS=1` only; included by dec_chain.hip after its launch helpers
-// -- lds_request, SL_XMODE, SL_CHAIN_TAIL, raise_lds_limits -- and before the product launchers).  The product build has one-line stubs
+// -- lds_request, SL_XMODE, SL_CHAIN_TAIL, raise_lds_limits' declaration -- and before the product launchers).  The product build has one-line stubs
 // instead (dec_chain.hip), so no launch function of the product carries a build switch.
 
 // row tiles per workgroup of the projection / feed-forward / QKV chains: 2 (32 rows, round 5: a weight fragment serves two row tiles, half
@@ -9,14 +9,10 @@
 // the rows each stream as long and finish later.  EXPERIMENTS builds only, off.
 static int chain_rtl(const simulst_handle* h, int B) { return h->dec_chain_rows32 && B >= h->dec_chain_rows32_min ? 2 : 1; }
 
-template <int XM>
-static hipError_t exp_raise_lds_limits() {
-  hipError_t e = hipFuncSetAttribute((const void*)dec_ffn_qkv_chain_kernel<1, XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_proj_chain_kernel<2, XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_ffn_chain_kernel<2, false, XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_qkv_chain_kernel<2, XM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-  return e;
-}
+// this file's part of raise_lds_limits' list (dec_chain.hip), per fragment-read mode
+#define SL_EXP_CHAIN_LDS_LIMITS(XM)                                                                                    \
+  {(const void*)dec_ffn_qkv_chain_kernel<1, XM>, LDS_WHOLE_CU}, {(const void*)dec_proj_chain_kernel<2, XM>, LDS_WHOLE_CU},            \
+  {(const void*)dec_ffn_chain_kernel<2, false, XM>, LDS_WHOLE_CU}, {(const void*)dec_qkv_chain_kernel<2, XM>, LDS_WHOLE_CU},
 
 // the three chains on 32-row tiles: true = launched (the caller then skips its 16-row launch)
 static bool exp_proj_chain_rows32(simulst_handle* h, const void* ctx, void* x, const void* Wo, const float* bo, const float* ln_g,

@@ -31,12 +31,12 @@
 // Algorithmic work per launch: 4 * rows * D * F flop (two contractions), HBM bytes 2 * rows * D * 2 (x read for the
 // contraction, again for the residual: L2/MALL-hot) + rows * D * 2 written; weights 2 * D * F * 2 B from L2 per workgroup.
 #include "gemm_args.h"
+#include "ffn_variant.h"
 
 int sl_launch_qkv_rows(simulst_handle* h, const void* z, const void* wqkv_fm, const float* bqkv, void* qkv, int n_utt, int rows_z, int n_mem,
                        int sum0, int n_sum);
 int sl_launch_ffn_pipe(simulst_handle* h, const void* x, const float* ln_g, const float* ln_b, const void* w1p, const float* b1,
-                       const void* w2p, const float* b2, void* out, long rows, int F, int waves, int packed, int uniform,
-                       const sl_ffn_z* zout = nullptr);
+                       const void* w2p, const float* b2, void* out, long rows, int F, sl_ffn_variant v, const sl_ffn_z* zout = nullptr);
 
 namespace {
 
@@ -44,10 +44,6 @@ namespace {
 // and WAVES = 4 (256 threads, 128 rows, 32 hidden units per chunk, 75 KB of LDS: TWO workgroups per CU, which drift out
 // of phase, so that one's GELU arithmetic runs beside the other's MFMAs; each streams the weights for half as many rows).
 constexpr int FF_D = 256;             // model width (K of fc1, N of fc2)
-constexpr bool FF_DEFAULT_FOUR_WAVES = true;
-constexpr bool FF_PIPELINED_UNIFORM = true;   // ffn_pipe.hip UNI (SIMULST_OPT_FFN_WAVES = 43): a quarter of an element pair's GELU behind each of the 32 MFMAs of an iteration: 439 / 830 / 941 / 927 TFLOP/s at 64 / 256 / 1280 / 4096 utterances against 394 / 743 / 889 / 881 for the phase form (41) on the same device
-constexpr bool FF_PIPELINED_PACKED = false;   // packed GELU inside the MFMA stream measured SLOWER (826 vs 887 TFLOP/s): an anti-lever beside MFMAs
-constexpr bool FF_DEFAULT_PIPELINED = true;   // ffn_pipe.hip, 4 waves: 804 / 887 / 875 TFLOP/s at 448 / 1280 / 4096 utterances against 758 / 863 / 851     // ffn_pipe.hip: SIMULST_OPT_FFN_WAVES = 41 selects it
 template <int WAVES> struct FFG {
   static constexpr int THREADS = 64 * WAVES;
   static constexpr int ROWS = 32 * WAVES;            // rows per workgroup
@@ -59,6 +55,7 @@ template <int WAVES> struct FFG {
   static constexpr int MAX_F = WAVES == 8 ? 4096 : 2048;   // fc1 bias lives in LDS
   static constexpr int LDS = 2 * CHUNK_BYTES + 3072 + MAX_F * 4;
 };
+static_assert(FFG<4>::MAX_F == SL_FFN_BLOCK4_MAX_F, "ffn_variant.h decides the block form's geometry");
 constexpr int FF_PF = 4;               // weight fragments requested ahead of the MFMA that consumes them
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -247,35 +244,24 @@ extern "C" int simulst_emformer_ffn(simulst_handle* h, const void* x, const floa
   SL_REQUIRE(h, F <= FFG<8>::MAX_F, SIMULST_E_SHAPE, "simulst_emformer_ffn: F <= 4096");
   SL_REQUIRE(h, x != out, SIMULST_E_ARG, "simulst_emformer_ffn: in place (the residual rows are re-read at the end)");
   if (rows <= 0) return SIMULST_OK;
-  if (!h->ffn_lds_attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)ffn_fused_kernel<0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, FFG<8>::LDS);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)ffn_fused_kernel<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, FFG<4>::LDS);
+  static const sl_lds_limit limits[] = {
+      {(const void*)ffn_fused_kernel<0, 8>, FFG<8>::LDS}, {(const void*)ffn_fused_kernel<0, 4>, FFG<4>::LDS},
 #ifdef SL_DEBUG_HOOKS
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)ffn_fused_kernel<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, FFG<8>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_fused_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, FFG<4>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_fused_kernel<3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, FFG<4>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_fused_kernel<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, FFG<4>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_fused_kernel<5, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, FFG<4>::LDS);
+      {(const void*)ffn_fused_kernel<1, 8>, FFG<8>::LDS}, {(const void*)ffn_fused_kernel<2, 4>, FFG<4>::LDS},
+      {(const void*)ffn_fused_kernel<3, 4>, FFG<4>::LDS}, {(const void*)ffn_fused_kernel<4, 4>, FFG<4>::LDS},
+      {(const void*)ffn_fused_kernel<5, 4>, FFG<4>::LDS},
 #endif
-    if (e != hipSuccess) { h->err = "simulst_emformer_ffn: cannot raise the dynamic LDS limit"; return (int)e; }
-    h->ffn_lds_attr_set = true;
-  }
+  };
+  if (int rc = sl_raise_lds(h, SL_LDS_FFN, limits, "simulst_emformer_ffn")) return rc;
   KTimer t(h, SIMULST_K_LINEAR);
-  // the software-pipelined form (ffn_pipe.hip: GELU inside the matrix-core stream): 128 rows per workgroup, two workgroups per CU
-  // SIMULST_OPT_FFN_WAVES 41 / 81: scalar GELU, 4 / 8 waves; 42 / 82: packed GELU
-  if (((h->ffn_waves >= 41 && h->ffn_waves <= 47) || (h->ffn_waves >= 81 && h->ffn_waves <= 87) || (h->ffn_waves == 0 && FF_DEFAULT_PIPELINED)) && F <= 2048)
-    return sl_launch_ffn_pipe(h, x, ln_gamma, ln_beta, w1_packed, b1, w2_packed, b2, out, rows, F, h->ffn_waves >= 81 ? 8 : 4,
-                              h->ffn_waves == 0 ? FF_PIPELINED_PACKED : (h->ffn_waves % 10) == 2,
-                              h->ffn_waves == 0 ? FF_PIPELINED_UNIFORM : (h->ffn_waves == 45 ? 2 : (h->ffn_waves % 10) == 7 ? 3 : (h->ffn_waves % 10) == 3));
+  // SIMULST_OPT_FFN_WAVES (0: the library's choice): the software-pipelined form (ffn_pipe.hip: GELU inside the matrix-core stream,
+  // 128 rows per workgroup, two workgroups per CU) while F <= 2048, else the block form below
+  const sl_ffn_variant v = sl_decode_ffn_variant(h->ffn_waves, F);
+  if (v.pipelined) return sl_launch_ffn_pipe(h, x, ln_gamma, ln_beta, w1_packed, b1, w2_packed, b2, out, rows, F, v);
 #define FFN(V, W)                                                                                                  \
   hipLaunchKernelGGL((ffn_fused_kernel<V, W>), dim3((unsigned)((rows + FFG<W>::ROWS - 1) / FFG<W>::ROWS)),         \
                      dim3(FFG<W>::THREADS), FFG<W>::LDS, h->stream, (const bf16*)x, ln_gamma, ln_beta,             \
                      (const bf16*)w1_packed, b1, (const bf16*)w2_packed, b2, (bf16*)out, (long)rows, F)
-  // geometry: two 4-wave workgroups per CU when the fc1 bias fits their LDS budget (F <= 2048), else one 8-wave workgroup
-  // (SIMULST_OPT_FFN_WAVES forces one of the two)
-  const bool four = h->ffn_waves == 4 || (h->ffn_waves == 0 && FF_DEFAULT_FOUR_WAVES);
 #ifdef SL_DEBUG_HOOKS
   // simulst_debug_ffn_variant: timing ablations, results are NOT the operator's
   if (h->ffn_variant == 1) FFN(1, 8);            // no GELU arithmetic (8 waves)
@@ -285,7 +271,7 @@ extern "C" int simulst_emformer_ffn(simulst_handle* h, const void* x, const floa
   else if (h->ffn_variant == 15) FFN(5, 4);      //   no GELU
   else
 #endif
-  if (four && F <= FFG<4>::MAX_F) FFN(0, 4);
+  if (v.waves == 4) FFN(0, 4);
   else FFN(0, 8);
 #undef FFN
   return sl_launch_status(h, "simulst_emformer_ffn");
@@ -317,7 +303,7 @@ static int ffn_prenorm_launch(simulst_handle* h, const char* who, const void* x,
   z.Z = (bf16*)z_next; z.g = next_gamma; z.b = next_beta; z.lengths = lengths;
   z.rows_x = n_rc + T; z.T = T; z.n_mem = n_mem; z.n_rc = n_rc; z.n_sum = n_sum; z.tiles = (z.rows_x + 127) / 128;
   z.Wqkv = (const bf16*)wqkv_fm; z.bqkv = bqkv; z.QKV = (bf16*)qkv_next;
-  return sl_launch_ffn_pipe(h, x, ln_gamma, ln_beta, w1_packed, b1, w2_packed, b2, out, (long)B * z.rows_x, F, 4, 0, 1, &z);
+  return sl_launch_ffn_pipe(h, x, ln_gamma, ln_beta, w1_packed, b1, w2_packed, b2, out, (long)B * z.rows_x, F, sl_decode_ffn_variant(0, F), &z);
 }
 
 extern "C" int simulst_emformer_ffn_prenorm(simulst_handle* h, const void* x, const float* ln_gamma, const float* ln_beta,

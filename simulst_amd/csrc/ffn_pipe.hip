@@ -2,6 +2,7 @@
 // Compiled WITHOUT the SLP vectoriser (Makefile): it re-packs the per-element scalar GELU of four neighbouring elements into packed
 // fp32 instructions and emits them as one block per four MFMAs, undoing the placement pinned in the source.
 #include "gemm_args.h"
+#include "ffn_variant.h"
 #include <type_traits>
 #include <cstdio>
 #include <vector>
@@ -972,36 +973,27 @@ __global__ __launch_bounds__(256, 1) void ffn_wide_kernel(
 }  // namespace
 
 int sl_launch_ffn_pipe(simulst_handle* h, const void* x, const float* ln_g, const float* ln_b, const void* w1p, const float* b1,
-                       const void* w2p, const float* b2, void* out, long rows, int F, int waves, int packed, int uniform,
-                       const sl_ffn_z* zout) {
-  // the packed-GELU instantiations (measured slower: 826 vs 887 TFLOP/s at 1280 utterances) exist in DEBUG_HOOKS builds only
-#ifndef SL_DEBUG_HOOKS
-  packed = 0;
-#endif
-  // the shipped form: 4 waves, a quarter of an element pair's GELU behind each of the 32 MFMAs of an iteration (SIMULST_OPT_FFN_WAVES 43);
-  // the 8-wave, phase and 64-rows-per-wave forms measured slower and exist in EXPERIMENTS builds (41 / 45 / 81 / 83; 42 / 82 DEBUG_HOOKS)
-#ifndef SL_EXPERIMENTS
-  waves = 4; uniform = 1;
-#endif
-  if (!h->ffn_pipe_lds_attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<4, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<4>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<4, false, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<4>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<4, false, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<4>::LDS);
+                       const void* w2p, const float* b2, void* out, long rows, int F, sl_ffn_variant v, const sl_ffn_z* zout) {
+  // (ffn_variant.h has already mapped forms this build lacks onto the shipped one: 4 waves, a quarter of an element pair's GELU behind
+  // each of the 32 MFMAs of an iteration, SIMULST_OPT_FFN_WAVES 43)
+  static const sl_lds_limit limits[] = {
+      {(const void*)ffn_pipe_kernel<4, false, true, true>, FPG<4>::LDS},
+      {(const void*)ffn_pipe_kernel<4, false, true, true, true>, FPG<4>::LDS},
+      {(const void*)ffn_pipe_kernel<4, false, true, true, true, true>, FPG<4>::LDS},
 #ifdef SL_EXPERIMENTS
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<4, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<4>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<4, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<4>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<8, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<8>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<8>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_wide_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, FWG::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<8, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<8>::LDS);
+      {(const void*)ffn_pipe_kernel<4, false, true, false>, FPG<4>::LDS},
+      {(const void*)ffn_pipe_kernel<4, false, false>, FPG<4>::LDS},
+      {(const void*)ffn_pipe_kernel<8, false, false>, FPG<8>::LDS},
+      {(const void*)ffn_pipe_kernel<8, false, true>, FPG<8>::LDS},
+      {(const void*)ffn_wide_kernel<2>, FWG::LDS},
+      {(const void*)ffn_pipe_kernel<8, false, true, true>, FPG<8>::LDS},
 #endif
 #ifdef SL_DEBUG_HOOKS
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<4, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<4>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ffn_pipe_kernel<8, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FPG<8>::LDS);
+      {(const void*)ffn_pipe_kernel<4, true, false>, FPG<4>::LDS},
+      {(const void*)ffn_pipe_kernel<8, true, false>, FPG<8>::LDS},
 #endif
-    if (e != hipSuccess) { h->err = "simulst_emformer_ffn: cannot raise the dynamic LDS limit (pipelined form)"; return (int)e; }
-    h->ffn_pipe_lds_attr_set = true;
-  }
+  };
+  if (int rc = sl_raise_lds(h, SL_LDS_FFN_PIPE, limits, "simulst_emformer_ffn(pipelined)")) return rc;
   if (zout) {      // the shipped form with the next layer's LayerNorm + summaries in its epilogue; workgroups tile each utterance
     const long nb = rows / zout->rows_x;
     if (zout->QKV)
@@ -1017,24 +1009,25 @@ int sl_launch_ffn_pipe(simulst_handle* h, const void* x, const float* ln_g, cons
   hipLaunchKernelGGL((ffn_pipe_kernel<W, P, U, ##__VA_ARGS__>), dim3((unsigned)((rows + 32 * W - 1) / (32 * W))), dim3(64 * W), FPG<W>::LDS, h->stream, \
                      (const bf16*)x, ln_g, ln_b, (const bf16*)w1p, b1, (const bf16*)w2p, b2, (bf16*)out, rows, F, noz)
 #ifdef SL_DEBUG_HOOKS
-  if (packed) { if (waves == 8) FPL(8, true, false); else FPL(4, true, false); } else
+  if (v.packed) { if (v.waves == 8) FPL(8, true, false); else FPL(4, true, false); } else
 #endif
 #ifdef SL_EXPERIMENTS
-  if (uniform == 2) {
+  if (v.uniform == 2) {
     hipLaunchKernelGGL((ffn_wide_kernel<2>), dim3((unsigned)((rows + 255) / 256)), dim3(256), FWG::LDS, h->stream, (const bf16*)x, ln_g, ln_b,
                        (const bf16*)w1p, b1, (const bf16*)w2p, b2, (bf16*)out, rows, F);
   } else
   // 43: the shipped form (uniform GELU, LDS-DMA pieces one per MFMA gap); 47: the same with the pieces as a burst behind the barrier;
   // 83 / 87: 8 waves, burst / spread
-  if (uniform == 3) { if (waves == 8) FPL(8, false, true, true); else FPL(4, false, true, false); }
-  else if (uniform) { if (waves == 8) FPL(8, false, true, false); else FPL(4, false, true, true); }
-  else { if (waves == 8) FPL(8, false, false); else FPL(4, false, false); }
+  if (v.uniform == 3) { if (v.waves == 8) FPL(8, false, true, true); else FPL(4, false, true, false); }
+  else if (v.uniform) { if (v.waves == 8) FPL(8, false, true, false); else FPL(4, false, true, true); }
+  else { if (v.waves == 8) FPL(8, false, false); else FPL(4, false, false); }
 #else
   FPL(4, false, true, true);
 #endif
 #undef FPL
 #ifdef SL_PROBE
   {
+    const int waves = v.waves, packed = v.packed;
     static int calls[4] = {0, 0, 0, 0};
     if ((++calls[(waves == 8) * 2 + (packed != 0)] % 8) == 0) {
       (void)hipStreamSynchronize(h->stream);
@@ -1060,12 +1053,9 @@ int sl_launch_ffn_pipe(simulst_handle* h, const void* x, const float* ln_g, cons
 int sl_launch_qkv_rows(simulst_handle* h, const void* z, const void* wqkv_fm, const float* bqkv, void* qkv, int n_utt, int rows_z, int n_mem,
                        int sum0, int n_sum) {
   const int tiles = (n_mem + n_sum + 31) / 32;
-  const size_t lds = (size_t)4 * FP_W + 768 * sizeof(float);
-  if (!h->qkv_rows_lds_attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)qkv_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { h->err = "simulst_emformer_qkv_mem_sum: cannot raise the dynamic LDS limit"; return (int)e; }
-    h->qkv_rows_lds_attr_set = true;
-  }
+  constexpr size_t lds = (size_t)4 * FP_W + 768 * sizeof(float);
+  static const sl_lds_limit limits[] = {{(const void*)qkv_rows_kernel, (int)lds}};
+  if (int rc = sl_raise_lds(h, SL_LDS_QKV_ROWS, limits, "simulst_emformer_qkv_mem_sum")) return rc;
   const long waves = (long)n_utt * tiles;
   hipLaunchKernelGGL(qkv_rows_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, h->stream, (const bf16*)z, (const bf16*)wqkv_fm, bqkv,
                      (bf16*)qkv, n_utt, rows_z, n_mem, sum0, n_sum, tiles);

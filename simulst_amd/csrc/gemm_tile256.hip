@@ -291,17 +291,10 @@ __global__ __launch_bounds__(512, 1) void tile256_ring_kernel(const bf16* __rest
 }  // namespace
 
 int sl_launch_tile256(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
-  const void* kernel = pl.ring ? (const void*)tile256_ring_kernel : (const void*)tile256_glu_kernel;
-  bool& attr_set = pl.ring ? h->tile256_ring_attr_set : h->tile256_lds_attr_set;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      h->err = std::string(pl.ring ? "simulst_linear(256 x 256 tiles, ring)" : "simulst_linear(256 x 256 tiles)") +
-               ": cannot raise the dynamic LDS limit: " + hipGetErrorString(e);
-      return (int)e;
-    }
-    attr_set = true;
-  }
+  static const sl_lds_limit ring[] = {{(const void*)tile256_ring_kernel, 160 * 1024}}, staged[] = {{(const void*)tile256_glu_kernel, 160 * 1024}};
+  if (int rc = pl.ring ? sl_raise_lds(h, SL_LDS_TILE256_RING, ring, "simulst_linear(256 x 256 tiles, ring)")
+                       : sl_raise_lds(h, SL_LDS_TILE256, staged, "simulst_linear(256 x 256 tiles)"))
+    return rc;
   KTimer t(h, pl.timer);
   if (pl.ring) {                                                     // the LDS-DMA ring (round 6)
     hipLaunchKernelGGL(tile256_ring_kernel, dim3(pl.grid[0]), dim3(512), pl.lds, h->stream, (const bf16*)o.A, (const bf16*)o.W, o.bias, (bf16*)o.C, p);

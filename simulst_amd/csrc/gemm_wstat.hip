@@ -127,13 +127,10 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wstat_kernel(const bf16* __rest
 }  // namespace
 
 int sl_launch_wstat(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
-  if (!h->wstat_lds_attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wstat_kernel<SIMULST_EPI_BIAS, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wstat_kernel<SIMULST_EPI_BIAS, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wstat_kernel<SIMULST_EPI_EMF_OUT, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { h->err = std::string("simulst_linear(weight-stationary): cannot raise the dynamic LDS limit: ") + hipGetErrorString(e); return (int)e; }
-    h->wstat_lds_attr_set = true;
-  }
+  static const sl_lds_limit limits[] = {{(const void*)wstat_kernel<SIMULST_EPI_BIAS, 8>, 160 * 1024},
+                                        {(const void*)wstat_kernel<SIMULST_EPI_BIAS, 6>, 160 * 1024},
+                                        {(const void*)wstat_kernel<SIMULST_EPI_EMF_OUT, 8>, 160 * 1024}};
+  if (int rc = sl_raise_lds(h, SL_LDS_WSTAT, limits, "simulst_linear(weight-stationary)")) return rc;
   KTimer t(h, pl.timer);
 #define WSTAT(E, P) hipLaunchKernelGGL((wstat_kernel<E, P>), dim3(pl.grid[0]), dim3(WS_THREADS), pl.lds, h->stream, (const bf16*)o.A, (const bf16*)o.W, \
                                       o.bias, (const bf16*)o.R, (bf16*)o.C, (bf16*)o.aux, p, pl.n_slices)

@@ -1,6 +1,7 @@
 // Handle lifecycle + timers of libsimulst_hip.so.
-#include "common.h"
+#include "ffn_variant.h"
 #include <cstdlib>
+#include <initializer_list>
 
 // 100: rounds 1-2.  103: round 3 -- simulst_linear_desc, simulst_stream_ctl and simulst_cif_stream_ctl grew at their ends
 // (c_tensor_heads / c_tensor_stride; the chunk schedules of self-paced rows), simulst_decoder_desc gained P_cap.
@@ -9,126 +10,124 @@
 // 105: round 5 -- simulst_get_option (what a handle actually runs with, for the roofline models of bench.py).
 // 106: round 6 -- simulst_emformer_ffn_prenorm (the next layer's LayerNorm + summaries in the feed-forward launch); no structure changed.
 // 107: round 6 -- simulst_stream_ctl grew row_map / compact_rows (active-row compaction of simulst_mma_stream_steps).
-// 108: round 6 -- simulst_emformer_ffn_prenorm_qkv (... and the next layer's Q | K | V projection of the rc | utterance rows); no structure changed.
+// 108: round 6 -- simulst_emformer_ffn_prenorm_qkv (... and the next layer's Q | K | V projection of the rc | utterance rows) and
+// simulst_emformer_qkv_mem_sum; no structure changed.
 extern "C" int simulst_version(void) { return 108; }
+
+// ---- the tunables: one row each ---------------------------------------------------------------------------------------------------
+// Run-time options of a handle: path selection (each alternative is a complete, valid implementation -- the tests use them for
+// A/B parity) and the tuning values that simulst_create reads from the environment.  A new tunable is a member of simulst_handle
+// with its default (common.h), a row here and, if it is an option, its id in the header's enum.
+//   env_ok / set_ok: the values the environment / simulst_set_option may give it; none: any (atoi of the text, as it is).  The
+//   environment ignores a value outside, simulst_set_option refuses it with `refusal`.  A `flag` is stored as value != 0.
+//   flavour: the build that has it (common.h); elsewhere the environment is not read and simulst_set_option refuses.
+// Not rows, because they are not one value in one member: SIMULST_DEC_TALL_MIN_ROWS (its default depends on another row),
+// PANEL_WIDE (one value, two members) and what simulst_get_option(DEC_FUSE_PROJ_CROSS) adds from the device.
+namespace {
+
+typedef bool (*legal_fn)(int);
+bool one_of(int v, std::initializer_list<int> set) {
+  for (int s : set) if (s == v) return true;
+  return false;
+}
+#define ONE_OF(...) [](int v) { return one_of(v, {__VA_ARGS__}); }
+#define RANGE(lo, hi) [](int v) { return v >= (lo) && v <= (hi); }
+constexpr legal_fn ANY = nullptr;
+constexpr legal_fn VOCAB_SPLITS = ONE_OF(0, 1, 2, 4, 8, 16);
+constexpr legal_fn TILE256_FORMS = RANGE(0, 2);
+constexpr legal_fn NOT_NEGATIVE = [](int v) { return v >= 0; };
+constexpr int NO_OPTION = -1;
+constexpr int EXP = SL_EXPERIMENTS_BUILD, DBG = SL_DEBUG_HOOKS_BUILD;
+
+struct tunable {
+  int option;
+  const char* env;
+  int simulst_handle::*member;
+  bool flag;
+  legal_fn env_ok, set_ok;
+  int flavour;
+  const char* refusal;
+};
+
+#define M(name) &simulst_handle::name
+const tunable TUNABLES[] = {
+    {SIMULST_OPT_VALU_ATTENTION, nullptr, M(force_valu_attention), true, ANY, ANY, SL_PRODUCT, ""},
+    {SIMULST_OPT_UNFUSED_DECODE, nullptr, M(force_unfused_decode), true, ANY, ANY, SL_PRODUCT, ""},
+    {SIMULST_OPT_FFN_WAVES, nullptr, M(ffn_waves), false, ANY, [](int v) { return sl_ffn_code_legal(v); }, SL_PRODUCT,
+#ifdef SL_EXPERIMENTS
+     "simulst_set_option(FFN_WAVES): 0 (the library's choice), 4 / 8 (GELU as a block between the products), 41 / 81 (GELU inside the "
+     "MFMA stream, 4 / 8 waves; 42 / 82: packed GELU, DEBUG_HOOKS builds only), 43 / 83 (GELU spread over all 32 MFMAs; 47 / 87: LDS-DMA "
+     "pieces as a burst / spread), 45 (64 rows per wave)"},
+#else
+     "simulst_set_option(FFN_WAVES): 0 (the library's choice: 43 while F <= 2048), 43 (GELU inside the MFMA stream), 4 / 8 (the block form "
+     "with that many waves: GELU between the two products); the measured-slower forms exist in EXPERIMENTS builds"},
+#endif
+    {NO_OPTION, "SIMULST_PANEL_SPLIT_MIN_ROWS", M(panel_split_min_rows), false, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_PANEL_SPLIT_BLOCKS", M(panel_split_blocks), false, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_MID_MIN_BLOCKS", M(mid_min_blocks), false, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_MID_NARROW_MIN_ROWS", M(mid_narrow_min_rows), false, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_SKINNY_MIN_BLOCKS_TALL", M(skinny_min_blocks_tall), false, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_FUSE_Q_MAX_ROWS", M(fuse_q_max_rows), false, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_EA_GENERAL", M(ea_general_only), true, ANY, ANY, SL_PRODUCT, ""},
+    {SIMULST_OPT_DEC_CHAIN, "SIMULST_DEC_CHAIN", M(dec_chain_on), true, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_DEC_CHAIN_MIN_ROWS", M(dec_chain_min_rows), false, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_DEC_CHAIN_MAX_ROWS", M(dec_chain_max_rows), false, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_DEC_CHAIN_FFN_MAX_ROWS", M(dec_chain_ffn_max_rows), false, ANY, ANY, SL_PRODUCT, ""},
+    {SIMULST_OPT_DEC_TALL_FFN, "SIMULST_DEC_TALL_FFN", M(dec_tall_ffn), true, ANY, ANY, SL_PRODUCT, ""},
+    // investigation knobs (xmode: bitmask, bit 0 hoisted fragment reads, bit 1 DPP reductions; LDS request up to the CU's 160 KB)
+    {NO_OPTION, "SIMULST_DEC_CHAIN_XMODE", M(dec_chain_xmode), false, RANGE(0, 3), ANY, DBG, ""},
+    {NO_OPTION, "SIMULST_DEC_CHAIN_LDS_BYTES", M(dec_chain_lds_bytes), false, RANGE(0, 160 * 1024), ANY, DBG, ""},
+    {SIMULST_OPT_DEC_ATTN_CHAIN_MAX_ROWS, "SIMULST_DEC_ATTN_CHAIN_MAX_ROWS", M(dec_attn_chain_max_rows), false, ANY, NOT_NEGATIVE, EXP,
+     "simulst_set_option(DEC_ATTN_CHAIN_MAX_ROWS): >= 0; self-attention inside the projection chain exists in EXPERIMENTS builds only (measured slower)"},
+    {SIMULST_OPT_DEC_ATTN_CHAIN_ROWS, "SIMULST_DEC_ATTN_CHAIN_ROWS", M(dec_attn_chain_rows), false, ONE_OF(4, 8, 16), ONE_OF(0, 4, 8, 16), EXP,
+     "simulst_set_option(DEC_ATTN_CHAIN_ROWS): 0, 4, 8 or 16; self-attention inside the projection chain exists in EXPERIMENTS builds only (measured slower)"},
+    {SIMULST_OPT_FUSED_ARGMAX, "SIMULST_FUSED_ARGMAX", M(fused_argmax), true, ANY, ANY, SL_PRODUCT, ""},
+    {SIMULST_OPT_DEC_VOCAB_CHAIN_SPLIT, "SIMULST_DEC_VOCAB_CHAIN_SPLIT", M(dec_vocab_chain_split), false, VOCAB_SPLITS, VOCAB_SPLITS, SL_PRODUCT,
+     "simulst_set_option(DEC_VOCAB_CHAIN_SPLIT): 0 (off), 1, 2, 4, 8 or 16"},
+    {SIMULST_OPT_DEC_EMBED_QKV_CHAIN, "SIMULST_DEC_EMBED_QKV_CHAIN", M(dec_embed_qkv_chain), true, ANY, ANY, SL_PRODUCT, ""},
+    {SIMULST_OPT_DEC_CHAIN_ROWS32, "SIMULST_DEC_CHAIN_ROWS32", M(dec_chain_rows32), true, ANY, ANY, EXP,
+     "simulst_set_option(DEC_CHAIN_ROWS32): 0 or 1; the layer chains on 32-row tiles exist in EXPERIMENTS builds only (measured slower)"},
+    {NO_OPTION, "SIMULST_DEC_CHAIN_ROWS32_MIN", M(dec_chain_rows32_min), false, ANY, ANY, EXP, ""},
+    {SIMULST_OPT_DEC_FUSE_FFN_QKV, "SIMULST_DEC_FUSE_FFN_QKV", M(dec_fuse_ffn_qkv), true, ANY, ANY, EXP,
+     "simulst_set_option(DEC_FUSE_FFN_QKV): 0 or 1; the feed-forward chain + next layer's QKV in one launch exists in EXPERIMENTS builds only (measured slower)"},
+    {SIMULST_OPT_DEC_FUSE_PROJ_CROSS, "SIMULST_DEC_FUSE_PROJ_CROSS", M(dec_fuse_proj_cross), true, ANY, ANY, EXP,
+     "simulst_set_option(DEC_FUSE_PROJ_CROSS): 0 or 1; the one-launch projection chain + cross-attention exists in EXPERIMENTS builds only (measured slower)"},
+    {SIMULST_OPT_CONV_TILE256, "SIMULST_CONV_TILE256", M(tile256), false, TILE256_FORMS, TILE256_FORMS, SL_PRODUCT,
+     "simulst_set_option(CONV_TILE256): 0 (128 x 128 tiles), 1 (256 x 256, register stage), 2 (256 x 256, LDS-DMA ring)"},
+    {SIMULST_OPT_WEIGHT_STATIONARY, "SIMULST_WEIGHT_STATIONARY", M(wstat), true, ANY, ANY, SL_PRODUCT, ""},
+    {NO_OPTION, "SIMULST_POLICY_LDS_BYTES", M(policy_lds_bytes), false, RANGE(0, 64 * 1024), ANY, SL_PRODUCT, ""},
+};
+#undef M
+
+bool in_this_build(const tunable& t) { return (t.flavour & SL_BUILD_FLAVOUR) == t.flavour; }
+const tunable* find_option(int option) {
+  for (const tunable& t : TUNABLES) if (t.option == option) return &t;
+  return nullptr;
+}
+
+}  // namespace
 
 extern "C" int simulst_create(simulst_handle** out, void* hip_stream) {
   if (!out) return SIMULST_E_NULL;
   simulst_handle* h = new (std::nothrow) simulst_handle();
   if (!h) return SIMULST_E_ARG;
   h->stream = (hipStream_t)hip_stream;
-  h->ev_used = 0;
-  h->ws = nullptr;
-  h->ws_bytes = 0;
-  h->graph_on = false;
-  h->capturing = false;
-  h->force_valu_attention = false;
-  h->force_unfused_decode = false;
-  h->panel_split_min_rows = 2560;
-  if (const char* e = getenv("SIMULST_PANEL_SPLIT_MIN_ROWS")) h->panel_split_min_rows = atoi(e);
-  h->panel_split_blocks = 256;
-  if (const char* e = getenv("SIMULST_PANEL_SPLIT_BLOCKS")) h->panel_split_blocks = atoi(e);
-  h->mid_min_blocks = 48;      // measured with three 448-row sequences in flight (bench.py --steps 20): 192 -> 1.25 M, <= 64 -> 1.29-1.30 M tokens/s
-  if (const char* e = getenv("SIMULST_MID_MIN_BLOCKS")) h->mid_min_blocks = atoi(e);
-  h->mid_narrow_min_rows = 3072;
-  if (const char* e = getenv("SIMULST_MID_NARROW_MIN_ROWS")) h->mid_narrow_min_rows = atoi(e);
-  h->skinny_min_blocks_tall = 192;
-  if (const char* e = getenv("SIMULST_SKINNY_MIN_BLOCKS_TALL")) h->skinny_min_blocks_tall = atoi(e);
-  h->fuse_q_max_rows = 128;
-  if (const char* e = getenv("SIMULST_FUSE_Q_MAX_ROWS")) h->fuse_q_max_rows = atoi(e);
-  h->dec_chain_on = true;
-  if (const char* e = getenv("SIMULST_DEC_CHAIN")) h->dec_chain_on = atoi(e) != 0;
-  h->dec_chain_min_rows = 129;
-  if (const char* e = getenv("SIMULST_DEC_CHAIN_MIN_ROWS")) h->dec_chain_min_rows = atoi(e);
-  h->dec_chain_max_rows = 1 << 30;
-  if (const char* e = getenv("SIMULST_DEC_CHAIN_MAX_ROWS")) h->dec_chain_max_rows = atoi(e);
-  h->dec_chain_ffn_max_rows = 1024;     // measured (bench.py --steps 20): 448-row sequences +4 %, 640 +2 %, 1280 -2 %, 4096 -3 %
-  if (const char* e = getenv("SIMULST_DEC_CHAIN_FFN_MAX_ROWS")) h->dec_chain_ffn_max_rows = atoi(e);
-  h->dec_tall_ffn = true;
-  if (const char* e = getenv("SIMULST_DEC_TALL_FFN")) h->dec_tall_ffn = atoi(e) != 0;
-  h->dec_tall_min_rows = h->dec_chain_ffn_max_rows + 1;      // where the feed-forward chain ends
-  if (const char* e = getenv("SIMULST_DEC_TALL_MIN_ROWS")) h->dec_tall_min_rows = atoi(e);
-  h->dec_chain_lds_attr_set = false;
-  h->dec_chain_probe_attr_set = false;
-  h->dec_chain_lds_bytes = 0;
-  h->dec_chain_xmode = 3;      // fragments hoisted + LayerNorm reductions on the DPP path: 1.378 -> 1.401 M tokens/s in the driver form
-  h->dec_chain_tail = nullptr;
-#ifdef SL_DEBUG_HOOKS
-  // investigation knobs (bitmask 0..3: bit 0 hoisted fragment reads, bit 1 DPP reductions; LDS request up to the CU's 160 KB):
-  // out-of-range values are ignored, like the simulst_debug_* setters refuse them
-  if (const char* e = getenv("SIMULST_DEC_CHAIN_XMODE")) { const int v = atoi(e); if (v >= 0 && v <= 3) h->dec_chain_xmode = v; }
-  if (const char* e = getenv("SIMULST_DEC_CHAIN_LDS_BYTES")) { const int v = atoi(e); if (v >= 0 && v <= 160 * 1024) h->dec_chain_lds_bytes = v; }
-#endif
-  h->dec_attn_chain_max_rows = 0;      // OFF: measured slower than the two launches at every cache length (dec_chain.hip)
-#ifdef SL_EXPERIMENTS
-  if (const char* e = getenv("SIMULST_DEC_ATTN_CHAIN_MAX_ROWS")) h->dec_attn_chain_max_rows = atoi(e);
-#endif
-  h->dec_attn_chain_rows = 0;
-  // the decode step's closing launch (dec_chain.hip dec_vocab_chain_kernel), workgroups per 16-row tile.  Driver form at 448-row sequences
-  // (bench.py --steps 20, two rounds each): off 1.490 / 1.497 M tokens/s, 1: 1.474, 2: 1.500 / 1.492, 4: 1.515 / 1.514 / 1.504, 8: 1.498 / 1.504 /
-  // 1.503, 16: 1.500; one sequence alone 50.2-50.4 ms with 4 or 8 against 50.6-50.7 ms
-  h->dec_vocab_chain_split = 4;
-  if (const char* e = getenv("SIMULST_DEC_VOCAB_CHAIN_SPLIT")) { const int v = atoi(e); if (v == 0 || v == 1 || v == 2 || v == 4 || v == 8 || v == 16) h->dec_vocab_chain_split = v; }
-  h->dec_embed_qkv_chain = true;
-  if (const char* e = getenv("SIMULST_DEC_EMBED_QKV_CHAIN")) h->dec_embed_qkv_chain = atoi(e) != 0;
-  h->dec_chain_rows32 = false;        // experiment, off (dec_chain.hip chain_rtl)
-  h->dec_chain_rows32_min = 256;
-#ifdef SL_EXPERIMENTS
-  if (const char* e = getenv("SIMULST_DEC_CHAIN_ROWS32")) h->dec_chain_rows32 = atoi(e) != 0;
-  if (const char* e = getenv("SIMULST_DEC_CHAIN_ROWS32_MIN")) h->dec_chain_rows32_min = atoi(e);
-#endif
-  h->dec_fuse_ffn_qkv = false;        // experiment, off
-#ifdef SL_EXPERIMENTS
-  if (const char* e = getenv("SIMULST_DEC_FUSE_FFN_QKV")) h->dec_fuse_ffn_qkv = atoi(e) != 0;
-#endif
-  h->chain_sem = nullptr;
-  h->chain_sem_splits = 0;
-  h->tile256 = 2;
-  if (const char* e = getenv("SIMULST_CONV_TILE256")) { const int v = atoi(e); if (v >= 0 && v <= 2) h->tile256 = v; }
-  h->tile256_lds_attr_set = false;
-  h->tile256_ring_attr_set = false;
-  h->wstat = true;
-  if (const char* e = getenv("SIMULST_WEIGHT_STATIONARY")) h->wstat = atoi(e) != 0;
-  h->wstat_lds_attr_set = false;
-  {
-    int dev = 0, n = 0;
-    // a failed query leaves 0: the persistent one-workgroup-per-CU kernels (gemm_wstat.hip) then decline and the row panels run
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 0;
-    h->n_cus = n;
+  for (const tunable& t : TUNABLES) {
+    const char* e = t.env && in_this_build(t) ? getenv(t.env) : nullptr;
+    if (!e) continue;
+    const int v = atoi(e);
+    if (!t.env_ok || t.env_ok(v)) h->*t.member = t.flag ? v != 0 : v;
   }
-  h->panel_wide = true;
-  h->panel_wide_plain_stores = false;
+  const char* tall = getenv("SIMULST_DEC_TALL_MIN_ROWS");
+  h->dec_tall_min_rows = tall ? atoi(tall) : h->dec_chain_ffn_max_rows + 1;      // where the feed-forward chain ends
   if (const char* e = getenv("SIMULST_PANEL_WIDE")) {
     h->panel_wide = atoi(e) != 0;
-#ifdef SL_EXPERIMENTS
-    h->panel_wide_plain_stores = atoi(e) == 2;
-#endif
+    h->panel_wide_plain_stores = (SL_BUILD_FLAVOUR & SL_EXPERIMENTS_BUILD) && atoi(e) == 2;
   }
-  h->policy_lds_bytes = 0;
-  if (const char* e = getenv("SIMULST_POLICY_LDS_BYTES")) { const int v = atoi(e); if (v >= 0 && v <= 64 * 1024) h->policy_lds_bytes = v; }
-  h->fused_argmax = true;      // greedy pick's partial maxima in the vocabulary projection's epilogue (decode loops, bf16, co-scheduled rows)
-  if (const char* e = getenv("SIMULST_FUSED_ARGMAX")) h->fused_argmax = atoi(e) != 0;
-#ifdef SL_EXPERIMENTS
-  if (const char* e = getenv("SIMULST_DEC_ATTN_CHAIN_ROWS")) { const int v = atoi(e); if (v == 4 || v == 8 || v == 16) h->dec_attn_chain_rows = v; }
-#endif
-  h->dec_fuse_proj_cross = false;      // experiment, off
-#ifdef SL_EXPERIMENTS
-  if (const char* e = getenv("SIMULST_DEC_FUSE_PROJ_CROSS")) h->dec_fuse_proj_cross = atoi(e) != 0;
-#endif
-  h->fuse_flags = nullptr;
-  h->fuse_epoch = 0;
-  h->graph_exec = nullptr;
-  h->ctc_lds_attr_set = false;
-  h->conv_pos_lds_attr_set = false;
-  h->ffn_lds_attr_set = false;
-  h->ffn_pipe_lds_attr_set = false;
-  h->qkv_rows_lds_attr_set = false;
-  h->ffn_variant = 0;
-  h->ffn_waves = 0;
-  h->ea_general_only = false;
-  if (const char* e = getenv("SIMULST_EA_GENERAL")) h->ea_general_only = atoi(e) != 0;
-  h->graph_key = 0;
-  for (int i = 0; i < SIMULST_K_COUNT; ++i) { h->timer_on[i] = false; h->timer_ms[i] = 0.0; h->timer_n[i] = 0; }
+  int dev = 0, n = 0;
+  // a failed query leaves 0: the persistent one-workgroup-per-CU kernels (gemm_wstat.hip) then decline and the row panels run
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 0;
+  h->n_cus = n;
   *out = h;
   return SIMULST_OK;
 }
@@ -141,6 +140,15 @@ extern "C" int simulst_destroy(simulst_handle* h) {
   if (h->chain_sem) (void)hipFree(h->chain_sem);
   if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
   delete h;
+  return SIMULST_OK;
+}
+
+int sl_raise_lds_limits(simulst_handle* h, sl_lds_slot slot, const sl_lds_limit* list, int n, const char* who) {
+  for (int i = 0; i < n; ++i) {
+    const hipError_t e = hipFuncSetAttribute(list[i].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, list[i].bytes);
+    if (e != hipSuccess) { h->err = std::string(who) + ": cannot raise the dynamic LDS limit: " + hipGetErrorString(e); return (int)e; }
+  }
+  h->lds_raised[slot] = true;
   return SIMULST_OK;
 }
 
@@ -205,85 +213,21 @@ extern "C" int simulst_graph_enable(simulst_handle* h, int on) {
   return SIMULST_OK;
 }
 
-// Run-time options of a handle: path selection (each alternative is a complete, valid implementation -- the tests use them for
-// A/B parity) and the tuning values that simulst_create reads from the environment.
 extern "C" int simulst_set_option(simulst_handle* h, int32_t option, int32_t value) {
   if (!h) return SIMULST_E_NULL;
-  switch (option) {
-    case SIMULST_OPT_VALU_ATTENTION: h->force_valu_attention = value != 0; return SIMULST_OK;
-    case SIMULST_OPT_UNFUSED_DECODE: h->force_unfused_decode = value != 0; return SIMULST_OK;
-    case SIMULST_OPT_FFN_WAVES:
-#ifdef SL_EXPERIMENTS
-      SL_REQUIRE(h, value == 0 || value == 4 || value == 8 || value == 41 || value == 43 || value == 45 || value == 47 || value == 81 || value == 83 || value == 87
-#ifdef SL_DEBUG_HOOKS
-                        || value == 42 || value == 82
-#endif
-                 , SIMULST_E_ARG,
-                 "simulst_set_option(FFN_WAVES): 0 (the library's choice), 4 / 8 (GELU as a block between the products), 41 / 81 (GELU inside the "
-                 "MFMA stream, 4 / 8 waves; 42 / 82: packed GELU, DEBUG_HOOKS builds only), 43 / 83 (GELU spread over all 32 MFMAs), 45 (64 rows per wave)");
-#else
-      SL_REQUIRE(h, value == 0 || value == 4 || value == 8 || value == 43, SIMULST_E_ARG,
-                 "simulst_set_option(FFN_WAVES): 0 (the library's choice: 43 while F <= 2048), 43 (GELU inside the MFMA stream), 4 / 8 (the block form "
-                 "with that many waves: GELU between the two products); the measured-slower forms exist in EXPERIMENTS builds");
-#endif
-      h->ffn_waves = value; return SIMULST_OK;
-    case SIMULST_OPT_DEC_CHAIN: h->dec_chain_on = value != 0; return SIMULST_OK;
-#ifdef SL_EXPERIMENTS
-    case SIMULST_OPT_DEC_ATTN_CHAIN_MAX_ROWS:
-      SL_REQUIRE(h, value >= 0, SIMULST_E_ARG, "simulst_set_option(DEC_ATTN_CHAIN_MAX_ROWS): >= 0");
-      h->dec_attn_chain_max_rows = value; return SIMULST_OK;
-    case SIMULST_OPT_DEC_ATTN_CHAIN_ROWS:
-      SL_REQUIRE(h, value == 0 || value == 4 || value == 8 || value == 16, SIMULST_E_ARG, "simulst_set_option(DEC_ATTN_CHAIN_ROWS): 0, 4, 8 or 16");
-      h->dec_attn_chain_rows = value; return SIMULST_OK;
-#else
-    case SIMULST_OPT_DEC_ATTN_CHAIN_MAX_ROWS:
-    case SIMULST_OPT_DEC_ATTN_CHAIN_ROWS:
-      h->err = "simulst_set_option: self-attention inside the projection chain exists in EXPERIMENTS builds only (measured slower)";
+  if (option == SIMULST_OPT_PANEL_WIDE) {
+    if (value < 0 || value > ((SL_BUILD_FLAVOUR & SL_EXPERIMENTS_BUILD) ? 2 : 1)) {
+      h->err = "simulst_set_option(PANEL_WIDE): 0, 1 or 2 (plain stores: EXPERIMENTS builds only)";
       return SIMULST_E_ARG;
-#endif
-    case SIMULST_OPT_FUSED_ARGMAX: h->fused_argmax = value != 0; return SIMULST_OK;
-    case SIMULST_OPT_DEC_EMBED_QKV_CHAIN: h->dec_embed_qkv_chain = value != 0; return SIMULST_OK;
-    case SIMULST_OPT_WEIGHT_STATIONARY: h->wstat = value != 0; return SIMULST_OK;
-    case SIMULST_OPT_DEC_TALL_FFN: h->dec_tall_ffn = value != 0; return SIMULST_OK;
-    case SIMULST_OPT_CONV_TILE256:
-      SL_REQUIRE(h, value >= 0 && value <= 2, SIMULST_E_ARG, "simulst_set_option(CONV_TILE256): 0 (128 x 128 tiles), 1 (256 x 256, register stage), 2 (256 x 256, LDS-DMA ring)");
-      h->tile256 = value; return SIMULST_OK;
-    case SIMULST_OPT_DEC_CHAIN_ROWS32:
-#ifdef SL_EXPERIMENTS
-      h->dec_chain_rows32 = value != 0; return SIMULST_OK;
-#else
-      h->err = "simulst_set_option: the layer chains on 32-row tiles exist in EXPERIMENTS builds only (measured slower)";
-      return SIMULST_E_ARG;
-#endif
-    case SIMULST_OPT_DEC_FUSE_FFN_QKV:
-#ifdef SL_EXPERIMENTS
-      h->dec_fuse_ffn_qkv = value != 0; return SIMULST_OK;
-#else
-      h->err = "simulst_set_option: the feed-forward chain + next layer's QKV in one launch exists in EXPERIMENTS builds only (measured slower)";
-      return SIMULST_E_ARG;
-#endif
-    case SIMULST_OPT_PANEL_WIDE:
-#ifdef SL_EXPERIMENTS
-      SL_REQUIRE(h, value >= 0 && value <= 2, SIMULST_E_ARG, "simulst_set_option(PANEL_WIDE): 0, 1, 2 (plain stores)");
-#else
-      SL_REQUIRE(h, value == 0 || value == 1, SIMULST_E_ARG, "simulst_set_option(PANEL_WIDE): 0 or 1 (2, plain stores: EXPERIMENTS builds)");
-#endif
-      h->panel_wide = value != 0; h->panel_wide_plain_stores = value == 2; return SIMULST_OK;
-    case SIMULST_OPT_DEC_FUSE_PROJ_CROSS:
-#ifdef SL_EXPERIMENTS
-      h->dec_fuse_proj_cross = value != 0; return SIMULST_OK;
-#else
-      h->err = "simulst_set_option: the one-launch projection chain + cross-attention exists in EXPERIMENTS builds only (measured slower)";
-      return SIMULST_E_ARG;
-#endif
-    case SIMULST_OPT_DEC_VOCAB_CHAIN_SPLIT:
-      SL_REQUIRE(h, value == 0 || value == 1 || value == 2 || value == 4 || value == 8 || value == 16, SIMULST_E_ARG,
-                 "simulst_set_option(DEC_VOCAB_CHAIN_SPLIT): 0 (off), 1, 2, 4, 8 or 16");
-      h->dec_vocab_chain_split = value; return SIMULST_OK;
-    default: break;
+    }
+    h->panel_wide = value != 0; h->panel_wide_plain_stores = value == 2;
+    return SIMULST_OK;
   }
-  h->err = "simulst_set_option: unknown option";
-  return SIMULST_E_ARG;
+  const tunable* t = find_option(option);
+  if (!t) { h->err = "simulst_set_option: unknown option"; return SIMULST_E_ARG; }
+  if (!in_this_build(*t) || (t->set_ok && !t->set_ok(value))) { h->err = t->refusal; return SIMULST_E_ARG; }
+  h->*t->member = t->flag ? value != 0 : value;
+  return SIMULST_OK;
 }
 
 // What the handle currently runs with (the environment overrides of simulst_create included): callers that MODEL the launches of a
@@ -291,36 +235,18 @@ extern "C" int simulst_set_option(simulst_handle* h, int32_t option, int32_t val
 extern "C" int simulst_get_option(simulst_handle* h, int32_t option, int32_t* value) {
   if (!h) return SIMULST_E_NULL;
   SL_CHECK_NULL(h, value);
-  switch (option) {
-    case SIMULST_OPT_VALU_ATTENTION: *value = h->force_valu_attention; return SIMULST_OK;
-    case SIMULST_OPT_UNFUSED_DECODE: *value = h->force_unfused_decode; return SIMULST_OK;
-    case SIMULST_OPT_FFN_WAVES: *value = h->ffn_waves; return SIMULST_OK;
-    case SIMULST_OPT_DEC_CHAIN: *value = h->dec_chain_on; return SIMULST_OK;
-    case SIMULST_OPT_DEC_ATTN_CHAIN_MAX_ROWS: *value = h->dec_attn_chain_max_rows; return SIMULST_OK;
-    case SIMULST_OPT_DEC_ATTN_CHAIN_ROWS: *value = h->dec_attn_chain_rows; return SIMULST_OK;
-    case SIMULST_OPT_FUSED_ARGMAX: *value = h->fused_argmax; return SIMULST_OK;
-    case SIMULST_OPT_DEC_EMBED_QKV_CHAIN: *value = h->dec_embed_qkv_chain; return SIMULST_OK;
-    case SIMULST_OPT_PANEL_WIDE: *value = h->panel_wide ? (h->panel_wide_plain_stores ? 2 : 1) : 0; return SIMULST_OK;
-    case SIMULST_OPT_DEC_VOCAB_CHAIN_SPLIT: *value = h->dec_vocab_chain_split; return SIMULST_OK;
-    case SIMULST_OPT_WEIGHT_STATIONARY: *value = h->wstat; return SIMULST_OK;
-    case SIMULST_OPT_DEC_TALL_FFN: *value = h->dec_tall_ffn; return SIMULST_OK;
-    case SIMULST_OPT_CONV_TILE256: *value = h->tile256; return SIMULST_OK;
-    case SIMULST_OPT_DEC_FUSE_FFN_QKV: *value = h->dec_fuse_ffn_qkv; return SIMULST_OK;
-    case SIMULST_OPT_DEC_CHAIN_ROWS32: *value = h->dec_chain_rows32; return SIMULST_OK;
-    case SIMULST_OPT_DEC_FUSE_PROJ_CROSS: {
-      // bit 0: on; bit 1: a waiting workgroup's bounded spin ran out at some point (synchronises the stream: tests only)
-      int err = 0;
-      if (h->fuse_flags) {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipMemcpy(&err, h->fuse_flags + 1023, sizeof(int), hipMemcpyDeviceToHost);
-      }
-      *value = (h->dec_fuse_proj_cross ? 1 : 0) | (err ? 2 : 0);
-      return SIMULST_OK;
-    }
-    default: break;
+  if (option == SIMULST_OPT_PANEL_WIDE) { *value = h->panel_wide ? (h->panel_wide_plain_stores ? 2 : 1) : 0; return SIMULST_OK; }
+  const tunable* t = find_option(option);
+  if (!t) { h->err = "simulst_get_option: unknown option"; return SIMULST_E_ARG; }
+  *value = h->*t->member;
+  if (option == SIMULST_OPT_DEC_FUSE_PROJ_CROSS && h->fuse_flags) {
+    // bit 0: on; bit 1: a waiting workgroup's bounded spin ran out at some point (synchronises the stream: tests only)
+    int err = 0;
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipMemcpy(&err, h->fuse_flags + 1023, sizeof(int), hipMemcpyDeviceToHost);
+    *value |= err ? 2 : 0;
   }
-  h->err = "simulst_get_option: unknown option";
-  return SIMULST_E_ARG;
+  return SIMULST_OK;
 }
 
 // HIP streams with a compute-unit mask and / or a priority, for callers whose framework cannot create them (torch wraps the returned
@@ -352,10 +278,4 @@ extern "C" int simulst_stream_destroy(void* stream) {
 }
 
 // 1 in a `make EXPERIMENTS=1` build (the measured-slower kernel families and their option values are compiled in), else 0
-extern "C" int simulst_has_experiments(void) {
-#ifdef SL_EXPERIMENTS
-  return 1;
-#else
-  return 0;
-#endif
-}
+extern "C" int simulst_has_experiments(void) { return (SL_BUILD_FLAVOUR & SL_EXPERIMENTS_BUILD) ? 1 : 0; }

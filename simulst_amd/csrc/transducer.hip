@@ -596,13 +596,9 @@ template <typename T>
 int lattice_launch(simulst_handle* h, const float* P, const float* G, const void* W_fm, const int32_t* labels, const int32_t* src_len,
                    const int32_t* tgt_len, float* partials, int B, int S, int U1, int D, int V, int blank, int n_split) {
   const size_t lds = lattice_lds_bytes<T>(D);
-  static bool raised = false;                       // more than 64 KB of dynamic LDS has to be asked for, once per kernel
-  if (!raised) {
-    const hipError_t e = hipFuncSetAttribute((const void*)joiner_lattice_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)LATTICE_LDS_MAX);
-    if (e != hipSuccess) { h->err = std::string("simulst_joiner_lattice: ") + hipGetErrorString(e); return (int)e; }
-    raised = true;
-  }
+  static const sl_lds_limit limits[] = {{(const void*)joiner_lattice_kernel<float>, (int)LATTICE_LDS_MAX},      // more than 64 KB of dynamic LDS
+                                        {(const void*)joiner_lattice_kernel<bf16>, (int)LATTICE_LDS_MAX}};
+  if (int rc = sl_raise_lds(h, SL_LDS_JOINER_LATTICE, limits, "simulst_joiner_lattice")) return rc;
   const int u_tiles = (U1 + 15) / 16;
   const long n_tiles = (long)B * S * u_tiles;
   const long wgs = (n_tiles + LatCfg<T>::R - 1) / LatCfg<T>::R;
