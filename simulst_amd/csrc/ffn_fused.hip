@@ -30,20 +30,14 @@
 // in every setting): they drift apart by themselves.
 // Algorithmic work per launch: 4 * rows * D * F flop (two contractions), HBM bytes 2 * rows * D * 2 (x read for the
 // contraction, again for the residual: L2/MALL-hot) + rows * D * 2 written; weights 2 * D * F * 2 B from L2 per workgroup.
-#include "gemm_args.h"
-#include "ffn_variant.h"
-
-int sl_launch_qkv_rows(simulst_handle* h, const void* z, const void* wqkv_fm, const float* bqkv, void* qkv, int n_utt, int rows_z, int n_mem,
-                       int sum0, int n_sum);
-int sl_launch_ffn_pipe(simulst_handle* h, const void* x, const float* ln_g, const float* ln_b, const void* w1p, const float* b1,
-                       const void* w2p, const float* b2, void* out, long rows, int F, sl_ffn_variant v, const sl_ffn_z* zout = nullptr);
+#include "ffn_core.h"
+using namespace ffn;
 
 namespace {
 
 // Two geometries of the same kernel: WAVES = 8 (512 threads, 256 rows, 64 hidden units per chunk, one workgroup per CU)
 // and WAVES = 4 (256 threads, 128 rows, 32 hidden units per chunk, 75 KB of LDS: TWO workgroups per CU, which drift out
 // of phase, so that one's GELU arithmetic runs beside the other's MFMAs; each streams the weights for half as many rows).
-constexpr int FF_D = 256;             // model width (K of fc1, N of fc2)
 template <int WAVES> struct FFG {
   static constexpr int THREADS = 64 * WAVES;
   static constexpr int ROWS = 32 * WAVES;            // rows per workgroup
@@ -53,19 +47,9 @@ template <int WAVES> struct FFG {
   static constexpr int CHUNK_BYTES = 2 * W1_BYTES;
   static constexpr int PIECE = THREADS * 16;         // bytes one LDS-DMA instruction of the whole workgroup moves
   static constexpr int MAX_F = WAVES == 8 ? 4096 : 2048;   // fc1 bias lives in LDS
-  static constexpr int LDS = 2 * CHUNK_BYTES + 3072 + MAX_F * 4;
+  static constexpr int LDS = 2 * CHUNK_BYTES + FF_PARAM_BYTES + MAX_F * 4;
 };
 static_assert(FFG<4>::MAX_F == SL_FFN_BLOCK4_MAX_F, "ffn_variant.h decides the block form's geometry");
-constexpr int FF_PF = 4;               // weight fragments requested ahead of the MFMA that consumes them
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-__device__ __forceinline__ unsigned int pack_bf16x2(float lo, float hi) {
-  const bf16 l = __float2bfloat16(lo), h = __float2bfloat16(hi);
-  return (unsigned int)(*reinterpret_cast<const unsigned short*>(&l)) |
-         ((unsigned int)(*reinterpret_cast<const unsigned short*>(&h)) << 16);
-}
 
 // one chunk (W1 part then W2 part, each already in fragment order) global -> LDS: 4 + 4 x 16 B per thread,
 // LDS destination of a wave instruction = wave-uniform base + lane * 16
@@ -93,11 +77,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void ffn_fused_kernel(const bf16* __
                                                            bf16* __restrict__ out, long M, int F) {
   using G = FFG<WAVES>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  float* lng = reinterpret_cast<float*>(lds + 2 * G::CHUNK_BYTES);
-  float* lnb = lng + FF_D;
-  float* b2s = lnb + FF_D;
-  float* b1s = b2s + FF_D;                                   // fc1 bias: an ordinary global load inside the loop would
-                                                             // make hipcc drain the in-flight LDS-DMA (vmcnt(0)) at its use
+  const Params p = params_at(lds + 2 * G::CHUNK_BYTES);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
   const long row0 = (long)blockIdx.x * G::ROWS + wave * 32;
@@ -106,23 +86,14 @@ __global__ __launch_bounds__(64 * WAVES, 2) void ffn_fused_kernel(const bf16* __
   const unsigned voff = (unsigned)tid * 16u;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   stage_chunk<WAVES>(W1p, W2p, 0, lds, voff, wave_u);                       // first weights on their way before anything else
-  for (int k = tid; k < FF_D; k += G::THREADS) { lng[k] = ln_g[k]; lnb[k] = ln_b[k]; b2s[k] = b2[k]; }
-  for (int k = tid; k < F; k += G::THREADS) b1s[k] = b1[k];
+  for (int k = tid; k < FF_D; k += G::THREADS) { p.lng[k] = ln_g[k]; p.lnb[k] = ln_b[k]; p.b2s[k] = b2[k]; }
+  for (int k = tid; k < F; k += G::THREADS) p.b1s[k] = b1[k];
+  const float* b1s = p.b1s;
 
-  // ---- this wave's rows as B-operand fragments of Ht = W1 . LN(x)^T: lane (lr, lh) holds x[row lr][16 s + 8 lh + j]
-  uint4 xa[16];
-  {
-    const long r = row0 + lr;
-    const bool ok = r < M;
-    const bf16* xr = X + (ok ? r : 0) * FF_D + lh * 8;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const uint4 v = ld16(xr + s * 16);
-      xa[s] = make_uint4(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u);
-    }
-  }
+  uint4 xa[16];                                              // this wave's rows, LayerNorm-ed: the B operand of the first product
+  load_rows(xa, X, row0, M, lr, lh);
   __syncthreads();                                           // gamma / beta / b2 visible
-  {
+  {  // layer_norm_rows (ffn_core.h) written out: under this file's SLP vectoriser the shared function packs 32 more of the moments' adds
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int s = 0; s < 16; ++s) moments_mid(xa[s], s1, s2, bf16());
@@ -131,7 +102,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void ffn_fused_kernel(const bf16* __
     const float mean = s1 * (1.0f / FF_D);
     const float rstd = 1.0f / sqrtf(fmaxf(s2 * (1.0f / FF_D) - mean * mean, 0.f) + 1e-5f);
 #pragma unroll
-    for (int s = 0; s < 16; ++s) xa[s] = ln_frag_mid(xa[s], mean, rstd, lng, lnb, s * 16 + lh * 8, bf16());
+    for (int s = 0; s < 16; ++s) xa[s] = ln_frag_mid(xa[s], mean, rstd, p.lng, p.lnb, s * 16 + lh * 8, bf16());
   }
 
   f32x16 y[8];
@@ -196,37 +167,12 @@ __global__ __launch_bounds__(64 * WAVES, 2) void ffn_fused_kernel(const bf16* __
       }
     }
   }
-  // ---- epilogue: y[n][e] = Y[row (e & 3) + 8 (e >> 2) + 4 lh][col 32 n + lr].  Stage as bf16 rows in
-  // this wave's 16 KB slice of the weight buffers, then whole rows leave with the residual added.
+  // ---- epilogue: bf16 rows staged in this wave's 16 KB slice of the weight buffers (8 waves x 16 KB = the two buffers), then whole
+  // rows leave with the residual added
   __syncthreads();                                           // every wave is done with the weight buffers
-  constexpr int RS = FF_D * 2;                               // staged row stride in bytes (8 waves x 16 KB = the two buffers)
-  char* st = lds + wave * (32 * RS);
-#pragma unroll
-  for (int n = 0; n < 8; ++n) {
-    const float bv = b2s[n * 32 + lr];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
-      *reinterpret_cast<bf16*>(st + r * RS + (n * 32 + lr) * 2) = __float2bfloat16(y[n][e] + bv);
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int it = 0; it < 16; ++it) {
-    const int rl = it * 2 + lh;                              // 32 lanes x 16 B = one 512-byte row
-    const long r = row0 + rl;
-    if (r >= M) continue;
-    const uint4 yv = *reinterpret_cast<const uint4*>(st + rl * RS + lr * 16);
-    const uint4 xv = ld16(X + r * FF_D + lr * 8);
-    const unsigned int yu[4] = {yv.x, yv.y, yv.z, yv.w}, xu[4] = {xv.x, xv.y, xv.z, xv.w};
-    unsigned int ou[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      ou[q] = pack_bf16x2(__uint_as_float(yu[q] << 16) + __uint_as_float(xu[q] << 16),
-                          __uint_as_float(yu[q] & 0xffff0000u) + __uint_as_float(xu[q] & 0xffff0000u));
-    st_stream16(out + r * FF_D + lr * 8, make_uint4(ou[0], ou[1], ou[2], ou[3]));
-  }
+  stage_rows(lds, wave, y, p.b2s, lr, lh);
+  stage_sync();
+  store_rows(lds, wave, X, out, row0, M, lr, lh);
 }
 
 }  // namespace

@@ -1,8 +1,7 @@
 // The fused Emformer feed-forward block (ffn_fused.hip) with the GELU INSIDE the matrix-core stream -- gfx950, bf16, D = 256.
 // Compiled WITHOUT the SLP vectoriser (Makefile): it re-packs the per-element scalar GELU of four neighbouring elements into packed
 // fp32 instructions and emits them as one block per four MFMAs, undoing the placement pinned in the source.
-#include "gemm_args.h"
-#include "ffn_variant.h"
+#include "ffn_core.h"
 #include <type_traits>
 #include <cstdio>
 #include <vector>
@@ -16,18 +15,9 @@ __device__ long sl_probe_ffn[4096 * 8 * 4];
 #define FP_STAMP(v)
 #endif
 
+using namespace ffn;
+
 namespace {
-
-constexpr int FF_D = 256;
-constexpr int FF_PF = 4;               // weight fragments requested ahead of the MFMA that consumes them
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-__device__ __forceinline__ unsigned int pack_bf16x2(float lo, float hi) {
-  const bf16 l = __float2bfloat16(lo), h = __float2bfloat16(hi);
-  return (unsigned int)(*reinterpret_cast<const unsigned short*>(&l)) |
-         ((unsigned int)(*reinterpret_cast<const unsigned short*>(&h)) << 16);
-}
 
 // Round 4.  ffn_fused_kernel runs [fc1 MFMAs | GELU block | fc2 MFMAs] per 32-unit tile: hipcc emits the GELU as one block of ~130 vector
 // instructions between two runs of 16 MFMAs, so a wave's matrix cores idle through its own GELU and overlap only happens when the
@@ -42,17 +32,15 @@ __device__ __forceinline__ unsigned int pack_bf16x2(float lo, float hi) {
 // LDS: the weight tiles of fc1 run ONE tile ahead of those of fc2, so they are two rings of two 16 KB slots each (64 KB, as the
 // 4-wave geometry of ffn_fused.hip): at the start of iteration t every wave has finished iteration t - 1, the DMA of W1(t + 2) goes to the slot
 // W1(t) left and that of W2(t + 1) to the slot W2(t - 1) left; both land during iteration t.
-__device__ __forceinline__ float gelu_fast1(float x) {
-  // gelu_fast2 (common.h), one element: the same operations in the same order
-  const float h = x * 0.5f;
-  const float a = __builtin_fabsf(h);
-  float q = __builtin_fmaf(a, SL_GELU_C5, SL_GELU_C4);
-  q = __builtin_fmaf(q, a, SL_GELU_C3);
-  q = __builtin_fmaf(q, a, SL_GELU_C2);
-  q = __builtin_fmaf(q, a, SL_GELU_C1);
-  q = q * a;
-  const float e = __builtin_amdgcn_exp2f(q);
-  return __builtin_fmaf(-a, e, h + a);
+// (The phase forms themselves: experiments/ffn_pipe_forms.inc; what ships is the uniform schedule, at ffn_pipe_kernel below.)
+
+// two floats -> one register of two bf16 in ONE instruction.  hipcc lowers __float2bfloat16 to v_cvt_pk_bf16_f32 as well, but with
+// the two values produced in different scheduling regions it converted each on its own and merged them (2 x v_cvt_pk + v_lshlrev +
+// v_or_sdwa per pair); the vector pipe is what paces phase A, so the three instructions matter
+__device__ __forceinline__ unsigned int cvt_pk_bf16(float lo, float hi) {
+  unsigned int r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
 }
 
 // The same arithmetic for the uniform schedule.  It takes the fc1 accumulator and HALF the bias: fma(acc, 0.5, b / 2) == (acc + b) * 0.5
@@ -78,21 +66,22 @@ __device__ __forceinline__ void gelu_q3(GeluPair& g) {
 #pragma unroll
   for (int k = 0; k < 2; ++k) g.q[k] = __builtin_amdgcn_exp2f(g.q[k] * g.a[k]);
 }
-__device__ __forceinline__ unsigned int cvt_pk_bf16(float lo, float hi);
 __device__ __forceinline__ unsigned int gelu_q4(const GeluPair& g) {
   float v[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) v[k] = __builtin_fmaf(-g.a[k], g.q[k], g.h[k] + g.a[k]);
   return cvt_pk_bf16(v[0], v[1]);
 }
-
-// two floats -> one register of two bf16 in ONE instruction.  hipcc lowers __float2bfloat16 to v_cvt_pk_bf16_f32 as well, but with
-// the two values produced in different scheduling regions it converted each on its own and merged them (2 x v_cvt_pk + v_lshlrev +
-// v_or_sdwa per pair); the vector pipe is what paces phase A, so the three instructions matter
-__device__ __forceinline__ unsigned int cvt_pk_bf16(float lo, float hi) {
-  unsigned int r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
+// Quarter q (0 .. 3) of the GELU of element pair `pair` of the fc1 accumulator src, the unit of work behind one MFMA of the uniform
+// schedule: bv holds the half-bias of the pair's group of four elements (its .x / .y for an even pair, .z / .w for an odd one), the
+// result goes to hb[pair], and with `fetch` the second quarter loads the half-bias group at nxt_bias into dst_bias.  The callers keep
+// the sched_barrier on either side.
+__device__ __forceinline__ void gelu_quarter(GeluPair& gp, int q, int pair, const f32x16& src, const float4& bv, unsigned int* hb,
+                                             bool fetch, const float* nxt_bias, float4& dst_bias) {
+  if (q == 0) gelu_q1(gp, src[2 * pair], src[2 * pair + 1], (pair & 1) ? bv.z : bv.x, (pair & 1) ? bv.w : bv.y);
+  else if (q == 1) { gelu_q2(gp); if (fetch) dst_bias = *reinterpret_cast<const float4*>(nxt_bias); }
+  else if (q == 2) gelu_q3(gp);
+  else hb[pair] = gelu_q4(gp);
 }
 
 constexpr int FP_W = 16 * 1024;         // one weight tile: 32 hidden units x 256 x bf16
@@ -107,7 +96,7 @@ template <int WAVES> struct FPG {
   static constexpr int NS = WAVES == 8 ? 4 : 2;              // slots per ring
   static constexpr int AHEAD = WAVES == 8 ? 2 : 1;           // iterations between a tile's request and its first use
   static constexpr int PIECES = FP_W / (THREADS * 16);       // DMA instructions per wave and tile
-  static constexpr int LDS = 2 * NS * FP_W + 3072 + 2048 * 4;
+  static constexpr int LDS = 2 * NS * FP_W + FF_PARAM_BYTES + SL_FFN_PIPE_MAX_F * 4;
 };
 
 // One 1 KiB LDS-DMA piece, issued from inline assembly (round 6).  Through __builtin_amdgcn_global_load_lds hipcc books the piece as a
@@ -135,24 +124,15 @@ __device__ __forceinline__ void stage_tile(const bf16* __restrict__ wp, int tile
     glds16(g + (unsigned)(voff + q * FPG<WAVES>::THREADS * 16), d0 + (unsigned)(q * FPG<WAVES>::THREADS * 16));
 }
 
-// UNI (round 4, second form): the GELU of a tile spread over ALL 32 MFMAs of an iteration instead of the 16 of phase A -- a quarter
-// of an element pair (two independent chains) behind every MFMA.  The phase form leaves a wave's 16 fc2 MFMAs without vector work, and since that run is short the two waves
-// of a SIMD spend most of their time BOTH in phase A, where 2 x 21 vector instructions per MFMA pace them (phase probe: A 74 %, B 22 %).
-// What allows it: fc2's MFMAs 0 .. 7 read only the packed elements 0 .. 7 of the tile (k-step 0), MFMAs 8 .. 15 only elements 8 .. 15, and
-// the accumulator of tile t + 1 is complete after the 16th fc1 MFMA.  So, per iteration t:
-//   MFMAs  0 .. 15   fc1 of tile t + 1     with the GELU of elements  4 .. 11 of tile t       (a quarter of an element PAIR per MFMA)
-//   MFMAs 16 .. 23   fc2 k-step 0 of t     with elements 12 .. 15 of tile t
-//   MFMAs 24 .. 31   fc2 k-step 1 of t     with elements 0 .. 3 of tile t + 1 (its registers were freed by MFMAs 16 .. 23)
-// No extra registers: the packed elements are written into the halves of hb that the fc2 MFMAs have already read.
+// SPREAD (round 6, uniform schedule only): the 2 * PIECES LDS-DMA pieces of an iteration are issued ONE PER MFMA GAP behind the first
+// fc1 MFMAs instead of as a burst behind the barrier, where all waves of both resident workgroups issue theirs at the same moment
+// (MI355X_MICROARCH.md: a piece costs its wave 100-185 cycles inside a phase already carrying 8 pieces, 25-60 in a later gap).
 template <int WAVES>
 __device__ __forceinline__ void stage_piece(const bf16* __restrict__ wp, int tile, char* dst, unsigned voff, int wave, int q) {
   const char* g = reinterpret_cast<const char*>(wp) + (long)tile * FP_W;
   glds16(g + (unsigned)(voff + q * FPG<WAVES>::THREADS * 16), lds_addr(dst) + (unsigned)wave * 1024u + (unsigned)(q * FPG<WAVES>::THREADS * 16));
 }
 
-// SPREAD (round 6, uniform schedule only): the 2 * PIECES LDS-DMA pieces of an iteration are issued ONE PER MFMA GAP behind the first
-// fc1 MFMAs instead of as a burst behind the barrier, where all waves of both resident workgroups issue theirs at the same moment
-// (MI355X_MICROARCH.md: a piece costs its wave 100-185 cycles inside a phase already carrying 8 pieces, 25-60 in a later gap).
 // A K = 256 projection of 32 rows per wave with the weights streamed through LDS (the next layer's fused Q | K | V projection, QOUT and
 // qkv_rows_kernel; measured and not kept, DESIGN.md section 3: the attention output projection in front of the feed-forward): simulst_linear's weight-stationary kernel
 // (gemm_wstat.hip) operation for operation -- v_mfma_f32_16x16x32_bf16, weights as the A operand, k-steps 0 .. 7, its permuted column
@@ -236,10 +216,7 @@ __device__ __forceinline__ void pair_ring(char* lds, const bf16* Wfm, const uint
 __device__ __forceinline__ uint4 ring_store8(bf16* dst, const float (&y)[8]) {
   unsigned int ou[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const bf16 lo = __float2bfloat16(y[2 * q]), hi = __float2bfloat16(y[2 * q + 1]);
-    ou[q] = (unsigned int)(*reinterpret_cast<const unsigned short*>(&lo)) | ((unsigned int)(*reinterpret_cast<const unsigned short*>(&hi)) << 16);
-  }
+  for (int q = 0; q < 4; ++q) ou[q] = pack_bf16x2(y[2 * q], y[2 * q + 1]);
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   const u32x4 ov = {ou[0], ou[1], ou[2], ou[3]};
   asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(dst), "v"(ov) : "memory");
@@ -289,13 +266,20 @@ __global__ __launch_bounds__(256, 2) void qkv_rows_kernel(const bf16* __restrict
   qkv_pair_ring(lds, bias_lds, Wqkv, bqkv, fq, qrow, tid, wave_u);
 }
 
-// ZOUT (round 6): the launch also does the NEXT layer's pre-attention LayerNorm (_EmformerLayer.layer_norm_input,
-// torchaudio_models/emformer.py:431-452: feed-forward -> residual -> next layer's pre-LN) and its segment summaries (:163-167, the
-// AvgPool1d of the normalised utterance rows), i.e. what simulst_emformer_prenorm did in a launch of its own: the epilogue holds every
-// output row whole (32 lanes x 8 columns), so the row's statistics are one 32-lane reduction, the normalised row goes to its place in
-// the next layer's Z buffer and a wave's 32 rows are exactly two 16-row segments.  For that the workgroups tile every utterance on
-// its own (rows_x = n_rc + T rows, n_rc a multiple of 32): a wave never straddles two utterances or two segments.
+#if defined(SL_EXPERIMENTS) || defined(SL_DEBUG_HOOKS)
+#define SL_FFN_PHASE_FORMS      // ffn_pipe_kernel's tile loop has its UNI = false branch
+#include "experiments/ffn_pipe_forms.inc"      // the measured-slower forms: gelu_fast1 for the phase forms, (EXPERIMENTS) ffn_wide_kernel
+#endif
 
+// UNI (round 4, second form): the GELU of a tile spread over ALL 32 MFMAs of an iteration instead of the 16 of phase A -- a quarter
+// of an element pair (two independent chains) behind every MFMA.  The phase form leaves a wave's 16 fc2 MFMAs without vector work, and since that run is short the two waves
+// of a SIMD spend most of their time BOTH in phase A, where 2 x 21 vector instructions per MFMA pace them (phase probe: A 74 %, B 22 %).
+// What allows it: fc2's MFMAs 0 .. 7 read only the packed elements 0 .. 7 of the tile (k-step 0), MFMAs 8 .. 15 only elements 8 .. 15, and
+// the accumulator of tile t + 1 is complete after the 16th fc1 MFMA.  So, per iteration t:
+//   MFMAs  0 .. 15   fc1 of tile t + 1     with the GELU of elements  4 .. 11 of tile t       (a quarter of an element PAIR per MFMA)
+//   MFMAs 16 .. 23   fc2 k-step 0 of t     with elements 12 .. 15 of tile t
+//   MFMAs 24 .. 31   fc2 k-step 1 of t     with elements 0 .. 3 of tile t + 1 (its registers were freed by MFMAs 16 .. 23)
+// No extra registers: the packed elements are written into the halves of hb that the fc2 MFMAs have already read.
 template <int WAVES, bool PK, bool UNI, bool SPREAD = false, bool ZOUT = false, bool QOUT = false>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void ffn_pipe_kernel(
     const bf16* __restrict__ X, const float* __restrict__ ln_g, const float* __restrict__ ln_b, const bf16* __restrict__ W1p,
@@ -306,10 +290,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void ffn_pipe_kerne
   extern __shared__ __attribute__((aligned(16))) char lds[];
   char* w1ring = lds;                                        // NS slots
   char* w2ring = lds + NS * FP_W;                            // NS slots
-  float* lng = reinterpret_cast<float*>(lds + 2 * NS * FP_W);
-  float* lnb = lng + FF_D;
-  float* b2s = lnb + FF_D;
-  float* b1s = b2s + FF_D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
   // rows [row0, row0 + 32) of the flattened activations, valid below row_end: the whole matrix, or (ZOUT) this utterance's rows
@@ -336,31 +316,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void ffn_pipe_kerne
     if (a < nt) stage_tile<WAVES>(W1p, a, w1ring + (a % NS) * FP_W, voff, wave_u);
     if (a < AH && a < nt) stage_tile<WAVES>(W2p, a, w2ring + (a % NS) * FP_W, voff, wave_u);
   }
-  for (int k = tid; k < FF_D; k += G::THREADS) { lng[k] = ln_g[k]; lnb[k] = ln_b[k]; b2s[k] = b2[k]; }
-  for (int k = tid; k < F; k += G::THREADS) b1s[k] = UNI ? 0.5f * b1[k] : b1[k];     // UNI: half the bias (gelu_first_half)
+  const Params p = params_at(lds + 2 * NS * FP_W);
+  for (int k = tid; k < FF_D; k += G::THREADS) { p.lng[k] = ln_g[k]; p.lnb[k] = ln_b[k]; p.b2s[k] = b2[k]; }
+  for (int k = tid; k < F; k += G::THREADS) p.b1s[k] = UNI ? 0.5f * b1[k] : b1[k];     // UNI: half the bias (gelu_q1)
+  float* const b1s = p.b1s;
   uint4 xa[16];
-  {
-    const long r = row0 + lr;
-    const bool ok = r < row_end;
-    const bf16* xr = X + (ok ? r : 0) * FF_D + lh * 8;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const uint4 v = ld16(xr + s * 16);
-      xa[s] = make_uint4(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u);
-    }
-  }
+  load_rows(xa, X, row0, row_end, lr, lh);
   __syncthreads();
-  {
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) moments_mid(xa[s], s1, s2, bf16());
-    s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
-    const float mean = s1 * (1.0f / FF_D);
-    const float rstd = 1.0f / sqrtf(fmaxf(s2 * (1.0f / FF_D) - mean * mean, 0.f) + 1e-5f);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) xa[s] = ln_frag_mid(xa[s], mean, rstd, lng, lnb, s * 16 + lh * 8, bf16());
-  }
+  layer_norm_rows(xa, p.lng, p.lnb, lh);
   f32x16 y[8];
 #pragma unroll
   for (int n = 0; n < 8; ++n)
@@ -429,7 +392,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void ffn_pipe_kerne
     f32x16 hnext;
 #pragma unroll
     for (int e = 0; e < 16; ++e) hnext[e] = 0.f;
-    // ---- phase A: one fc1 MFMA of tile t + 1, then bias + GELU of element s of tile t (pairs packed as they complete)
     uint4 wfa[FF_PF];
     if constexpr (MORE) {
 #pragma unroll
@@ -453,10 +415,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void ffn_pipe_kerne
         }
         if constexpr (MORE) { if (s + FF_PF < 16) wfa[s % FF_PF] = w1[(s + FF_PF) * 64 + lane]; }
         const int pr = 2 + (s >> 2);                            // pairs 2 .. 5 = elements 4 .. 11 of tile t
-        if ((s & 3) == 0) gelu_q1(gp, hcur[2 * pr], hcur[2 * pr + 1], (pr & 1) ? bv.z : bv.x, (pr & 1) ? bv.w : bv.y);
-        else if ((s & 3) == 1) { gelu_q2(gp); if (pr & 1) bv = *reinterpret_cast<const float4*>(bt + 8 * ((pr + 1) >> 1)); }
-        else if ((s & 3) == 2) gelu_q3(gp);
-        else hb[pr] = gelu_q4(gp);
+        gelu_quarter(gp, s & 3, pr, hcur, bv, hb, pr & 1, bt + 8 * ((pr + 1) >> 1), bv);
         __builtin_amdgcn_sched_barrier(0);
       }
       FP_STAMP(p3);
@@ -471,97 +430,22 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void ffn_pipe_kerne
         __builtin_amdgcn_sched_barrier(0);
         if (i + FF_PF < 16) wf[i % FF_PF] = w2[(i + FF_PF) * 64 + lane];
         if (i < 8) {
-          const int pr = 6 + (i >> 2);                          // pairs 6, 7 = elements 12 .. 15 of tile t
-          if ((i & 3) == 0) gelu_q1(gp, hcur[2 * pr], hcur[2 * pr + 1], (pr & 1) ? bv.z : bv.x, (pr & 1) ? bv.w : bv.y);
-          else if ((i & 3) == 1) { gelu_q2(gp); if (pr == 7) { if constexpr (MORE) bv = *reinterpret_cast<const float4*>(bt + 32); } }
-          else if ((i & 3) == 2) gelu_q3(gp);
-          else hb[pr] = gelu_q4(gp);
+          const int pr = 6 + (i >> 2);                          // pairs 6, 7 = elements 12 .. 15 of tile t; then the half-bias of tile t + 1
+          gelu_quarter(gp, i & 3, pr, hcur, bv, hb, MORE && pr == 7, bt + 32, bv);
         } else if constexpr (MORE) {
           const int pr = (i - 8) >> 2;                          // pairs 0, 1 = elements 0 .. 3 of tile t + 1: hb[0], hb[1] were read by MFMAs 16 .. 23
-          if ((i & 3) == 0) gelu_q1(gp, hnext[2 * pr], hnext[2 * pr + 1], (pr & 1) ? bv.z : bv.x, (pr & 1) ? bv.w : bv.y);
-          else if ((i & 3) == 1) { gelu_q2(gp); if (pr == 1) bv_carry = *reinterpret_cast<const float4*>(bt + 32 + 8); }
-          else if ((i & 3) == 2) gelu_q3(gp);
-          else hb[pr] = gelu_q4(gp);
+          gelu_quarter(gp, i & 3, pr, hnext, bv, hb, pr == 1, bt + 32 + 8, bv_carry);
         }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#ifdef SL_PROBE
-      FP_STAMP(p4);
-      pr_dma += p1 - p0; pr_bar += p2 - p1; pr_a += p3 - p2; pr_b += p4 - p3;
-#endif
-      if constexpr (MORE) hcur = hnext;
-      return;
-    }
-    float4 bv = *reinterpret_cast<const float4*>(bt);
-    float gprev = 0.f;
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!PK) {
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        if constexpr (MORE)
-          hnext = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(&wfa[s % FF_PF]),
-                                                          *reinterpret_cast<const bf16x8_t*>(&xa[s]), hnext, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MORE) { if (s + FF_PF < 16) wfa[s % FF_PF] = w1[(s + FF_PF) * 64 + lane]; }
-        const float bias = (s & 3) == 0 ? bv.x : (s & 3) == 1 ? bv.y : (s & 3) == 2 ? bv.z : bv.w;
-        const float gv = gelu_fast1(hcur[s] + bias);
-        if ((s & 3) == 3 && s < 15) bv = *reinterpret_cast<const float4*>(bt + 8 * ((s + 1) >> 2));
-        if (s & 1) hb[s >> 1] = cvt_pk_bf16(gprev, gv); else gprev = gv;
         __builtin_amdgcn_sched_barrier(0);
       }
     } else {
-      // packed form: the GELU of an element PAIR (gelu_fast2, the arithmetic of ffn_fused_kernel) in two halves behind two MFMAs --
-      // 15 packed instructions + 2 v_rcp per pair instead of 2 x 17 scalar ones (the phase probe of the scalar form: both waves of a
-      // SIMD sit in phase A 74 % of the time and their 2 x 21 vector instructions per MFMA, not the matrix cores, pace it)
-      f32x2 ph, pha, pq;
-#pragma unroll
-      for (int sp = 0; sp < 8; ++sp) {
-        if constexpr (MORE)
-          hnext = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(&wfa[(2 * sp) % FF_PF]),
-                                                          *reinterpret_cast<const bf16x8_t*>(&xa[2 * sp]), hnext, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MORE) { if (2 * sp + FF_PF < 16) wfa[(2 * sp) % FF_PF] = w1[(2 * sp + FF_PF) * 64 + lane]; }
-        {
-          const f32x2 b2v = (sp & 1) ? f32x2{bv.z, bv.w} : f32x2{bv.x, bv.y};
-          const f32x2 xv = f32x2{hcur[2 * sp] + b2v.x, hcur[2 * sp + 1] + b2v.y};
-          ph = xv * 0.5f;
-          pha = __builtin_elementwise_abs(ph);
-          pq = pha * SL_GELU_C5 + SL_GELU_C4;
-          pq = pq * pha + SL_GELU_C3;
-          pq = pq * pha + SL_GELU_C2;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MORE)
-          hnext = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(&wfa[(2 * sp + 1) % FF_PF]),
-                                                          *reinterpret_cast<const bf16x8_t*>(&xa[2 * sp + 1]), hnext, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MORE) { if (2 * sp + 1 + FF_PF < 16) wfa[(2 * sp + 1) % FF_PF] = w1[(2 * sp + 1 + FF_PF) * 64 + lane]; }
-        {
-          pq = pq * pha + SL_GELU_C1;
-          pq = pq * pha;
-          f32x2 r;
-          r.x = __builtin_amdgcn_exp2f(pq.x);
-          r.y = __builtin_amdgcn_exp2f(pq.y);
-          const f32x2 gv2 = (ph + pha) - pha * r;
-          hb[sp] = pack_bf16x2(gv2.x, gv2.y);
-          if ((sp & 1) && sp < 7) bv = *reinterpret_cast<const float4*>(bt + 8 * ((sp + 1) >> 1));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    FP_STAMP(p3);
-    // ---- phase B: the 16 fc2 MFMAs of tile t
-    {
-      uint4 wf[FF_PF];
-#pragma unroll
-      for (int i = 0; i < FF_PF; ++i) wf[i] = w2[i * 64 + lane];
-      const uint4 hb0 = make_uint4(hb[0], hb[1], hb[2], hb[3]), hb1 = make_uint4(hb[4], hb[5], hb[6], hb[7]);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        y[i & 7] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(i < 8 ? &hb0 : &hb1),
-                                                           *reinterpret_cast<const bf16x8_t*>(&wf[i % FF_PF]), y[i & 7], 0, 0, 0);
-        if (i + FF_PF < 16) wf[i % FF_PF] = w2[(i + FF_PF) * 64 + lane];
-      }
+#ifdef SL_FFN_PHASE_FORMS
+#define SL_FFN_PHASE_BODY
+#include "experiments/ffn_pipe_forms.inc"      // phase A: 16 x { fc1 MFMA, one element's GELU }; phase B: the 16 fc2 MFMAs
+#undef SL_FFN_PHASE_BODY
+#else
+      static_assert(UNI, "the phase forms are experiments/ffn_pipe_forms.inc (EXPERIMENTS and DEBUG_HOOKS builds)");
+#endif
     }
 #ifdef SL_PROBE
     FP_STAMP(p4);
@@ -585,38 +469,21 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void ffn_pipe_kerne
 #endif
   // ---- epilogue: as ffn_fused_kernel (WAVES x 16 KB staging = the 2 * NS weight slots)
   __syncthreads();
-  constexpr int RS = FF_D * 2;
-  char* st = lds + wave * (32 * RS);
-#pragma unroll
-  for (int n = 0; n < 8; ++n) {
-    const float bvv = b2s[n * 32 + lr];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
-      *reinterpret_cast<bf16*>(st + r * RS + (n * 32 + lr) * 2) = __float2bfloat16(y[n][e] + bvv);
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  stage_rows(lds, wave, y, p.b2s, lr, lh);
+  stage_sync();
   if constexpr (!ZOUT) {
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      const int rl = it * 2 + lh;
-      const long r = row0 + rl;
-      if (r >= row_end) continue;
-      const uint4 yv = *reinterpret_cast<const uint4*>(st + rl * RS + lr * 16);
-      const uint4 xv = ld16(X + r * FF_D + lr * 8);
-      const unsigned int yu[4] = {yv.x, yv.y, yv.z, yv.w}, xu[4] = {xv.x, xv.y, xv.z, xv.w};
-      unsigned int ou[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        ou[q] = pack_bf16x2(__uint_as_float(yu[q] << 16) + __uint_as_float(xu[q] << 16),
-                            __uint_as_float(yu[q] & 0xffff0000u) + __uint_as_float(xu[q] & 0xffff0000u));
-      st_stream16(out + r * FF_D + lr * 8, make_uint4(ou[0], ou[1], ou[2], ou[3]));
-    }
+    store_rows(lds, wave, X, out, row0, row_end, lr, lh);
   } else {
+    // ZOUT (round 6): the launch also does the NEXT layer's pre-attention LayerNorm (_EmformerLayer.layer_norm_input,
+    // torchaudio_models/emformer.py:431-452: feed-forward -> residual -> next layer's pre-LN) and its segment summaries (:163-167, the
+    // AvgPool1d of the normalised utterance rows), i.e. what simulst_emformer_prenorm did in a launch of its own: the epilogue holds every
+    // output row whole (32 lanes x 8 columns), so the row's statistics are one 32-lane reduction, the normalised row goes to its place in
+    // the next layer's Z buffer and a wave's 32 rows are exactly two 16-row segments.  For that the workgroups tile every utterance on
+    // its own (rows_x = n_rc + T rows, n_rc a multiple of 32): a wave never straddles two utterances or two segments.
     // ---- the same rows, plus the next layer's LayerNorm of each and the segment summaries.  No lane leaves the loop: the reductions
     //      need the whole wave (a row past the utterance's end is computed on zeros and stored nowhere)
+    constexpr int RS = FF_RS;
+    char* st = lds + wave * (32 * RS);
     float g8[8], b8[8];
     {
       const float4 ga = *reinterpret_cast<const float4*>(z.g + lr * 8), gb = *reinterpret_cast<const float4*>(z.g + lr * 8 + 4);
@@ -652,13 +519,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void ffn_pipe_kerne
       const uint4 yv = *reinterpret_cast<const uint4*>(st + rl * RS + lr * 16);
       uint4 xv = make_uint4(0, 0, 0, 0);
       if (rok) xv = ld16(X + r * FF_D + lr * 8);
-      const unsigned int yu[4] = {yv.x, yv.y, yv.z, yv.w}, xu[4] = {xv.x, xv.y, xv.z, xv.w};
-      unsigned int ou[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        ou[q] = pack_bf16x2(__uint_as_float(yu[q] << 16) + __uint_as_float(xu[q] << 16),
-                            __uint_as_float(yu[q] & 0xffff0000u) + __uint_as_float(xu[q] & 0xffff0000u));
-      if (rok) st_stream16(out + r * FF_D + lr * 8, make_uint4(ou[0], ou[1], ou[2], ou[3]));
+      const uint4 ov = add_residual(yv, xv);
+      if (rok) st_stream16(out + r * FF_D + lr * 8, ov);
+      const unsigned int ou[4] = {ov.x, ov.y, ov.z, ov.w};
 #pragma unroll
       for (int q = 0; q < 4; ++q) { o[it][2 * q] = __uint_as_float(ou[q] << 16); o[it][2 * q + 1] = __uint_as_float(ou[q] & 0xffff0000u); }
       red[it] = ((o[it][0] + o[it][1]) + (o[it][2] + o[it][3])) + ((o[it][4] + o[it][5]) + (o[it][6] + o[it][7]));
@@ -756,275 +619,47 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void ffn_pipe_kerne
   }
 }
 
-
-#ifdef SL_EXPERIMENTS     // 64 rows per wave, one 4-wave workgroup per compute unit: 0.52-0.54 PFLOP/s against 0.87 (profiles/r04_ffn_bench_wide.json)
-// ---------------------------------------------------------------------------------------------------------------------------------------
-// WIDE form (round 4, third form): 64 rows per wave -- RT = 2 row tiles of 32 -- in ONE 4-wave workgroup per compute unit (one wave per
-// SIMD, 512 registers).  Every weight fragment a wave reads from LDS then feeds TWO MFMAs (one per row tile): the uniform form's third
-// budget, the LDS reads of the fragments (8 waves x 32 KB per compute unit and iteration), is halved, and so is the number of waves
-// sharing the SIMD's vector issue.  The schedule is the uniform one scaled by RT: per iteration 32 RT MFMAs
-//   fc1 of tile t + 1 (16 k-steps x RT)  |  fc2 k-step 0 of tile t (8 column tiles x RT)  |  fc2 k-step 1 of tile t (8 x RT)
-// each followed by a quarter of the GELU of one element pair of one row tile: pairs 2 .. 5 of tile t behind the fc1 MFMAs, pairs 6, 7
-// behind fc2's k-step 0, pairs 0, 1 of tile t + 1 behind k-step 1 (row tiles alternate inside a pair index).  With one wave per SIMD
-// nothing else hides a stall, so the weight rings are four slots deep and tiles are requested two iterations ahead (counted vmcnt).
-// fc2's accumulators (RT x 8 x 16 = 256 registers) live in the AGPR half of the file.  Arithmetic and rounding points unchanged.
-struct FWG {
-  static constexpr int THREADS = 256, NS = 4, AHEAD = 2, PIECES = FP_W / (THREADS * 16);
-  static constexpr int LDS = 2 * NS * FP_W + 3072 + 2048 * 4;
-};
-
-template <int RT>
-__global__ __launch_bounds__(256, 1) void ffn_wide_kernel(
-    const bf16* __restrict__ X, const float* __restrict__ ln_g, const float* __restrict__ ln_b, const bf16* __restrict__ W1p,
-    const float* __restrict__ b1, const bf16* __restrict__ W2p, const float* __restrict__ b2, bf16* __restrict__ out, long M, int F) {
-  constexpr int NS = FWG::NS, AH = FWG::AHEAD;
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  char* w1ring = lds;
-  char* w2ring = lds + NS * FP_W;
-  float* lng = reinterpret_cast<float*>(lds + 2 * NS * FP_W);
-  float* lnb = lng + FF_D;
-  float* b2s = lnb + FF_D;
-  float* b1s = b2s + FF_D;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 31, lh = lane >> 5;
-  const long row0 = (long)blockIdx.x * (32 * RT * 4) + wave * (32 * RT);
-  const int nt = F / 32;
-  const unsigned voff = (unsigned)tid * 16u;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  stage_tile<4>(W1p, 0, w1ring, voff, wave_u);
-  stage_tile<4>(W2p, 0, w2ring, voff, wave_u);
-#pragma unroll
-  for (int a = 1; a <= AH; ++a) {
-    if (a < nt) stage_tile<4>(W1p, a, w1ring + (a % NS) * FP_W, voff, wave_u);
-    if (a < AH && a < nt) stage_tile<4>(W2p, a, w2ring + (a % NS) * FP_W, voff, wave_u);
-  }
-  for (int k = tid; k < FF_D; k += 256) { lng[k] = ln_g[k]; lnb[k] = ln_b[k]; b2s[k] = b2[k]; }
-  for (int k = tid; k < F; k += 256) b1s[k] = 0.5f * b1[k];                  // half the bias (gelu_q1)
-  uint4 xa[RT][16];
-#pragma unroll
-  for (int r = 0; r < RT; ++r) {
-    const long rr = row0 + r * 32 + lr;
-    const bool ok = rr < M;
-    const bf16* xr = X + (ok ? rr : 0) * FF_D + lh * 8;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const uint4 v = ld16(xr + s * 16);
-      xa[r][s] = make_uint4(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < RT; ++r) {
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) moments_mid(xa[r][s], s1, s2, bf16());
-    s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
-    const float mean = s1 * (1.0f / FF_D);
-    const float rstd = 1.0f / sqrtf(fmaxf(s2 * (1.0f / FF_D) - mean * mean, 0.f) + 1e-5f);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) xa[r][s] = ln_frag_mid(xa[r][s], mean, rstd, lng, lnb, s * 16 + lh * 8, bf16());
-  }
-  f32x16 y[RT][8];
-#pragma unroll
-  for (int r = 0; r < RT; ++r)
-#pragma unroll
-    for (int n = 0; n < 8; ++n)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) y[r][n][e] = 0.f;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  f32x16 hcur[RT];
-#pragma unroll
-  for (int r = 0; r < RT; ++r)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) hcur[r][e] = 0.f;
-  {
-    const uint4* w1 = reinterpret_cast<const uint4*>(w1ring);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const uint4 wf = w1[s * 64 + lane];
-#pragma unroll
-      for (int r = 0; r < RT; ++r)
-        hcur[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(&wf),
-                                                          *reinterpret_cast<const bf16x8_t*>(&xa[r][s]), hcur[r], 0, 0, 0);
-    }
-  }
-  // packed GELU outputs (fc2's A operand) per row tile: [r][0] = elements 0 .. 7 (k-step 0), [r][1] = elements 8 .. 15
-  uint4 hbv[RT][2];
-  float4 bv_carry;
-  {
-    const float* bt0 = b1s + 4 * lh;
-    const float4 b0 = *reinterpret_cast<const float4*>(bt0);
-#pragma unroll
-    for (int r = 0; r < RT; ++r) {
-      unsigned int* hb = reinterpret_cast<unsigned int*>(hbv[r]);
-      GeluPair g0;
-      gelu_q1(g0, hcur[r][0], hcur[r][1], b0.x, b0.y); gelu_q2(g0); gelu_q3(g0); hb[0] = gelu_q4(g0);
-      gelu_q1(g0, hcur[r][2], hcur[r][3], b0.z, b0.w); gelu_q2(g0); gelu_q3(g0); hb[1] = gelu_q4(g0);
-    }
-    bv_carry = *reinterpret_cast<const float4*>(bt0 + 8);
-  }
-  auto iteration = [&](int t, auto more_tag) {
-    constexpr bool MORE = decltype(more_tag)::value;
-    if (t == 0 || t + AH + 1 > nt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * FWG::PIECES) : "memory");
-    __syncthreads();
-    if (t + 1 + AH < nt) stage_tile<4>(W1p, t + 1 + AH, w1ring + ((t + 1 + AH) % NS) * FP_W, voff, wave_u);
-    if (t + AH < nt) stage_tile<4>(W2p, t + AH, w2ring + ((t + AH) % NS) * FP_W, voff, wave_u);
-    const uint4* w1 = reinterpret_cast<const uint4*>(w1ring + ((t + 1) % NS) * FP_W);    // fc1 weights of tile t + 1
-    const uint4* w2 = reinterpret_cast<const uint4*>(w2ring + (t % NS) * FP_W);          // fc2 weights of tile t
-    const float* bt = b1s + t * 32 + 4 * lh;
-    f32x16 hnext[RT];
-#pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) hnext[r][e] = 0.f;
-    uint4 wfa[FF_PF];
-    if constexpr (MORE) {
-#pragma unroll
-      for (int i = 0; i < FF_PF; ++i) wfa[i] = w1[i * 64 + lane];
-    }
-    float4 bv = bv_carry;                                       // half-bias of elements 4 .. 7 (pairs 2, 3)
-    GeluPair gp;
-    // one quarter of job (pair, row tile) -- q 0 .. 3; src = the fc1 accumulator holding the pair; nxt = bias group to fetch afterwards
-    auto quarter = [&](int q, int pair, int r, const f32x16& src, const float* nxt_bias, float4& dst_bias, bool fetch) {
-      if (q == 0) gelu_q1(gp, src[2 * pair], src[2 * pair + 1], (pair & 1) ? bv.z : bv.x, (pair & 1) ? bv.w : bv.y);
-      else if (q == 1) { gelu_q2(gp); if (fetch) dst_bias = *reinterpret_cast<const float4*>(nxt_bias); }
-      else if (q == 2) gelu_q3(gp);
-      else reinterpret_cast<unsigned int*>(hbv[r])[pair] = gelu_q4(gp);
-    };
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k = 0; k < 16 * RT; ++k) {                         // fc1 of tile t + 1
-      const int s = k / RT, r = k % RT;
-      if constexpr (MORE)
-        hnext[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(&wfa[s % FF_PF]),
-                                                           *reinterpret_cast<const bf16x8_t*>(&xa[r][s]), hnext[r], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (MORE) { if (r == RT - 1 && s + FF_PF < 16) wfa[s % FF_PF] = w1[(s + FF_PF) * 64 + lane]; }
-      const int j = k / 4, pair = 2 + j / RT, jr = j % RT;      // pairs 2 .. 5 of tile t
-      quarter(k % 4, pair, jr, hcur[jr], bt + 8 * ((pair + 1) >> 1), bv, (pair & 1) && jr == RT - 1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    uint4 wf[FF_PF];
-#pragma unroll
-    for (int i = 0; i < FF_PF; ++i) wf[i] = w2[i * 64 + lane];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k = 0; k < 16 * RT; ++k) {                         // fc2 of tile t: k-step 0 (i < 8), then k-step 1
-      const int i = k / RT, r = k % RT;
-      y[r][i & 7] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(&hbv[r][i >> 3]),
-                                                            *reinterpret_cast<const bf16x8_t*>(&wf[i % FF_PF]), y[r][i & 7], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (r == RT - 1 && i + FF_PF < 16) wf[i % FF_PF] = w2[(i + FF_PF) * 64 + lane];
-      if (k < 8 * RT) {
-        const int j = k / 4, pair = 6 + j / RT, jr = j % RT;    // pairs 6, 7 of tile t; then the half-bias of tile t + 1, elements 0 .. 3
-        quarter(k % 4, pair, jr, hcur[jr], bt + 32, bv, MORE && pair == 7 && jr == RT - 1);
-      } else if constexpr (MORE) {
-        const int j = (k - 8 * RT) / 4, pair = j / RT, jr = j % RT;   // pairs 0, 1 of tile t + 1: their registers were read by k-step 0
-        quarter(k % 4, pair, jr, hnext[jr], bt + 32 + 8, bv_carry, pair == 1 && jr == RT - 1);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (MORE) {
-#pragma unroll
-      for (int r = 0; r < RT; ++r) hcur[r] = hnext[r];
-    }
-  };
-  for (int t = 0; t + 1 < nt; ++t) iteration(t, std::true_type());
-  iteration(nt - 1, std::false_type());
-  // ---- epilogue: as ffn_pipe_kernel, 64 rows per wave (4 x 32 KB staging = the 2 * NS weight slots)
-  __syncthreads();
-  constexpr int RS = FF_D * 2;
-  char* st = lds + wave * (32 * RT * RS);
-#pragma unroll
-  for (int r = 0; r < RT; ++r)
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-      const float bvv = b2s[n * 32 + lr];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int rw = r * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-        *reinterpret_cast<bf16*>(st + rw * RS + (n * 32 + lr) * 2) = __float2bfloat16(y[r][n][e] + bvv);
-      }
-    }
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int it = 0; it < 16 * RT; ++it) {
-    const int rl = it * 2 + lh;
-    const long r = row0 + rl;
-    if (r >= M) continue;
-    const uint4 yv = *reinterpret_cast<const uint4*>(st + rl * RS + lr * 16);
-    const uint4 xv = ld16(X + r * FF_D + lr * 8);
-    const unsigned int yu[4] = {yv.x, yv.y, yv.z, yv.w}, xu[4] = {xv.x, xv.y, xv.z, xv.w};
-    unsigned int ou[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      ou[q] = pack_bf16x2(__uint_as_float(yu[q] << 16) + __uint_as_float(xu[q] << 16),
-                          __uint_as_float(yu[q] & 0xffff0000u) + __uint_as_float(xu[q] & 0xffff0000u));
-    st_stream16(out + r * FF_D + lr * 8, make_uint4(ou[0], ou[1], ou[2], ou[3]));
-  }
-}
-
-#endif  // SL_EXPERIMENTS
-
 }  // namespace
 
 int sl_launch_ffn_pipe(simulst_handle* h, const void* x, const float* ln_g, const float* ln_b, const void* w1p, const float* b1,
                        const void* w2p, const float* b2, void* out, long rows, int F, sl_ffn_variant v, const sl_ffn_z* zout) {
-  // (ffn_variant.h has already mapped forms this build lacks onto the shipped one: 4 waves, a quarter of an element pair's GELU behind
-  // each of the 32 MFMAs of an iteration, SIMULST_OPT_FFN_WAVES 43)
-  static const sl_lds_limit limits[] = {
-      {(const void*)ffn_pipe_kernel<4, false, true, true>, FPG<4>::LDS},
-      {(const void*)ffn_pipe_kernel<4, false, true, true, true>, FPG<4>::LDS},
-      {(const void*)ffn_pipe_kernel<4, false, true, true, true, true>, FPG<4>::LDS},
+  // One row per form this build has.  key: waves | packed | uniform as sl_decode_ffn_variant gives them (ffn_variant.h has already
+  // mapped forms this build lacks onto the shipped one, 401 = SIMULST_OPT_FFN_WAVES 43; a packed form has no uniform variants), + 1000
+  // with the next layer's LayerNorm + summaries in the epilogue (ZOUT), + 2000 with its Q | K | V projection as well (QOUT)
+  using kernel_t = void (*)(const bf16*, const float*, const float*, const bf16*, const float*, const bf16*, const float*, bf16*, long, int, sl_ffn_z);
+  static const struct { int key; kernel_t kernel; int lds, rows; } forms[] = {
+      {401, ffn_pipe_kernel<4, false, true, true>, FPG<4>::LDS, 128},                   // 43: uniform GELU, LDS-DMA pieces one per MFMA gap
+      {1401, ffn_pipe_kernel<4, false, true, true, true>, FPG<4>::LDS, 128},
+      {2401, ffn_pipe_kernel<4, false, true, true, true, true>, FPG<4>::LDS, 128},
 #ifdef SL_EXPERIMENTS
-      {(const void*)ffn_pipe_kernel<4, false, true, false>, FPG<4>::LDS},
-      {(const void*)ffn_pipe_kernel<4, false, false>, FPG<4>::LDS},
-      {(const void*)ffn_pipe_kernel<8, false, false>, FPG<8>::LDS},
-      {(const void*)ffn_pipe_kernel<8, false, true>, FPG<8>::LDS},
-      {(const void*)ffn_wide_kernel<2>, FWG::LDS},
-      {(const void*)ffn_pipe_kernel<8, false, true, true>, FPG<8>::LDS},
+      {403, ffn_pipe_kernel<4, false, true, false>, FPG<4>::LDS, 128},                  // 47: the pieces as a burst behind the barrier
+      {400, ffn_pipe_kernel<4, false, false>, FPG<4>::LDS, 128},                        // 41: GELU as a phase
+      {800, ffn_pipe_kernel<8, false, false>, FPG<8>::LDS, 256},                        // 81
+      {801, ffn_pipe_kernel<8, false, true>, FPG<8>::LDS, 256},                         // 83: 8 waves, burst
+      {803, ffn_pipe_kernel<8, false, true, true>, FPG<8>::LDS, 256},                   // 87: 8 waves, spread
+      {402, ffn_wide_kernel<2>, FWG::LDS, 256},                                         // 45: 64 rows per wave
 #endif
 #ifdef SL_DEBUG_HOOKS
-      {(const void*)ffn_pipe_kernel<4, true, false>, FPG<4>::LDS},
-      {(const void*)ffn_pipe_kernel<8, true, false>, FPG<8>::LDS},
+      {410, ffn_pipe_kernel<4, true, false>, FPG<4>::LDS, 128},                         // 42 / 82: packed GELU as a phase
+      {810, ffn_pipe_kernel<8, true, false>, FPG<8>::LDS, 256},
 #endif
   };
-  if (int rc = sl_raise_lds(h, SL_LDS_FFN_PIPE, limits, "simulst_emformer_ffn(pipelined)")) return rc;
-  if (zout) {      // the shipped form with the next layer's LayerNorm + summaries in its epilogue; workgroups tile each utterance
-    const long nb = rows / zout->rows_x;
-    if (zout->QKV)
-      hipLaunchKernelGGL((ffn_pipe_kernel<4, false, true, true, true, true>), dim3((unsigned)(nb * zout->tiles)), dim3(256), FPG<4>::LDS, h->stream,
-                         (const bf16*)x, ln_g, ln_b, (const bf16*)w1p, b1, (const bf16*)w2p, b2, (bf16*)out, rows, F, *zout);
-    else
-      hipLaunchKernelGGL((ffn_pipe_kernel<4, false, true, true, true>), dim3((unsigned)(nb * zout->tiles)), dim3(256), FPG<4>::LDS, h->stream,
-                         (const bf16*)x, ln_g, ln_b, (const bf16*)w1p, b1, (const bf16*)w2p, b2, (bf16*)out, rows, F, *zout);
-    return sl_launch_status(h, "simulst_emformer_ffn_prenorm");
+  constexpr int NF = sizeof(forms) / sizeof(forms[0]);
+  if (!h->lds_raised[SL_LDS_FFN_PIPE]) {
+    sl_lds_limit limits[NF];
+    for (int i = 0; i < NF; ++i) limits[i] = {(const void*)forms[i].kernel, forms[i].lds};
+    if (int rc = sl_raise_lds(h, SL_LDS_FFN_PIPE, limits, "simulst_emformer_ffn(pipelined)")) return rc;
   }
+  const int key = zout ? (zout->QKV ? 2401 : 1401) : v.waves * 100 + (v.packed ? 10 : v.uniform);
+  int f = 0;
+  while (f < NF && forms[f].key != key) ++f;
+  SL_REQUIRE(h, f < NF, SIMULST_E_ARG, "simulst_emformer_ffn(pipelined): no such form in this build");
+  // ZOUT: workgroups tile each utterance on its own
+  const long groups = zout ? rows / zout->rows_x * zout->tiles : (rows + forms[f].rows - 1) / forms[f].rows;
   const sl_ffn_z noz = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr};
-#define FPL(W, P, U, ...)                                                                                                           \
-  hipLaunchKernelGGL((ffn_pipe_kernel<W, P, U, ##__VA_ARGS__>), dim3((unsigned)((rows + 32 * W - 1) / (32 * W))), dim3(64 * W), FPG<W>::LDS, h->stream, \
-                     (const bf16*)x, ln_g, ln_b, (const bf16*)w1p, b1, (const bf16*)w2p, b2, (bf16*)out, rows, F, noz)
-#ifdef SL_DEBUG_HOOKS
-  if (v.packed) { if (v.waves == 8) FPL(8, true, false); else FPL(4, true, false); } else
-#endif
-#ifdef SL_EXPERIMENTS
-  if (v.uniform == 2) {
-    hipLaunchKernelGGL((ffn_wide_kernel<2>), dim3((unsigned)((rows + 255) / 256)), dim3(256), FWG::LDS, h->stream, (const bf16*)x, ln_g, ln_b,
-                       (const bf16*)w1p, b1, (const bf16*)w2p, b2, (bf16*)out, rows, F);
-  } else
-  // 43: the shipped form (uniform GELU, LDS-DMA pieces one per MFMA gap); 47: the same with the pieces as a burst behind the barrier;
-  // 83 / 87: 8 waves, burst / spread
-  if (v.uniform == 3) { if (v.waves == 8) FPL(8, false, true, true); else FPL(4, false, true, false); }
-  else if (v.uniform) { if (v.waves == 8) FPL(8, false, true, false); else FPL(4, false, true, true); }
-  else { if (v.waves == 8) FPL(8, false, false); else FPL(4, false, false); }
-#else
-  FPL(4, false, true, true);
-#endif
-#undef FPL
+  hipLaunchKernelGGL(forms[f].kernel, dim3((unsigned)groups), dim3(64 * v.waves), forms[f].lds, h->stream, (const bf16*)x, ln_g, ln_b,
+                     (const bf16*)w1p, b1, (const bf16*)w2p, b2, (bf16*)out, rows, F, zout ? *zout : noz);
+  if (zout) return sl_launch_status(h, "simulst_emformer_ffn_prenorm");
 #ifdef SL_PROBE
   {
     const int waves = v.waves, packed = v.packed;
