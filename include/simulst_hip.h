@@ -367,7 +367,16 @@ int simulst_segment_mean(simulst_handle* h, const void* X, const int32_t* length
  * (n_mem_valid[b] newest rows valid), lc_k/lc_v [B][Lc][D] ring of the last Lc projected
  * utterance rows of which lc_valid[b] are valid (oldest first).
  * Replaces _EmformerAttention._forward_impl/_gen_attention_probs + the mask of
- * Emformer._gen_attention_mask (torchaudio_models/emformer.py:127-219,259-318,711-793). */
+ * Emformer._gen_attention_mask (torchaudio_models/emformer.py:127-219,259-318,711-793).
+ * Any S, R, Lc, M is accepted (head_dim <= 64).  With nk_max = (use_summary ? M : 0) + R + Lc + S and
+ * nq_max = R + S + use_summary, three kernel classes serve a call:
+ *   one-tile MFMA : bf16, head_dim 64, nq_max <= 32, nk_max <= 64 (P rounded to bf16 once, fp32 denominator)
+ *   VALU          : every other call with nk_max <= 128: all keys of a segment in LDS, one or two per lane, fp32 throughout
+ *   blocked       : nk_max > 128: the key list walked in blocks under an online softmax -- bf16 at head_dim 64 on the
+ *                   matrix cores (query blocks of 32 x key blocks of 64, same roundings as the one-tile MFMA kernel), everything
+ *                   else in the VALU scheme over key blocks of 128; no bound on nk_max or nq_max.  Its only limit:
+ *                   one utterance's QKV block must stay below 2^31 elements (32-bit row offsets), SIMULST_E_SHAPE otherwise.
+ * SIMULST_OPT_VALU_ATTENTION routes bf16 calls to the VALU scheme in every class. */
 typedef struct {
   int32_t B, T, D, H, S, R, Lc, M;
   int32_t n_mem, n_seg;         /* rows in the memory block, segments (= rc blocks = summaries) */

@@ -398,3 +398,7 @@ int sl_beam_reorder(simulst_handle* h, const char* who, const simulst_dec_layer*
 int sl_emformer_attention_mfma(simulst_handle* h, const simulst_emf_attn_desc* d, const void* QKV,
                                const int32_t* lengths, const void* lc_k, const void* lc_v, const int32_t* lc_valid,
                                const int32_t* n_mem_valid, void* CTX);
+// segments of more than 128 keys (emformer_attn_tiled.hip): tiled MFMA form or looped general form
+int sl_emformer_attention_tiled(simulst_handle* h, const simulst_emf_attn_desc* d, const void* QKV,
+                                const int32_t* lengths, const void* lc_k, const void* lc_v, const int32_t* lc_valid,
+                                const int32_t* n_mem_valid, void* CTX);

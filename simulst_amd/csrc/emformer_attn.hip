@@ -6,6 +6,8 @@
 // v_readlane), wave-level fp32 softmax, ONE CHANNEL PER LANE for PV.  The T x T mask of the
 // reference (Emformer._gen_attention_mask) is never materialised: key ranges are computed
 // from (i, S, R, Lc, M, len_b).
+// This kernel serves segments of up to 128 keys (one or two per lane); bf16 segments of <= 32 queries x <= 64 keys at head_dim 64
+// go to emformer_attn_mfma.hip, and segments of more than 128 keys to the blocked kernels of emformer_attn_tiled.hip.
 #include "common.h"
 
 namespace {
@@ -145,8 +147,10 @@ extern "C" int simulst_emformer_attention(simulst_handle* h, const simulst_emf_a
   SL_REQUIRE(h, (lc_k == nullptr) == (lc_v == nullptr), SIMULST_E_ARG, "simulst_emformer_attention: lc_k/lc_v");
   SL_REQUIRE(h, lc_k == nullptr || d->n_seg == 1, SIMULST_E_SHAPE, "simulst_emformer_attention: streaming needs one segment");
   const int nk_max = (d->use_summary ? d->M : 0) + d->R + d->Lc + d->S;
-  SL_REQUIRE(h, nk_max <= 128, SIMULST_E_SHAPE, "simulst_emformer_attention: M+R+Lc+S must be <= 128");
   if (d->B <= 0) return SIMULST_OK;
+  // more than 128 keys per segment: the key list is walked in blocks (emformer_attn_tiled.hip); everything below is the
+  // all-keys-at-once dispatch
+  if (nk_max > 128) return sl_emformer_attention_tiled(h, d, QKV, lengths, lc_k, lc_v, lc_valid, n_mem_valid, CTX);
   // bf16, head_dim 64, <= 32 queries x <= 64 keys per segment: the MFMA kernel (emformer_attn_mfma.hip)
   {
     const int nq_max = d->R + d->S + (d->use_summary ? 1 : 0);

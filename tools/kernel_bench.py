@@ -4,9 +4,14 @@ process is what counts: cdna_hip_programming.md section 5.4 rule 24).
 
     python tools/kernel_bench.py emf_attn [--utterances 448 4096]
     python tools/kernel_bench.py self_attn [--utterances 448 4096] [--n-prev 55 109]
+    python tools/kernel_bench.py emformer_attn --geometry 64,8,48,8 --geometry 64,8,64,8 [--utterances 256 1280] [--rows 250]
 
 emf_attn: simulst_emformer_attention on the offline layout (T = 250 rows after the stride-4 subsampler, S = 16, R = 8, Lc = 32,
 M = 5, 4 heads x 64): bytes = every Q / K / V row of the launch read once + the context rows written.
+emformer_attn: the same launch at chosen segment geometries S,R,Lc,M (encoder rows; bf16, 4 heads x 64; --valu: under
+OPT_VALU_ATTENTION; --dtype fp32), the geometries timed alternately in one process: time per attended (query, key, head) triple,
+the spread over the timed rounds, and the fractions of the HBM roofline (bytes as above) and of the bf16 matrix peak
+(4 x 64 FLOP per triple: both products).
 self_attn: simulst_decoder_self_attention, one new target row per utterance against n_prev cached rows (K / V caches
 [B][H][cap][d]); bytes = cached K and V rows read + the new row's q / k / v + context.
 """
@@ -52,6 +57,71 @@ def emf_attn(args, ops):
         nbytes = B * (rows_z * 3 * D + rows_c * D) * 2
         out[str(B)] = {"us": round(us, 1), "GBps": round(nbytes / us / 1e3, 1), "bytes": nbytes}
         print("emf_attn", B, out[str(B)], flush=True)
+    return out
+
+
+HBM_PEAK_BPS, MFMA_BF16_PEAK_FLOPS = 8.0e12, 2.5e15      # MI355X spec sheet
+
+
+def attention_triples(T, H, S, R, Lc, M):
+    """(query, key, head) triples one full-length utterance attends: per segment, its rc block | rows | summary against
+    memory | rc block | left context + segment rows, less the memory keys hidden from the summary query."""
+    n = 0
+    for i in range((T + S - 1) // S):
+        t0, t1 = i * S, min((i + 1) * S, T)
+        n_mem = min(i, M) if M > 0 else 0
+        nq, nk = R + (t1 - t0) + (1 if M > 0 else 0), n_mem + R + (t1 - max(0, t0 - Lc))
+        n += nq * nk - n_mem
+    return n * H
+
+
+def emformer_attn(args, ops):
+    from simulst_amd import _lib
+    T, D, H = args.rows, 256, 4
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    esize = 2 if args.dtype == "bf16" else 4
+    cases = []
+    for geo in args.geometry:
+        S, R, Lc, M = (int(v) for v in geo.split(","))
+        N = (T + S - 1) // S
+        n_mem, n_sum = (N - 1, N) if M > 0 else (0, 0)
+        rows_z, rows_c = n_mem + N * R + T + n_sum, N * R + T + n_sum
+        for B in args.utterances:
+            QKV = torch.randn(B, rows_z, 3 * D, device="cuda").to(dtype)
+            CTX = torch.zeros(B, rows_c, D, device="cuda", dtype=dtype)
+            lengths = torch.full((B,), T, dtype=torch.int32, device="cuda")
+            kw = dict(B=B, T=T, D=D, H=H, S=S, R=R, Lc=Lc, M=M, n_mem=n_mem, n_seg=N, use_summary=M > 0)
+            cases.append((f"{geo}x{B}", QKV, lengths, CTX, kw, B * attention_triples(T, H, S, R, Lc, M),
+                          B * (rows_z * 3 * D + rows_c * D) * esize))
+    ops.h.set_option(_lib.OPT_VALU_ATTENTION, int(args.valu))
+    try:
+        times = {c[0]: [] for c in cases}
+        for c in cases:                                   # warm up every shape
+            for _ in range(3):
+                ops.emformer_attention(c[1], c[2], c[3], **c[4])
+        torch.cuda.synchronize()
+        for _ in range(args.rounds):                      # alternate the shapes: drift hits them alike
+            for name, QKV, lengths, CTX, kw, _, _ in cases:
+                iters = max(10, min(200, int(2.5e5 // kw["B"])))
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    ops.emformer_attention(QKV, lengths, CTX, **kw)
+                e1.record(); torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1) * 1e3 / iters)
+    finally:
+        ops.h.set_option(_lib.OPT_VALU_ATTENTION, 0)
+    out = {}
+    for name, _, _, _, kw, triples, nbytes in cases:
+        t = sorted(times[name])
+        us = t[len(t) // 2]
+        out[name] = {"us": round(us, 1), "us_min": round(t[0], 1), "us_max": round(t[-1], 1), "triples": triples,
+                     "ps_per_triple": round(us * 1e6 / triples, 3), "ps_per_triple_min": round(t[0] * 1e6 / triples, 3),
+                     "ps_per_triple_max": round(t[-1] * 1e6 / triples, 3), "bytes": nbytes,
+                     "hbm_roofline_fraction": round(nbytes / HBM_PEAK_BPS / (us * 1e-6), 4),
+                     "mfma_bf16_peak_fraction": round(triples * 4 * (D // H) / MFMA_BF16_PEAK_FLOPS / (us * 1e-6), 4),
+                     "keys_per_segment": (kw["M"] if kw["use_summary"] else 0) + kw["R"] + kw["Lc"] + kw["S"]}
+        print("emformer_attn", name, out[name], flush=True)
     return out
 
 
@@ -188,15 +258,22 @@ def cross_attn(args, ops):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["emf_attn", "self_attn", "dec_chain", "cross_attn", "attn_chain"])
+    ap.add_argument("what", choices=["emf_attn", "emformer_attn", "self_attn", "dec_chain", "cross_attn", "attn_chain"])
     ap.add_argument("--utterances", type=int, nargs="+", default=[448, 4096])
     ap.add_argument("--n-prev", type=int, nargs="+", default=[55, 109])
     ap.add_argument("--keys", type=int, nargs="+", default=[250], help="cross_attn: encoder rows per utterance")
+    ap.add_argument("--geometry", action="append", help="emformer_attn: S,R,Lc,M in encoder rows; may be repeated")
+    ap.add_argument("--rows", type=int, default=250, help="emformer_attn: encoder rows per utterance")
+    ap.add_argument("--rounds", type=int, default=7, help="emformer_attn: timed rounds per shape")
+    ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
+    ap.add_argument("--valu", action="store_true", help="emformer_attn: under OPT_VALU_ATTENTION")
     ap.add_argument("--tag", default="")
     args = ap.parse_args()
+    if args.what == "emformer_attn" and not args.geometry:
+        ap.error("emformer_attn needs --geometry S,R,Lc,M")
     from simulst_amd.ops import Ops
     ops = Ops()
-    res = {"emf_attn": emf_attn, "self_attn": self_attn, "dec_chain": dec_chain, "cross_attn": cross_attn, "attn_chain": attn_chain}[args.what](args, ops)
+    res = {"emf_attn": emf_attn, "emformer_attn": emformer_attn, "self_attn": self_attn, "dec_chain": dec_chain, "cross_attn": cross_attn, "attn_chain": attn_chain}[args.what](args, ops)
     print(json.dumps({"kernel": args.what, "tag": args.tag, "device": torch.cuda.get_device_name(0), "results": res}))
 
 
