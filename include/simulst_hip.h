@@ -994,7 +994,11 @@ int simulst_transducer_pool(simulst_handle* h, const void* x, const int32_t* len
  *   best[b][s][p], best_idx[..] the largest logit of the part's columns other than `blank` and its lowest index
  *                               (-inf / INT32_MAX for a part without such a column)
  * Other positions of the outputs are not written; the [B][S][V] logits never exist.  Row tiles of 16 positions that lie wholly
- * outside the scanned range are skipped. */
+ * outside the scanned range are skipped.
+ * An OPEN source (simultaneous decoding): src_len[b] = -1 - a < 0 says that a pooled positions of row b are available so far
+ * (a clamped to [0, S]) and that more may follow (0 stays what it is, a closed source without a position, so the open count is
+ * offset by one: open with nothing available is -1).  The scanned range is then [clamp(prev_emit[b], 0, a), a) -- empty for
+ * a == 0 or prev_emit[b] >= a --, same arithmetic, same tile skipping.  src_len[b] >= 0 is the closed source described above. */
 int simulst_joiner_scan(simulst_handle* h, const float* P, const float* g, const void* W_fm, const int32_t* prev_emit,
                         const int32_t* src_len, float* blank_logit, float* best, int32_t* best_idx, int32_t B, int32_t S,
                         int32_t D, int32_t V, int32_t blank, int32_t n_split, int32_t dtype);
@@ -1002,7 +1006,10 @@ int simulst_joiner_scan(simulst_handle* h, const float* P, const float* g, const
 /* Emission (:170-209) from the scan's outputs: new_emit[b] = the first scanned s whose best non-blank logit beats the blank one
  * (ties go to the lower column, as torch.argmax), the blank logit taken as -1e4 at s = src_len[b] - 1.  prev_emit[b] <- new_emit[b],
  * z[b] = tanh(P[b][new_emit] + g[b]) in the model dtype ([B][D]; the returned vocabulary row is simulst_linear of it),
- * at_eos[b] = (new_emit[b] == src_len[b] - 1). */
+ * at_eos[b] = (new_emit[b] == src_len[b] - 1).
+ * An OPEN source (src_len[b] = -1 - a < 0, see simulst_joiner_scan): no position gets the forced blank.  If a scanned s in
+ * [clamp(prev_emit[b], 0, a), a) emits, the row does what a closed one does (same tie rule, prev_emit[b] <- s, z[b] written) with
+ * at_eos[b] = 0.  Otherwise the row WAITS for more source: prev_emit[b] and z[b] are not written and at_eos[b] = -1. */
 int simulst_joiner_emit(simulst_handle* h, const float* P, const float* g, const float* blank_logit, const float* best,
                         const int32_t* best_idx, int32_t* prev_emit, const int32_t* src_len, void* z, int32_t* at_eos, int32_t B,
                         int32_t S, int32_t D, int32_t V, int32_t blank, int32_t n_split, int32_t dtype);
@@ -1014,7 +1021,10 @@ int simulst_joiner_emit(simulst_handle* h, const float* P, const float* g, const
  * NULL the two calls ARE those.  Rows of a finished sentence (finished[r / group] != 0) scan nothing -- their row tiles are empty
  * and take no matrix-core work -- and the emission leaves their prev_emit, z and at_eos as they are.  emit_log (int32 [R], one
  * row of the caller's [L][R] table, may be NULL) also receives the new emit position of every row that ran.  SIMULST_E_ARG as
- * above, and for group < 1 or R % group != 0. */
+ * above, and for group < 1 or R % group != 0.
+ * An OPEN source (src_len[r / group] = -1 - a < 0) is read by both calls as by simulst_joiner_scan / simulst_joiner_emit: every
+ * row of the group scans [clamp(prev_emit[r], 0, a), a) without a forced position, and a row that waits keeps prev_emit[r] and
+ * z[r], gets at_eos[r] = -1 and emit_log[r] = -1.  (Beam search itself runs over closed sources only.) */
 int simulst_joiner_scan_beam(simulst_handle* h, const float* P, const float* g, const void* W_fm, const int32_t* prev_emit,
                              const int32_t* src_len, const int32_t* finished, float* blank_logit, float* best, int32_t* best_idx,
                              int32_t R, int32_t group, int32_t S, int32_t D, int32_t V, int32_t blank, int32_t n_split,
@@ -1037,8 +1047,8 @@ int simulst_transducer_beam_reorder(simulst_handle* h, const simulst_decoder_des
                                     const simulst_dec_layer* dst, const int32_t* prev_emit_src, int32_t* prev_emit_dst,
                                     const int32_t* reorder, const int32_t* finished, int32_t block, int32_t n_prev, int32_t* result);
 
-/* logits fp32 [B][V]: column `blank` of the rows with at_eos[b] != 0 becomes -1e4 (the row gathered at :203-206 keeps the
- * scatter of :176-180). */
+/* logits fp32 [B][V]: column `blank` of the rows with at_eos[b] > 0 becomes -1e4 (the row gathered at :203-206 keeps the
+ * scatter of :176-180); a row that waits on an open source (at_eos[b] = -1) is left alone. */
 int simulst_joiner_mask_blank(simulst_handle* h, float* logits, const int32_t* at_eos, int32_t B, int32_t V, int32_t blank);
 
 /* The joiner over a whole target (:143-163 with no incremental state, and what criterion/rnnt_criterion.py:82-147 reads from it):

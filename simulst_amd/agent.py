@@ -154,6 +154,17 @@ class FairseqSimulSTAgent:
                 "AL": average_lagging(delays, src.total_ms()), "n_enc": st.enc_rows if st is not None else 0}
 
 
+def chunk_positions(T: int, segment_length: int, right_context: int, stride_ms: int):
+    """Source frames offered after each READ (agents/default_agent.py:367,407: first segment + right context, then segments)."""
+    pos, out = 0, []
+    expected = (segment_length + right_context) * stride_ms // SHIFT_SIZE
+    while pos < T:
+        pos = min(pos + expected, T)
+        out.append(pos)
+        expected = segment_length * stride_ms // SHIFT_SIZE
+    return out
+
+
 def self_paced_records(hyp, delays, tok_chunk, n_prev, chunk_idx, cap, total_ms, extra_key, extra_of):
     """Host records of a self-paced run: the READ / WRITE string is rebuilt from the chunk index stamped on every token ("R" for
     every chunk the row took, then the tokens written at it); Average Lagging for all rows at once (latency.average_lagging_batch,
@@ -216,14 +227,7 @@ class BatchedStreamingAgent(FairseqSimulSTAgent):
         return self._run_batch_lockstep(fbank)
 
     def _chunk_positions(self, T: int):
-        """Source frames offered after each READ (agents/default_agent.py:367,407: first segment + right context, then segments)."""
-        pos, out = 0, []
-        expected = (self.segment_length + self.right_context) * self.stride_ms // SHIFT_SIZE
-        while pos < T:
-            pos = min(pos + expected, T)
-            out.append(pos)
-            expected = self.segment_length * self.stride_ms // SHIFT_SIZE
-        return out
+        return chunk_positions(T, self.segment_length, self.right_context, self.stride_ms)
 
     def _run_batch_self_paced(self, fbank: torch.Tensor, encoder: str = "chunked", lengths=None):
         from . import _lib

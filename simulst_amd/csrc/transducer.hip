@@ -8,7 +8,10 @@
 //                             the argmax of :191) -- the [B][S'][V] logits of the reference are never written
 //   simulst_joiner_emit       first scanned position whose best non-blank beats the blank, -1e4 blank at src_len' - 1 (:170-200);
 //                             prev_emit <- new_emit, z[b] = tanh(P[b, new_emit] + g[b]), at_eos[b]
-//   simulst_joiner_mask_blank logits[b][blank] <- -1e4 where at_eos[b] (the gathered row of :203-206 keeps the scatter of :176-180)
+//   simulst_joiner_mask_blank logits[b][blank] <- -1e4 where at_eos[b] > 0 (the gathered row of :203-206 keeps the scatter of :176-180)
+//   an OPEN source (simultaneous decoding): src_len[b] = -1 - a < 0 says that a pooled positions are available and more may follow;
+//                             the scan covers [prev_emit, a), no position is forced, and a row in which no scanned position emits
+//                             WAITS: prev_emit and z stay, at_eos[b] = -1 (include/simulst_hip.h)
 //   simulst_joiner_scan_beam / simulst_joiner_emit_beam   the same two kernels over R beam rows of which every `group` consecutive
 //                             ones share one source (P and src_len are read at r / group, never replicated); the rows of a finished
 //                             sentence scan nothing
@@ -46,6 +49,10 @@ template <> __device__ __forceinline__ float join_act<bf16>(float x) {
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// src_len of the scan / emit kernels: sl >= 0 a closed source of sl pooled positions; sl < 0 an OPEN source (more may follow) of
+// which -1 - sl positions are available so far.  Either way clamped to the buffer's S.
+__device__ __forceinline__ int open_len(int sl, int S) { return clampi(sl < 0 ? -1 - sl : sl, 0, S); }
 
 // (value, index) with torch.argmax's order: the larger value, on a tie the lower index
 __device__ __forceinline__ void take_better(float& v, int& i, float ov, int oi) {
@@ -115,8 +122,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void joiner_scan_kernel(
       const int t = gt - b * tiles_per_row;
       src = b / group;
       if (!(finished && finished[src])) {
-        const int len = clampi(src_len[src], 0, S);
-        const int pe = clampi(prev_emit[b], 0, len > 0 ? len - 1 : 0);
+        const int sl = src_len[src];
+        const int len = open_len(sl, S);
+        const int pe = clampi(prev_emit[b], 0, sl < 0 ? len : (len > 0 ? len - 1 : 0));    // an open row may have nothing left to scan
         lo = max(pe, 16 * t);
         hi = min(len, 16 * t + 16);
       }
@@ -244,23 +252,32 @@ __global__ __launch_bounds__(64) void joiner_emit_kernel(const float* __restrict
                                                          int n_split) {
   const int b = blockIdx.x, lane = threadIdx.x, src = b / group;     // row b of source b / group
   if (finished && finished[src]) return;                             // uniform over the workgroup: the row keeps prev_emit, z, at_eos
-  const int len = clampi(src_len[src], 0, S);
+  const int sl = src_len[src];
+  const bool open = sl < 0;                                  // no position is the source's last one yet: nothing is forced
+  const int len = open_len(sl, S);
   const int last = len > 0 ? len - 1 : 0;
-  const int pe = clampi(prev_emit[b], 0, last);
+  const int pe = clampi(prev_emit[b], 0, open ? len : last);
   int first = 0x7fffffff;
   for (int s = pe + lane; s < len; s += 64) {                // bounded by S
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int p = 0; p < n_split; ++p) take_better(bv, bi, best_in[((long)b * S + s) * n_split + p], idx_in[((long)b * S + s) * n_split + p]);
-    const float blank_v = s == last ? -1e4f : blank_in[(long)b * S + s];       // force emit at source eos (:170-180)
+    const float blank_v = (s == last && !open) ? -1e4f : blank_in[(long)b * S + s];      // force emit at source eos (:170-180)
     if (bv > blank_v || (bv == blank_v && bi < blank)) { first = s; break; }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+  if (open && first == 0x7fffffff) {                         // uniform over the workgroup: the row waits for more source and
+    if (lane == 0) {                                         // ... keeps prev_emit and z
+      at_eos[b] = -1;
+      if (emit_log) emit_log[b] = -1;
+    }
+    return;
+  }
   const int ne = first <= last ? first : last;
   if (lane == 0) {
     prev_emit[b] = ne;
-    at_eos[b] = ne == last ? 1 : 0;
+    at_eos[b] = (ne == last && !open) ? 1 : 0;
     if (emit_log) emit_log[b] = ne;
   }
   const float* pr = P + ((long)src * S + ne) * D;
@@ -276,7 +293,7 @@ __global__ __launch_bounds__(64) void joiner_emit_kernel(const float* __restrict
 
 __global__ void joiner_mask_blank_kernel(float* __restrict__ logits, const int32_t* __restrict__ at_eos, int B, int V, int blank) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B && at_eos[b]) logits[(long)b * V + blank] = -1e4f;
+  if (b < B && at_eos[b] > 0) logits[(long)b * V + blank] = -1e4f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- lattice

@@ -25,8 +25,13 @@ network over the whole target at once (``features_teacher_forced``), then simuls
 every (source position, target position) cell, the reference's [B, S', U + 1, V] logits never written -- and
 ``TransducerModel.score_reference`` adds simulst_rnnt_forward: the log-likelihood summed over all monotonic alignments, the best
 alignment with the frame each token is emitted at, and the "offline path" term.  Gradients (the training criterion), FastEmit (it
-acts on gradients only) and label smoothing are out of scope; so is the reference's rollback (:214-239, not callable as
-written).
+acts on gradients only) and label smoothing are out of scope.
+
+Simultaneous decoding (``open_source`` / ``append_source`` / ``step_online``; the agents are in simulst_amd/transducer_agent.py):
+the source grows window by window and the scan / emit kernels are told so by a negative src_len (-1 - available positions): no
+position is forced, and a row in which none of the available positions emits WAITS -- prev_emit, z and its target position stay.
+That is the case the reference's rollback (:214-239, not callable as written) exists for; here nothing is rolled back, the step
+commits per row.  What is written this way is what ``greedy_offline`` writes; only the delays are new.
 """
 import math
 from typing import Dict, List, Optional
@@ -179,9 +184,12 @@ class TransducerDecoder:
             st.grow(2 * st.cap)
 
     def greedy_offline(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, n_steps: int, mask_eos: bool = False,
-                       T: Optional[int] = None):
-        """Batched greedy decode (beam 1; pad never, EOS masked at the first step as SequenceGenerator's min_len 1).
-        Returns (tokens [B, n_steps] int64, emit [B, n_steps] int32 -- the pooled frame each token was emitted at, state)."""
+                       T: Optional[int] = None, *, mask_first_eos: bool = True, until_all_eos: bool = False):
+        """Batched greedy decode (beam 1; pad never, EOS masked at the first step as SequenceGenerator's min_len 1 unless
+        mask_first_eos=False).  Returns (tokens [B, n_steps] int64, emit [B, n_steps] int32 -- the pooled frame each token was
+        emitted at, state).  until_all_eos: the loop looks every 8 steps whether every row has written an EOS and stops there;
+        the returned tokens / emit then have that many columns (the simultaneous evaluation form, which cuts every row at its
+        EOS anyway)."""
         cfg, ops = self.cfg, self.ops
         B = enc_btd.size(0)
         st = self.new_state(B, cap=n_steps + 2)
@@ -189,12 +197,165 @@ class TransducerDecoder:
         toks = torch.full((B,), BLANK, device=self.device, dtype=torch.int64)
         out = torch.empty(n_steps, B, device=self.device, dtype=torch.int64)
         emit = torch.empty(n_steps, B, device=self.device, dtype=torch.int32)
+        n_done = n_steps
         for s in range(n_steps):
             logits = self.step(st, toks)
-            toks = ops.greedy_argmax(logits, pad_idx=cfg.padding_idx, eos_idx=cfg.eos, mask_eos=mask_eos or s == 0, out=out[s])
+            toks = ops.greedy_argmax(logits, pad_idx=cfg.padding_idx, eos_idx=cfg.eos, mask_eos=mask_eos or (mask_first_eos and s == 0),
+                                     out=out[s])
             emit[s].copy_(st.prev_emit)
             self.commit(st)
-        return out.t().contiguous(), emit.t().contiguous(), st
+            if until_all_eos and s % 8 == 7 and bool((out[:s + 1] == cfg.eos).any(0).all().item()):
+                n_done = s + 1
+                break
+        return out[:n_done].t().contiguous(), emit[:n_done].t().contiguous(), st
+
+    # ------------------------------------------------------------------ a source that grows (simultaneous decoding)
+    def open_source(self, st: TransducerState, S_cap: int):
+        """Start an OPEN source of up to S_cap pooled positions (more make the buffers grow): P, the scan buffers and z are
+        allocated, no position is available yet (st.avail = 0) and every row is open (st.open = 1).  The kernels read
+        st.src_len = -1 - avail for an open row (include/simulst_hip.h: nothing is forced, a row may wait), avail for a closed one."""
+        B, D, dev = st.B, self.cfg.embed_dim, self.device
+        S_cap = max(int(S_cap), 1)
+        st.P = torch.zeros(B, S_cap, D, device=dev, dtype=torch.float32)
+        st.pooled = torch.zeros(B, S_cap, D, device=dev, dtype=self.dtype)
+        self._scan_buffers(st, S_cap)
+        st.z = torch.zeros(B, D, device=dev, dtype=self.dtype)
+        st.at_eos = torch.full((B,), -1, device=dev, dtype=torch.int32)
+        st.prev_emit.zero_()
+        st.emit_before = []
+        st.enc_rows = 0
+        st.avail_host, st.open_host = [0] * B, [1] * B
+        st.done = torch.zeros(B, device=dev, dtype=torch.int32)          # rows a driver has ended: they scan nothing and wait
+        st.left = torch.zeros(B, max(self.cfg.downsample - 1, 1), D, device=dev, dtype=self.dtype)     # rows of an incomplete window
+        st.left_host = [0] * B
+        st.g, st.g_fresh = None, False
+        st.n_wrote = 0                                                   # rows that wrote in the last step_online round (host)
+        st.scan_hi = torch.zeros(B, device=dev, dtype=torch.int32)       # positions below it hold the scan of the row's current g
+        st.n_prev.zero_()
+        st.n_prev_host = 0
+        self.sync_source(st)
+
+    def _scan_buffers(self, st: TransducerState, S: int):
+        B, dev = st.B, self.device
+        n_split = Ops.joiner_split(B, S, self.cfg.vocab, self.dtype)
+        st.blank_logit = torch.empty(B, S, device=dev, dtype=torch.float32)
+        st.best = torch.empty(B, S, n_split, device=dev, dtype=torch.float32)
+        st.best_idx = torch.empty(B, S, n_split, device=dev, dtype=torch.int32)
+
+    def sync_source(self, st: TransducerState):
+        """st.avail / st.open / st.src_len on the device from the host counts.  A row the driver has ended (st.done), and a closed
+        row without a single position, read as open with nothing available: they wait."""
+        i32 = dict(device=self.device, dtype=torch.int32)
+        st.avail, st.open = torch.tensor(st.avail_host, **i32), torch.tensor(st.open_host, **i32)
+        waits = (st.open != 0) | (st.avail == 0)
+        st.src_len = torch.where(st.done != 0, torch.full_like(st.avail, -1), torch.where(waits, -1 - st.avail, st.avail)).contiguous()
+
+    def _grow_source(self, st: TransducerState, S_need: int):
+        S_old = st.P.size(1)
+        if S_need <= S_old:
+            return
+        S_new = max(S_need, 2 * S_old)
+        for name in ("P", "pooled"):
+            old = getattr(st, name)
+            new = torch.zeros(old.size(0), S_new, old.size(2), device=old.device, dtype=old.dtype)
+            new[:, :S_old] = old
+            setattr(st, name, new)
+        self._scan_buffers(st, S_new)
+        st.scan_hi.zero_()                                   # the scan buffers' layout changed: every row scans from prev_emit again
+
+    def append_source(self, st: TransducerState, enc_rows: torch.Tensor, n_new, finish=False):
+        """More encoder states for an open source: enc_rows [B, n, D], of which the first n_new[b] are row b's (an int: every row's);
+        finish (one flag, or one per row): the source of the row ends here.  Only COMPLETE windows of k = cfg.downsample encoder
+        rows are pooled (simulst_transducer_pool) and projected into P; the < k rows behind them are carried to the next call.  On
+        finish the partial last window is flushed as the mean of its valid rows -- what AvgPool1dTBCPad gives a row that is not the
+        batch's longest -- and the row is closed: its last position is then forced as in the offline decode."""
+        cfg, ops, k = self.cfg, self.ops, self.cfg.downsample
+        B, n, D = enc_rows.shape
+        assert B == st.B
+        n_new = [int(n_new)] * B if isinstance(n_new, int) else [int(x) for x in (n_new.tolist() if torch.is_tensor(n_new) else n_new)]
+        fin = [bool(finish)] * B if isinstance(finish, (bool, int)) else [bool(x) for x in finish]
+        assert len(n_new) == B and len(fin) == B and all(0 <= x <= n for x in n_new)
+        for b in range(B):
+            if not st.open_host[b] and (n_new[b] > 0 or st.left_host[b] > 0):
+                raise ValueError(f"append_source: the source of row {b} is closed")
+        total = [st.left_host[b] + n_new[b] for b in range(B)]
+        lens = [t if fin[b] else t // k * k for b, t in enumerate(total)]               # the rows pooled now
+        wins = [(x + k - 1) // k for x in lens]
+        enc_rows = enc_rows.to(device=self.device, dtype=self.dtype)
+        uniform = len(set(st.left_host)) == 1 and len(set(n_new)) == 1 and len(set(st.avail_host)) == 1 and len(set(wins)) == 1
+        rows = (max(total) + k - 1) // k * k                                           # whole windows: the pool never clips one
+        if rows > 0:
+            X = torch.zeros(B, rows, D, device=self.device, dtype=self.dtype)
+            if uniform:
+                l0 = st.left_host[0]
+                X[:, :l0] = st.left[:, :l0]
+                X[:, l0:l0 + n_new[0]] = enc_rows[:, :n_new[0]]
+            else:
+                for b in range(B):
+                    l0 = st.left_host[b]
+                    X[b, :l0] = st.left[b, :l0]
+                    X[b, l0:l0 + n_new[b]] = enc_rows[b, :n_new[b]]
+            keep = [t - x for t, x in zip(total, lens)]                                # the rows behind the last complete window
+            if uniform and len(set(keep)) == 1:
+                st.left[:, :keep[0]] = X[:, lens[0]:total[0]]
+            else:
+                for b in range(B):
+                    st.left[b, :keep[b]] = X[b, lens[b]:total[b]]
+            st.left_host = keep
+        W = max(wins)
+        if W > 0:
+            self._grow_source(st, max(a + w for a, w in zip(st.avail_host, wins)))
+            Y, _ = ops.transducer_pool(X, torch.tensor(lens, device=self.device, dtype=torch.int32), T_max=W * k, k=k)       # [B, W, D]
+            Pn = ops.linear(Y.view(B * W, D), self.w.w_src, self.w.b_src, epilogue=EPI_BIAS_F32OUT).view(B, W, D)
+            if uniform:
+                a0 = st.avail_host[0]
+                st.pooled[:, a0:a0 + W] = Y
+                st.P[:, a0:a0 + W] = Pn
+            else:
+                for b in range(B):
+                    a0, w = st.avail_host[b], wins[b]
+                    st.pooled[b, a0:a0 + w] = Y[b, :w]
+                    st.P[b, a0:a0 + w] = Pn[b, :w]
+        for b in range(B):
+            st.avail_host[b] += wins[b]
+            if fin[b]:
+                st.open_host[b] = 0
+        st.enc_rows += max(n_new) if n_new else 0
+        self.sync_source(st)
+
+    def step_online(self, st: TransducerState, last_tokens: torch.Tensor, *, recompute_g: bool = False):
+        """One round over an open source: last_tokens [B] int64 -> (logits [B, V] fp32, wrote [B] bool).  A row writes if one of
+        its available positions emits (or its source is closed: the last position is forced); its logits row, st.prev_emit and
+        st.z are then those of ``step``, and the round is committed for it: st.n_prev[b] += 1.  A row that WAITS keeps prev_emit,
+        z and n_prev -- nothing is rolled back, the K/V row the round appended at n_prev[b] is overwritten by the next one -- and
+        its logits row is meaningless.  st.n_wrote is the number of rows that wrote, on the host (the round's one read-back).
+        The waiting rows keep their g: while NO row has written since g was computed (the round behind a new chunk, when every
+        live row waits), the next round skips the prediction network and scans only the positions that arrived since
+        (st.scan_hi).  The cache is per batch, not per row: once some row has written, the network and the scan run for every
+        row again, which gives a waiting row the bits it had.  recompute_g=True is the simpler form that does so every round
+        (tools/transducer_stream_bench.py times the two)."""
+        ops, V = self.ops, self.cfg.vocab
+        toks = last_tokens.to(device=self.device, dtype=torch.int64).contiguous()
+        if recompute_g or not st.g_fresh or st.g is None:
+            toks = torch.where(st.n_prev == 0, torch.full_like(toks, BLANK), toks)          # a row's first input is bos (:144)
+            feats = self.features(st, toks)
+            st.g = ops.linear(feats, self.w.w_tgt, None, epilogue=EPI_BIAS_F32OUT)
+            st.scan_hi.zero_()
+        lo = torch.maximum(st.prev_emit, st.scan_hi)
+        ops.joiner_scan(st.P, st.g, self.w.out_proj_fm, lo, st.src_len, st.blank_logit, st.best, st.best_idx, V=V, blank=BLANK)
+        st.scan_hi.copy_(torch.where(st.done != 0, st.scan_hi, st.avail))
+        ops.joiner_emit(st.P, st.g, st.blank_logit, st.best, st.best_idx, st.prev_emit, st.src_len, st.z, st.at_eos, V=V, blank=BLANK)
+        logits = ops.linear(st.z, self.w.out_proj, None, epilogue=EPI_BIAS_F32OUT)
+        ops.joiner_mask_blank(logits, st.at_eos, blank=BLANK)
+        wrote = st.at_eos >= 0
+        st.n_prev += wrote.to(torch.int32)
+        n_wrote, n_max = torch.stack([wrote.sum().to(torch.int32), st.n_prev.max()]).tolist()            # the round's one look at the device
+        st.n_wrote = int(n_wrote)
+        st.g_fresh = n_wrote == 0                  # g belongs to the rows' prefixes: it stays while none of them grows
+        st.n_prev_host = int(n_max)
+        if st.n_prev_host + 1 >= st.cap:
+            st.grow(2 * st.cap)
+        return logits, wrote
 
     # ------------------------------------------------------------------ beam search
     def beam_offline(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, max_len, *, beam: int, lenpen: float = 1.0, nbest: int = 1,
@@ -400,8 +561,9 @@ class TransducerDecoder:
 
 class TransducerModel(FairseqModelSurface):
     """models/transducer_model.py:271-300: S2TEmformerModel's encoder with the TransducerDecoder.  An offline model:
-    generate_offline (greedy, or beam search with beam / nbest / lenpen) and generate (beam search); no streaming agent exists
-    for it."""
+    generate_offline (greedy, or beam search with beam / nbest / lenpen) and generate (beam search).  The attention-policy
+    agents refuse it (model.refuse_offline_model); its own simultaneous agents are simulst_amd.transducer_agent.TransducerAgent
+    and BatchedTransducerStreamingAgent, which write what generate_offline writes."""
 
     def __init__(self, cfg: ModelConfig, weights: Dict[str, torch.Tensor], device="cuda", dtype=torch.float32,
                  ops: Optional[Ops] = None):
