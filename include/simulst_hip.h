@@ -54,7 +54,16 @@ enum {
   SIMULST_EPI_EMF_OUT = 4,     /* Emformer out_proj: rows < n_main of each utterance: C = . + b + R;
                                   summary rows: tanh(. + b) -> next layer's memory rows */
   SIMULST_EPI_BIAS_F32OUT = 5, /* C (always fp32) = A W^T + b   (logits, energies)  */
-  SIMULST_EPI_BIAS_RES_GELU = 6 /* C = gelu_erf(A W^T + b + R)   (CIF FakeCrossAttn, models/cif_transformer.py:357-362) */
+  SIMULST_EPI_BIAS_RES_GELU = 6, /* C = gelu_erf(A W^T + b + R)   (CIF FakeCrossAttn, models/cif_transformer.py:357-362) */
+  /* (7 is skipped: it is the value the plan tests record as refused with "unknown epilogue", and stays refused) */
+  SIMULST_EPI_ROW_PICK = 8     /* z = A W^T + b in fp32 is never written: C (int32, ONE element per row at the row's C address) = the
+                                  lowest column at which z is largest, aux (fp32 [M][2], logical row order) = (max z, logsumexp z).
+                                  The best path of a CTC head (criterion/joint_ctc_criterion.py:92-101) and its log-probabilities,
+                                  aux[r][0] - aux[r][1].  aux is required; a residual, a LayerNorm prologue, a_lead, c_head_dim and
+                                  c_tensor_heads are refused (E_ARG).  Any N >= 1, W row-major (or fragment-major in bf16 with
+                                  N % 16 == 0, K % 32 == 0, K <= 448).  bf16 with K % 32 == 0 and K <= 448 runs on the matrix
+                                  cores (csrc/gemm_pick.hip), other shapes on the VALU.  Fewer than 128 panels of 64 rows: the columns are
+                                  split over workgroups and the parts folded from the library's own scratch (no caller buffer). */
 };
 
 /* monotonic attention flavours (modules/__init__.py:11-16 registry names minus the

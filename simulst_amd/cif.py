@@ -14,6 +14,7 @@ import torch
 from . import _lib
 from .agent import READ_ACTION, WRITE_ACTION, FrameSource, States
 from .config import ModelConfig
+from .ctc import CTCTranscriber
 from .decoder import DecoderWeights
 from .encoder import S2TEmformerEncoder
 from .ops import Ops, EPI_BIAS, EPI_BIAS_F32OUT, EPI_BIAS_GELU, EPI_BIAS_RES
@@ -395,7 +396,7 @@ class CIFDecoder:
 
 
 @register_model("cif_transformer")
-class CIFTransformerModel(FairseqModelSurface):
+class CIFTransformerModel(FairseqModelSurface, CTCTranscriber):
     def __init__(self, cfg: ModelConfig, weights, device="cuda", dtype=torch.float32, ops=None):
         self.cfg = cfg
         self._deferred = None

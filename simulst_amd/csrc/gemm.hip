@@ -437,6 +437,14 @@ extern "C" int simulst_linear(simulst_handle* h, const simulst_linear_desc* d, c
     SL_REQUIRE(h, d->n_main >= 0 && d->n_main <= d->rows_per_batch && d->aux_rows >= 0, SIMULST_E_SHAPE,
                "simulst_linear: EMF_OUT row split");
   }
+  if (d->epilogue == SIMULST_EPI_ROW_PICK) {
+    // C holds one int32 per row and aux an fp32 pair: nothing of the other epilogues' row-shaped operands applies
+    SL_REQUIRE(h, R == nullptr, SIMULST_E_ARG, "simulst_linear: row pick takes no residual");
+    SL_REQUIRE(h, !d->ln_gamma && !d->ln_beta, SIMULST_E_ARG, "simulst_linear: row pick takes no LayerNorm prologue");
+    SL_REQUIRE(h, d->c_head_dim == 0 && d->c_tensor_heads == 0, SIMULST_E_ARG, "simulst_linear: row pick writes one element per row (no head-major output)");
+    SL_REQUIRE(h, d->a_lead == 0, SIMULST_E_ARG, "simulst_linear: row pick takes no a_lead");
+    SL_CHECK_NULL(h, aux);
+  }
   if (d->M_batches == 0) return SIMULST_OK;
   long M = (long)d->M_batches * d->rows_per_batch;
   SL_REQUIRE(h, M < (1L << 31), SIMULST_E_SHAPE, "simulst_linear: too many rows");
@@ -469,6 +477,7 @@ extern "C" int simulst_linear(simulst_handle* h, const simulst_linear_desc* d, c
     case SL_LIN_WAVE_TILE: return sl_launch_wave_tile(h, pl, o, p);
     case SL_LIN_SKINNY: return sl_launch_skinny(h, pl, o, p);
     case SL_LIN_TILE256: return sl_launch_tile256(h, pl, o, p);
+    case SL_LIN_ROW_PICK: return sl_launch_row_pick(h, pl, o, p);
     default: break;                                                  // SL_LIN_TILE128, SL_LIN_TILE64
   }
   KTimer t(h, pl.timer);

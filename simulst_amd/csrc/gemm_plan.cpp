@@ -189,10 +189,35 @@ static bool tile256_ok(const simulst_handle* h, int dtype, int epi, const LinArg
          p.a_bs >= 0 && p.a_rs >= 0;
 }
 
+// ---- row pick -----------------------------------------------------------------------------------------------------------------------
+// bf16 with whole 32-element k-steps and a panel that fits the default dynamic-LDS limit (K <= 448) runs on the matrix cores,
+// everything else on the VALU.  One workgroup per row panel over the whole width where the panels fill the chip; fewer than 128 panels
+// (a stream's chunk, a lockstep round: under 8192 rows) split the column tiles over blockIdx.y, at least 8 tiles a part (one pair per
+// wave), towards one workgroup per compute unit -- the parts fold through the library's scratch in a second launch.
+static sl_linear_plan plan_row_pick(sl_linear_plan pl, const LinArgs& p) {
+  const long panel = (long)PICK_M * (p.K + 8) * 2;
+  pl.family = SL_LIN_ROW_PICK;
+  pl.timer = SIMULST_K_LINEAR;
+  pl.pick_mfma = pl.dtype == SIMULST_BF16 && p.K % 32 == 0 && panel <= PICK_LDS_MAX;
+  if (p.w_packed && !(pl.pick_mfma && p.N % 16 == 0))
+    return refused(pl, SIMULST_E_SHAPE, "simulst_linear: row pick takes fragment-major weights in bf16 with N % 16 == 0, K % 32 == 0, K <= 448");
+  pl.grid[0] = cdiv(p.M, pl.pick_mfma ? PICK_M : PICK_VM);
+  pl.lds = pl.pick_mfma ? (unsigned)panel : 0;
+  pl.splits = 1;
+  if (pl.pick_mfma && pl.grid[0] < 128) {
+    const unsigned by_width = cdiv(cdiv(p.N, 16), 8), by_chip = cdiv(256, pl.grid[0]);
+    pl.splits = (int)(by_width < by_chip ? by_width : by_chip);
+    if (pl.splits < 1) pl.splits = 1;
+  }
+  pl.grid[1] = pl.splits;
+  return pl;
+}
+
 sl_linear_plan sl_plan_linear(const simulst_handle* h, int dtype, int epi, const LinArgs& p, const sl_linear_ops& o) {
   sl_linear_plan pl = {};
   pl.dtype = dtype; pl.epi = epi; pl.ln = p.ln_g != nullptr;
   pl.grid[0] = pl.grid[1] = pl.grid[2] = 1;
+  if (epi == SIMULST_EPI_ROW_PICK) return plan_row_pick(pl, p);
   const int G = dtype == SIMULST_F32 ? 4 : 8;
   const bool skinny_ok = p.M <= (p.w_packed ? SKINNY_MAX_ROWS_PACKED : SKINNY_MAX_ROWS) && p.a_lead == 0 && p.a_rs >= p.K &&
                          epi != SIMULST_EPI_GLU && epi != SIMULST_EPI_EMF_OUT;

@@ -19,6 +19,9 @@ constexpr unsigned T256_RING_LDS = 2 * R_STAGE > TB * (TB / 2 + 8) * 2 ? 2 * R_S
 constexpr int TILE_MIN_ROWS = 256;
 // decode-step shapes: up to 2048 rows, up to 8192 when the caller packed the weights for them (co-scheduled batches)
 constexpr int SKINNY_MAX_ROWS = 2048, SKINNY_MAX_ROWS_PACKED = 8192;
+// row pick (gemm_pick.hip): rows of a workgroup's LDS panel on the matrix cores, the panel's byte limit (with the kernel's 3 KB of
+// static LDS inside the default 64 KB: no raise), rows per workgroup of the VALU form
+constexpr int PICK_M = 64, PICK_LDS_MAX = 60 * 1024, PICK_VM = 4;
 
 enum sl_linear_family {
   SL_LIN_REFUSED = 0,
@@ -32,6 +35,7 @@ enum sl_linear_family {
   SL_LIN_TILE256,        // 256 x 256 GLU tiles, register-staged or on the LDS-DMA ring (gemm_tile256.hip)
   SL_LIN_TILE128,        // 128 x 128 tiles (gemm.hip)
   SL_LIN_TILE64,         // 64 x 64 tiles (gemm.hip)
+  SL_LIN_ROW_PICK,       // SIMULST_EPI_ROW_PICK: per-row (argmax, max, logsumexp), logits never written (gemm_pick.hip)
 };
 
 struct sl_linear_plan {
@@ -43,12 +47,14 @@ struct sl_linear_plan {
   unsigned grid[3];
   unsigned lds;          // dynamic LDS bytes
   bool ln;               // LayerNorm prologue form
-  int MTs, NTs, splits, kps;      // SKINNY: 16-row / 16-column tiles per workgroup, split-K ranges and the k of one
+  int MTs, NTs, splits, kps;      // SKINNY: 16-row / 16-column tiles per workgroup, split-K ranges and the k of one; ROW_PICK: splits =
+                                  //   column parts (grid[1]), folded by a second launch when > 1
   bool tall;             // MID: 128-row tiles
   int tiles_n;           // WAVE_TILE: 16-column tiles of a row
   int spb;               // PANEL, PANEL_SPLIT: column steps (of PB_N) per workgroup
   int pairs, n_slices;   // WSTAT: column-tile pairs of a slice, slices of the width
   bool ring;             // TILE256: LDS-DMA ring (option value 2) instead of the register stage (1)
+  bool pick_mfma;        // ROW_PICK: matrix-core form (bf16, K % 32 == 0, the row panel within PICK_LDS_MAX) instead of the VALU one
 };
 
 // the operands of a call, as simulst_linear got them
@@ -83,6 +89,7 @@ int sl_launch_panel_wide(simulst_handle* h, const sl_linear_plan& pl, const sl_l
 int sl_launch_panel_split(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p);   //   PANEL_SPLIT
 int sl_launch_wstat(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p);         // gemm_wstat.hip
 int sl_launch_tile256(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p);       // gemm_tile256.hip
+int sl_launch_row_pick(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p);      // gemm_pick.hip
 
 // The <TA, TC, EPI> of a decode-step epilogue: f(TA(), TC(), std::integral_constant<int, EPI>()).  The plan refuses every other
 // epilogue before a launcher is reached.

@@ -311,27 +311,7 @@ template <typename T> struct LatCfg;
 template <> struct LatCfg<bf16> { static constexpr int R = 8, THREADS = 512; };
 template <> struct LatCfg<float> { static constexpr int R = 4, THREADS = 256; };
 
-constexpr float LAT_NEG = -1e30f;         // "no column yet": finite, so that max - max never makes a NaN
-
-template <typename T> __device__ __forceinline__ f32x4 lat_mma(const uint4& a, const uint4& w, f32x4 acc) {
-  if constexpr (std::is_same<T, float>::value) {
-    const float* af = reinterpret_cast<const float*>(&a);
-    const float* wf = reinterpret_cast<const float*>(&w);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[e], wf[e], acc, 0, 0, 0);
-    return acc;
-  } else {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(&a), *reinterpret_cast<const bf16x8_t*>(&w),
-                                                   acc, 0, 0, 0);
-  }
-}
-
-// (m, s) <- (m, s) joined with (om, os): s counts exp(x - m)
-__device__ __forceinline__ void lse_join(float& m, float& s, float om, float os) {
-  const float mx = fmaxf(m, om);
-  s = s * __expf(m - mx) + os * __expf(om - mx);
-  m = mx;
-}
+// (lat_mma, lse_join and LAT_NEG live in gemv_mfma.h: the row-pick epilogue of simulst_linear shares them)
 
 // grid (ceil(B * S * u_tiles / R), n_split).  part[cell][p] = (max, sum, blank logit, label logit) of vocabulary part p.
 template <typename T>

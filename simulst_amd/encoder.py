@@ -342,6 +342,15 @@ class S2TEmformerEncoder:
             res["ctc_logits"] = [ops.linear(out.reshape(B * Te, D), self.w.ctc).view(B, Te, -1)]
         return res
 
+    def ctc_greedy(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, *, blank: int = 0):
+        """Best path of the CTC head over encoder rows (forward()'s "encoder_out_btd" view is read where it lies, "encoder_lengths"):
+        {"path", "lprob", "tokens", "n", "frames", "score"} as ctc.ctc_greedy describes them.  The head's logits are not written: the
+        pick and its log-probability come out of the projection's own launch (Ops.linear_pick).  ValueError without a head."""
+        if self.w.ctc is None:
+            raise ValueError("ctc_greedy: this model has no CTC head (ModelConfig.ctc_layer is off / no encoder.ctc_layer.weight)")
+        from .ctc import ctc_greedy
+        return ctc_greedy(self.ops, self.w.ctc, enc_btd, enc_len, blank=blank, pad=self.cfg.padding_idx)
+
 
     # ================================================================== streaming (Emformer.infer)
     def new_stream_state(self, B: int):

@@ -6,6 +6,7 @@ from typing import Dict, Optional
 import torch
 
 from .config import ModelConfig
+from .ctc import CTCTranscriber
 from .decoder import MMADecoder
 from .encoder import S2TEmformerEncoder
 from .ops import Ops
@@ -110,7 +111,7 @@ class FairseqModelSurface:
         return min(int(max_len_a * T + max_len_b), self.cfg.max_target_positions - 1)
 
 
-class SimulSTModel(FairseqModelSurface):
+class SimulSTModel(FairseqModelSurface, CTCTranscriber):
     """encoder/decoder holder with the attributes the agents use (agents/default_agent.py:157-175,
     394-406,418-420): .encoder, .decoder, get_normalized_probs, max_decoder_positions."""
 

@@ -82,6 +82,49 @@ class Ops:
                                c_bs=0, c_rs=N, epilogue=epilogue, R=residual, r_bs=0, r_rs=N, ln=ln,
                                w_fragment_major=w_fragment_major)
 
+    def linear_pick(self, x, W, bias=None, *, rows_per_batch=None, out=None, w_fragment_major=False):
+        """Best column of every row of z = x @ W[N, K]^T + bias without the logits (simulst_linear, SIMULST_EPI_ROW_PICK):
+        -> (pick int32, zmax fp32, lse fp32), each shaped like x without its last dimension; pick is the lowest column at which z is
+        largest (torch.argmax's rule), zmax - lse its log-probability.
+
+        x: [rows, K] (rows K-contiguous, any row stride) or a [B, T, K] view with a batch stride -- the encoder's output rows are read
+        where they lie.  rows_per_batch (2-D x only, default all rows): the rows form rows / rows_per_batch batches, which is how `out`
+        is addressed.  out: an int32 tensor (or view) [batches, rows_per_batch] to take the pick, any strides.  Runs on the handle's
+        stream like every op here; CPU tensors raise."""
+        _chk_contig(W)
+        _p(x), _p(W)                                           # (CPU tensors raise here, whatever the row count)
+        if x.dim() == 3:
+            if rows_per_batch is not None and rows_per_batch != x.shape[1]:
+                raise ValueError("linear_pick: rows_per_batch belongs to 2-D x")
+            Bb, rpb, K = x.shape
+            a_bs, a_rs = x.stride(0), x.stride(1)
+        elif x.dim() == 2:
+            rows, K = x.shape
+            rpb = max(rows, 1) if rows_per_batch is None else int(rows_per_batch)
+            if rpb <= 0 or rows % rpb:
+                raise ValueError("linear_pick: rows_per_batch must divide the rows")
+            Bb, a_rs = rows // rpb, x.stride(0)
+            a_bs = rpb * a_rs
+        else:
+            raise ValueError("linear_pick: x is [rows, K] or [B, T, K]")
+        if x.stride(-1) != 1 and x.numel():
+            raise ValueError("linear_pick: the rows of x must be contiguous")
+        N = W.shape[0]
+        if W.shape[1] != K or W.dtype != x.dtype:
+            raise ValueError("linear_pick: W is [N, K] in x's dtype")
+        if out is None:
+            out = torch.empty(Bb, rpb, device=x.device, dtype=torch.int32)
+        elif out.dtype != torch.int32 or tuple(out.shape) != (Bb, rpb):
+            raise ValueError("linear_pick: out is an int32 [batches, rows_per_batch] tensor")
+        aux = torch.empty(Bb * rpb, 2, device=x.device, dtype=torch.float32)
+        if Bb * rpb:                                           # (no rows: nothing to launch, and nothing to point at)
+            self.linear_raw(x, W, bias, out, M_batches=Bb, rows_per_batch=rpb, N=N, K=K, a_bs=a_bs, a_rs=a_rs, c_bs=out.stride(0),
+                            c_rs=out.stride(1), epilogue=_lib.EPI_ROW_PICK, aux=aux, w_fragment_major=w_fragment_major)
+        zmax, lse = aux[:, 0].view(Bb, rpb), aux[:, 1].view(Bb, rpb)
+        if x.dim() == 2 and rows_per_batch is None:
+            return (out[0], zmax[0], lse[0]) if Bb else (out.reshape(0), zmax.reshape(0), lse.reshape(0))
+        return out, zmax, lse
+
     def causal_conv1d_glu(self, x, Wp, bp, *, ksize, stride, scale=1.0, out=None):
         """Strided causal Conv1d + GLU over channel-last frames.
         x [B, T_in, C_in] whose first (ksize-1) frames are LEFT CONTEXT (zeros at utterance start,
