@@ -5,33 +5,18 @@ Same method names and control flow as the reference agent -- ``initialize_states
 going to the HIP encoder/decoder.  SimulEval (the process that drives the agent through
 READ/WRITE actions) is third-party and absent from the images; ``FrameSource`` + ``run_utterance``
 below stand in for its client/server loop at fbank-frame granularity (DESIGN.md "Synthetic
-harness"): a READ releases the next ``expected_frames`` frames (fewer at the end, raising
-``finish_read`` with the last ones) and every committed token is stamped with the source
-milliseconds released so far.
+harness"; the chunk protocol itself is stream_source.py): a READ releases the next ``expected_frames``
+frames (fewer at the end, raising ``finish_read`` with the last ones) and every committed token is
+stamped with the source milliseconds released so far.
 """
 from typing import List, Optional
 
 import torch
 
+from .stream_source import SHIFT_SIZE, WINDOW_SIZE, FrameSource, chunk_positions  # noqa: F401  (re-exported: harness, tools, tests)
+from .stream_source import ChunkedAgent, LockstepLog, encoder_chunks, offline_states, run_rounds
+
 READ_ACTION, WRITE_ACTION = 0, 1
-SHIFT_SIZE, WINDOW_SIZE = 10, 25
-
-
-class FrameSource:
-    def __init__(self, fbank: torch.Tensor):
-        self.fbank = fbank
-        self.pos = 0
-        self.finished = fbank.size(0) == 0
-
-    def read(self, n: int):
-        self.pos = min(self.pos + n, self.fbank.size(0))
-        self.finished = self.pos >= self.fbank.size(0)
-
-    def elapsed_ms(self):
-        return 0 if self.pos == 0 else self.pos * SHIFT_SIZE + (WINDOW_SIZE - SHIFT_SIZE)
-
-    def total_ms(self):
-        return self.fbank.size(0) * SHIFT_SIZE + (WINDOW_SIZE - SHIFT_SIZE)
 
 
 class States:
@@ -48,19 +33,16 @@ class States:
         return self.source.finished
 
 
-class FairseqSimulSTAgent:
+class FairseqSimulSTAgent(ChunkedAgent):
     def __init__(self, model, max_len_a: float = 1, max_len_b: int = 0, force_finish: bool = False):
         from .model import refuse_offline_model
         refuse_offline_model(model, type(self).__name__)
         self.model = model
-        enc = model.encoder
         # agents/default_agent.py:157-175
         self.pre_decision_ratio = model.decoder.pre_decision_ratio
-        self.stride_ms = enc.conv_layer_stride() * SHIFT_SIZE
-        self.right_context, self.segment_length = enc.right_context, enc.segment_length
+        self._init_chunks(model)
         self.max_len = lambda x: min(max_len_a * x + max_len_b, model.max_decoder_positions())
         self.force_finish = force_finish
-        self.eos = model.cfg.eos
 
     def initialize_states(self, states: States):
         states.enc_incremental_states = {}
@@ -72,9 +54,8 @@ class FairseqSimulSTAgent:
         update_len = src.pos - states.last_update_source_len
         if update_len == 0 and states.finish_read():
             return
-        finish = (update_len < self.expected_frames) or states.finish_read()
         frames = src.fbank[:src.pos].unsqueeze(0)
-        out = self.model.encoder.infer(frames, torch.tensor([src.pos]), states.enc_incremental_states, finish=finish)
+        out = self.model.encoder.infer(frames, torch.tensor([src.pos]), states.enc_incremental_states, finish=src.finish)
         new = out["encoder_out_btd"]
         dec = self.model.decoder
         if "dec" not in states.dec_incremental_states:
@@ -93,7 +74,7 @@ class FairseqSimulSTAgent:
     # ---- agents/default_agent.py:364-413
     def policy(self, states: States):
         if not getattr(states, "has_encoder_states", False):
-            self.expected_frames = (self.segment_length + self.right_context) * self.stride_ms // SHIFT_SIZE
+            self.expected_frames = self.first_frames
             if states.finish_read():
                 self.update_states_read(states)
             return READ_ACTION
@@ -104,7 +85,7 @@ class FairseqSimulSTAgent:
                                                  stop_on_read=True)
         states.decoder_out = logits
         if action == 0:
-            self.expected_frames = self.segment_length * self.stride_ms // SHIFT_SIZE
+            self.expected_frames = self.next_frames
             return READ_ACTION
         return WRITE_ACTION
 
@@ -136,7 +117,7 @@ class FairseqSimulSTAgent:
                         actions.pop()
                         break
                     raise RuntimeError("READ after source finished")
-                src.read(self.expected_frames)
+                src.take(self.expected_frames)
                 self.update_states_read(states)
                 continue
             actions.append("W")
@@ -152,17 +133,6 @@ class FairseqSimulSTAgent:
         st = states.dec_incremental_states.get("dec")
         return {"tokens": list(states.target), "delays_ms": delays, "actions": "".join(actions),
                 "AL": average_lagging(delays, src.total_ms()), "n_enc": st.enc_rows if st is not None else 0}
-
-
-def chunk_positions(T: int, segment_length: int, right_context: int, stride_ms: int):
-    """Source frames offered after each READ (agents/default_agent.py:367,407: first segment + right context, then segments)."""
-    pos, out = 0, []
-    expected = (segment_length + right_context) * stride_ms // SHIFT_SIZE
-    while pos < T:
-        pos = min(pos + expected, T)
-        out.append(pos)
-        expected = segment_length * stride_ms // SHIFT_SIZE
-    return out
 
 
 def self_paced_records(hyp, delays, tok_chunk, n_prev, chunk_idx, cap, total_ms, extra_key, extra_of):
@@ -226,9 +196,6 @@ class BatchedStreamingAgent(FairseqSimulSTAgent):
             raise ValueError("the lockstep form streams through encoder.infer; encoder='offline' needs self_paced=True")
         return self._run_batch_lockstep(fbank)
 
-    def _chunk_positions(self, T: int):
-        return chunk_positions(T, self.segment_length, self.right_context, self.stride_ms)
-
     def _run_batch_self_paced(self, fbank: torch.Tensor, encoder: str = "chunked", lengths=None):
         from . import _lib
         model, dec, enc = self.model, self.model.decoder, self.model.encoder
@@ -245,44 +212,27 @@ class BatchedStreamingAgent(FairseqSimulSTAgent):
         # ---- every row's schedule: frames offered after each READ, encoder rows released, source time, length cap
         #      (integer arithmetic per distinct length, cached on the agent; the [B, n_chunks] tables assembled with numpy)
         import numpy as np
-        cache = self.__dict__.setdefault("_schedule_cache", {})
-        per_T = {}
-        for t in set(Ls):
-            if t not in cache:
-                positions = self._chunk_positions(t)
-                cache[t] = (positions, enc.stream_row_schedule(positions),
-                            [p * SHIFT_SIZE + (WINDOW_SIZE - SHIFT_SIZE) for p in positions], [int(self.max_len(p)) for p in positions])
-            per_T[t] = cache[t]
-        n_chunks = max(len(v[0]) for v in per_T.values())
+        per_T = {t: self._schedule(t) for t in set(Ls)}
+        n_chunks = max(len(s.positions) for s in per_T.values())
         uniq, inv = np.unique(np.asarray(Ls), return_inverse=True)
         tab = np.zeros((3, len(uniq), n_chunks), dtype=np.int32)
         for u, t in enumerate(uniq.tolist()):
-            for k in (1, 2, 3):
-                v = per_T[t][k]
-                tab[k - 1, u, :len(v)] = v
-                tab[k - 1, u, len(v):] = v[-1]
+            for k, v in enumerate((per_T[t].rows, per_T[t].ms, per_T[t].max_len)):
+                tab[k, u, :len(v)] = v
+                tab[k, u, len(v):] = v[-1]
         i32 = dict(device=dev, dtype=torch.int32)
         sched = torch.from_numpy(np.ascontiguousarray(tab[:, inv])).to(dev)                       # [3][B][n_chunks]
-        row_chunks = torch.from_numpy(np.array([len(per_T[t][0]) for t in uniq.tolist()], dtype=np.int32)[inv]).to(dev)
-        rows_total = [per_T[t][1][-1] for t in Ls]
+        row_chunks = torch.from_numpy(np.array([len(per_T[t].positions) for t in uniq.tolist()], dtype=np.int32)[inv]).to(dev)
+        rows_total = [per_T[t].rows[-1] for t in Ls]
         cap = int(self.max_len(max(Ls))) + 4
         st = dec.new_state(B, cap=cap, S_cap=max(max(rows_total), 1))
         st.lockstep = False
         if encoder == "offline":
-            e = enc.forward(fbank, torch.tensor(Ls, device=dev))
-            out = e["encoder_out_btd"]
-            if e["encoder_lengths"].tolist() != rows_total:
-                raise RuntimeError("offline encoder lengths differ from the rows the streaming schedule releases")
-            dec.append_encoder_out(st, out, e["encoder_lengths"])
+            dec.append_encoder_out(st, *offline_states(enc, fbank, Ls, [per_T[t] for t in Ls]))
         else:
             # every chunk through the streaming encoder (the launches of the microphone form, minus its host round trips)
-            enc_state, positions, rows = {}, per_T[T][0], []
-            for i, pos in enumerate(positions):
-                new = enc.infer(fbank[:, :pos], torch.full((B,), pos), enc_state, finish=i == len(positions) - 1)["encoder_out_btd"]
+            for _, _, _, new in encoder_chunks(enc, fbank, per_T[T]):
                 dec.append_encoder_out(st, new, torch.full((B,), st.enc_rows + new.size(1)))
-                rows.append(st.enc_rows)
-            if rows != list(per_T[T][1]):
-                raise RuntimeError(f"streaming encoder released {rows}, stream_row_schedule predicted {per_T[T][1]}")
         # wait-k: READ is a closed form of position and source length (position u needs u + k pooled keys), so every row starts at
         # the first chunk that allows position 0 and the commit kernel keeps taking chunks the same way (simulst_stream_ctl.ff_waitk)
         ff_k = cfg.waitk_lagging if cfg.attn_type == "waitk" else 0
@@ -294,7 +244,7 @@ class BatchedStreamingAgent(FairseqSimulSTAgent):
             return min(-(-n // ratio_abs), max(n // ratio_abs, 1))
         c0_of = {}
         for t in uniq.tolist():
-            rows_t, c = per_T[t][1], 0
+            rows_t, c = per_T[t].rows, 0
             while ff_k > 0 and c + 1 < len(rows_t) and ff_k - 1 >= pooled_count(rows_t[c]):
                 c += 1
             c0_of[t] = c
@@ -313,34 +263,26 @@ class BatchedStreamingAgent(FairseqSimulSTAgent):
                              chunk_idx.data_ptr(), st.enc_len.data_ptr(), tok_chunk.data_ptr(), row_chunks.data_ptr(),
                              ff_k, dec.ratio_arg if ff_k else 0)
         # ---- one device loop; a row needs at most (tokens it may hold + 1) + (its chunks - 1) rounds
-        bound = max(per_T[t][3][-1] + 1 + len(per_T[t][0]) for t in set(Ls))
+        bound = max(s.max_len[-1] + 1 + len(s.positions) for s in per_T.values())
         # no row can finish its cap in fewer rounds than it may hold tokens: that many rounds go out before the first look at the
         # masks (wait-k rows, whose READs cost no round, are then done unless they met EOS earlier -- which the look finds), short
         # calls after it
-        first = max(per_T[t][3][-1] + 1 for t in set(Ls))
-        n_run = 0
-        while True:                                        # rows that meet EOS early end the loop before the bound
-            n = max(1, min(64, first - n_run) if n_run < first else min(8, bound - n_run))
-            dec.stream_steps(st, tokens, ctl, n)
-            n_run += n
-            if not bool(active.any().item()):
-                break
-            if n_run >= bound:
-                raise RuntimeError("self-paced rows still active after cap + n_chunks rounds")
-        return self_paced_records(hyp, delays, tok_chunk, st.n_prev, chunk_idx, cap,
-                                  [t * SHIFT_SIZE + (WINDOW_SIZE - SHIFT_SIZE) for t in Ls], "n_enc",
-                                  lambda b, c: per_T[Ls[b]][1][c])
+        first = max(s.max_len[-1] + 1 for s in per_T.values())
+        run_rounds(lambda n: dec.stream_steps(st, tokens, ctl, n), lambda: not bool(active.any().item()), first, bound,
+                   "self-paced rows still active after cap + n_chunks rounds")   # rows that meet EOS early end it before the bound
+        return self_paced_records(hyp, delays, tok_chunk, st.n_prev, chunk_idx, cap, [per_T[t].total_ms for t in Ls], "n_enc",
+                                  lambda b, c: per_T[Ls[b]].rows[c])
 
     def _run_batch_lockstep(self, fbank: torch.Tensor):
         from . import _lib
-        from .latency import average_lagging
         model, dec, enc = self.model, self.model.decoder, self.model.encoder
         cfg, dev = model.cfg, model.device
         B, T = fbank.size(0), fbank.size(1)
         fbank = fbank.to(dev)
         cap = int(self.max_len(T)) + 4
+        sched = self._schedule(T)
         # exactly the rows the schedule releases: up to 256 keys the policy / cross-attention kernel keeps its single-latency form
-        s_cap = max(enc.stream_row_schedule(self._chunk_positions(T))[-1], 1)
+        s_cap = max(sched.rows[-1], 1)
         st = dec.new_state(B, cap=cap, S_cap=s_cap)
         st.lockstep = False
         u8 = dict(device=dev, dtype=torch.uint8)
@@ -354,52 +296,28 @@ class BatchedStreamingAgent(FairseqSimulSTAgent):
         if n_slots and n_slots <= 128:
             raise ValueError("compact_rows: more than 128 slots per round (or 0: off)")
         row_map = torch.empty(n_slots, device=dev, dtype=torch.int32) if n_slots else None
-        enc_state = {}
-        src = FrameSource(fbank[0])
-        actions = [[] for _ in range(B)]
-        n_written = [0] * B
-        last_update = 0
-        expected = (self.segment_length + self.right_context) * self.stride_ms // SHIFT_SIZE
-        alive = list(range(B))
-        while alive:
+        chunks, log = encoder_chunks(enc, fbank, sched), LockstepLog(B)
+        while log.alive:
             # ---- READ phase: every unfinished stream takes the next chunk (agents/default_agent.py:303-342)
-            for b in alive:
-                actions[b].append("R")
-            if src.finished:
+            log.read()
+            chunk = next(chunks, None)
+            if chunk is None:
                 raise RuntimeError("READ after source finished")
-            src.read(expected)
-            update_len = src.pos - last_update
-            finish = update_len < expected or src.finished
-            out = enc.infer(fbank[:, :src.pos], torch.full((B,), src.pos), enc_state, finish=finish)
-            new = out["encoder_out_btd"]
+            c, _, finish, new = chunk
             dec.append_encoder_out(st, new, torch.full((B,), st.enc_rows + new.size(1)))
-            last_update = src.pos
-            expected = self.segment_length * self.stride_ms // SHIFT_SIZE
             # ---- WRITE phase: masked decoder steps until every row waits for source or is finished
-            online.fill_(0 if src.finished else 1)
+            online.fill_(0 if finish else 1)
             active.copy_(1 - done)
             ctl = _lib.StreamCtl(active.data_ptr(), read_flag.data_ptr(), online.data_ptr(), done.data_ptr(),
-                                 delays.data_ptr(), hyp.data_ptr(), cap, src.elapsed_ms(),
-                                 int(self.max_len(src.pos)), 0, None, None, None, None, None, None, None, 0, 0,
+                                 delays.data_ptr(), hyp.data_ptr(), cap, sched.ms[c],
+                                 sched.max_len[c], 0, None, None, None, None, None, None, None, 0, 0,
                                  row_map=row_map.data_ptr() if row_map is not None else None, compact_rows=n_slots)
             while True:
                 dec.stream_steps(st, tokens, ctl, self.steps_per_call)
                 if not bool(active.any().item()):
                     break
-            n_prev = st.n_prev.tolist()
-            done_h = done.tolist()
-            for b in alive:
-                actions[b].extend("W" * (n_prev[b] - n_written[b]))
-                n_written[b] = n_prev[b]
-            alive = [b for b in alive if not done_h[b]]
-        hyp_h, delays_h = hyp.tolist(), delays.tolist()
-        recs = []
-        for b in range(B):
-            n = n_written[b]
-            d = [int(x) for x in delays_h[b][:n]]
-            recs.append({"tokens": hyp_h[b][:n], "delays_ms": d, "actions": "".join(actions[b]),
-                         "AL": average_lagging(d, src.total_ms()), "n_enc": st.enc_rows})
-        return recs
+            log.wrote(st.n_prev.tolist(), done.tolist())
+        return log.records(hyp, delays, sched.total_ms, "n_enc", lambda b: st.enc_rows)
 
 
 class ConcurrentStreamingEval:

@@ -12,7 +12,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
-from .agent import READ_ACTION, WRITE_ACTION, FrameSource, States
+from .agent import READ_ACTION, WRITE_ACTION, States, self_paced_records
 from .config import ModelConfig
 from .ctc import CTCTranscriber
 from .decoder import DecoderWeights
@@ -20,6 +20,7 @@ from .encoder import S2TEmformerEncoder
 from .ops import Ops, EPI_BIAS, EPI_BIAS_F32OUT, EPI_BIAS_GELU, EPI_BIAS_RES
 from .model import FairseqModelSurface
 from .registry import register_model, register_model_architecture
+from .stream_source import ChunkedAgent, FrameSource, LockstepLog, encoder_chunks, run_rounds
 
 
 class CIFLayer:
@@ -423,28 +424,24 @@ class CIFTransformerModel(FairseqModelSurface, CTCTranscriber):
                                   "generate_offline decodes it greedily")
 
 
-class CIFAgent:
+class CIFAgent(ChunkedAgent):
     """agents/cif_agent.py: READ while cif_lengths <= len(hyp) and the source has not ended (:385-389),
     otherwise one decoder step and WRITE; cif_out / cif_lengths accumulate across READs (:327-343)."""
 
     def __init__(self, model: CIFTransformerModel, max_len_a: int = 1, max_len_b: int = 0,
                  overshoot_weight: float = 1.0):
         self.model = model
-        enc = model.encoder
-        self.stride_ms = enc.conv_layer_stride() * 10
-        self.right_context, self.segment_length = enc.right_context, enc.segment_length
+        self._init_chunks(model)
         self.max_len = lambda x: max_len_a * x + max_len_b
         self.overshoot_weight = overshoot_weight
-        self.eos = model.cfg.eos
 
     def update_model_encoder(self, states: States):
         src = states.source
         update_len = src.pos - states.last_update_source_len
         if update_len == 0 and states.finish_read():
             return
-        finish = (update_len < self.expected_frames) or states.finish_read()
         out = self.model.encoder.infer(src.fbank[:src.pos].unsqueeze(0), torch.tensor([src.pos]),
-                                       states.enc_incremental_states, finish=finish)
+                                       states.enc_incremental_states, finish=src.finish)
         if getattr(states, "cif_out", None) is None:
             states.cif_out, states.cif_len = out["cif_out_btd"], int(out["cif_lengths"][0])
         else:
@@ -461,21 +458,19 @@ class CIFAgent:
         dec = self.model.decoder
         dst = dec.new_state(1, cap=int(self.max_len(fbank.size(0))) + 4)
         actions, delays = [], []
-        first = (self.segment_length + self.right_context) * self.stride_ms // 10
-        nxt = self.segment_length * self.stride_ms // 10
         while True:
             if states.cif_out is None:
-                self.expected_frames = first
+                self.expected_frames = self.first_frames
                 read = True
             else:
                 read = states.cif_len <= len(states.target) and not states.finish_read()
                 if read:
-                    self.expected_frames = nxt
+                    self.expected_frames = self.next_frames
             if read:
                 actions.append("R")
                 if src.finished:
                     raise RuntimeError("READ after source finished")
-                src.read(self.expected_frames)
+                src.take(self.expected_frames)
                 self.update_model_encoder(states)
                 continue
             actions.append("W")
@@ -526,42 +521,20 @@ class BatchedCIFStreamingAgent(CIFAgent):
         B, T = fbank.size(0), fbank.size(1)
         fbank = fbank.to(dev)
         cap = int(self.max_len(T)) + 4
-        first = (self.segment_length + self.right_context) * self.stride_ms // 10
-        nxt = self.segment_length * self.stride_ms // 10
-        positions, pos = [], 0
-        while pos < T:
-            pos = min(pos + (nxt if positions else first), T)
-            positions.append(pos)
-        plan_rows = enc.stream_row_schedule(positions)
-        n_cap = int((plan_rows[-1] + 1) / enc.cif_layer.beta) + 4
+        sched = self._schedule(T)
+        n_cap = int((sched.rows[-1] + 1) / enc.cif_layer.beta) + 4
         st = dec.new_device_state(B, cap=cap, n_cap=n_cap)
         st["lockstep"] = False
         cst = enc.cif_layer.new_batched_state(B, cfg.embed_dim, n_cap)
-        src = FrameSource(fbank[0])
-        off = None
-        if encoder == "offline":
-            off = S2TEmformerEncoder.forward(enc, fbank, torch.full((B,), T, device=dev))["encoder_out_btd"]
-            if off.size(1) != plan_rows[-1]:
-                raise RuntimeError(f"offline encoder returned {off.size(1)} rows, the streaming schedule releases {plan_rows[-1]}")
-        enc_state, table, ms, mlen, r0 = {}, [], [], [], 0
-        for i, pos in enumerate(positions):
-            src.read(pos - src.pos)
-            finish = i == len(positions) - 1
-            if off is None:
-                out = S2TEmformerEncoder.infer(enc, fbank[:, :pos], torch.full((B,), pos), enc_state, finish=finish)["encoder_out_btd"]
-                if r0 + out.size(1) != plan_rows[i]:
-                    raise RuntimeError(f"streaming encoder released {r0 + out.size(1)} rows after chunk {i}, predicted {plan_rows[i]}")
-            else:
-                out = off[:, r0:plan_rows[i]]
-            r0 = plan_rows[i]
+        table = []
+        for _, _, finish, out in encoder_chunks(enc, fbank, sched, encoder):
             enc.cif_layer.infer_batched(out.contiguous(), cst, finish)
             table.append(cst["cif_len"].clone())
-            ms.append(src.elapsed_ms()); mlen.append(int(self.max_len(src.pos)))
-        n_chunks = len(positions)
+        ms, mlen, n_chunks = sched.ms, sched.max_len, len(sched.positions)
         i32 = dict(device=dev, dtype=torch.int32)
         sched_len = torch.stack(table, 1).contiguous()                            # [B][n_chunks]
         dec.project_cif(st, cst["cif"], 0, min(n_cap, int(sched_len[:, -1].max().item())))
-        sched = torch.tensor([[ms] * B, [mlen] * B], **i32)                       # [2][B][n_chunks]
+        sched_t = torch.tensor([[ms] * B, [mlen] * B], **i32)                     # [2][B][n_chunks]
         st["cif_len"] = sched_len[:, 0].clone()
         u8 = dict(device=dev, dtype=torch.uint8)
         online, done = torch.full((B,), 1 if n_chunks > 1 else 0, **u8), torch.zeros(B, **u8)
@@ -569,24 +542,16 @@ class BatchedCIFStreamingAgent(CIFAgent):
         delays, tok_chunk, chunk_idx = torch.zeros(B, cap, **i32), torch.zeros(B, cap, **i32), torch.zeros(B, **i32)
         st["tok"].fill_(cfg.eos)
         ctl = _lib.CifStreamCtl(online.data_ptr(), done.data_ptr(), delays.data_ptr(), hyp.data_ptr(), cap, 0, 0, n_chunks,
-                                sched_len.data_ptr(), sched[0].data_ptr(), sched[1].data_ptr(), chunk_idx.data_ptr(),
+                                sched_len.data_ptr(), sched_t[0].data_ptr(), sched_t[1].data_ptr(), chunk_idx.data_ptr(),
                                 st["cif_len"].data_ptr(), tok_chunk.data_ptr(), None)
-        bound, first, n_run = mlen[-1] + 2, mlen[-1] + 1, 0
-        while True:                                        # every round of an unfinished row is a WRITE: cap + 1 rounds, unless EOS
-            n = max(1, min(64, first - n_run) if n_run < first else min(8, bound - n_run))
-            dec.stream_steps(st, ctl, n, self.overshoot_weight)
-            n_run += n
-            if bool(done.all().item()):
-                break
-            if n_run >= bound:
-                raise RuntimeError("self-paced CIF rows unfinished after cap rounds")
-        from .agent import self_paced_records
+        # every round of an unfinished row is a WRITE: cap + 1 rounds, unless EOS
+        run_rounds(lambda n: dec.stream_steps(st, ctl, n, self.overshoot_weight), lambda: bool(done.all().item()),
+                   mlen[-1] + 1, mlen[-1] + 2, "self-paced CIF rows unfinished after cap rounds")
         clen_h = st["cif_len"].tolist()
-        return self_paced_records(hyp, delays, tok_chunk, st["n_prev"], chunk_idx, cap, [src.total_ms()] * B, "n_cif",
+        return self_paced_records(hyp, delays, tok_chunk, st["n_prev"], chunk_idx, cap, [sched.total_ms] * B, "n_cif",
                                   lambda b, c: clen_h[b])
 
     def _run_batch_lockstep(self, fbank: torch.Tensor):
-        from .latency import average_lagging
         model, dec, enc = self.model, self.model.decoder, self.model.encoder
         cfg, dev = model.cfg, model.device
         B, T = fbank.size(0), fbank.size(1)
@@ -602,57 +567,36 @@ class BatchedCIFStreamingAgent(CIFAgent):
         hyp = torch.zeros(B, cap, device=dev, dtype=torch.int64)
         delays = torch.zeros(B, cap, device=dev, dtype=torch.int32)
         st["tok"].fill_(cfg.eos)
-        enc_state = {}
-        src = FrameSource(fbank[0])
-        actions = [[] for _ in range(B)]
-        n_written = [0] * B
+        sched = self._schedule(T)
+        chunks, log = encoder_chunks(enc, fbank, sched), LockstepLog(B)
         cif_len_h = [0] * B
-        last_update = 0
-        expected = (self.segment_length + self.right_context) * self.stride_ms // 10
-        alive = list(range(B))
-        while alive:
+        while log.alive:
             # ---- READ phase: every unfinished stream takes the next chunk (agents/cif_agent.py:296-346)
-            for b in alive:
-                actions[b].append("R")
-            if src.finished:
+            log.read()
+            chunk = next(chunks, None)
+            if chunk is None:
                 raise RuntimeError("READ after source finished")
-            src.read(expected)
-            finish = (src.pos - last_update) < expected or src.finished
-            out = S2TEmformerEncoder.infer(enc, fbank[:, :src.pos], torch.full((B,), src.pos), enc_state, finish=finish)
-            enc.cif_layer.infer_batched(out["encoder_out_btd"].contiguous(), cst, finish)
-            last_update = src.pos
-            expected = self.segment_length * self.stride_ms // 10
+            c, _, finish, out = chunk
+            enc.cif_layer.infer_batched(out.contiguous(), cst, finish)
             new_len = cst["cif_len"].tolist()                      # one read-back per chunk: loop control + projection window
             lo, hi = min(cif_len_h), max(new_len)
             cif_len_h = new_len
             dec.project_cif(st, cst["cif"], lo, hi)
             # ---- WRITE phase: masked steps until no row can write any more
-            online.fill_(0 if src.finished else 1)
+            online.fill_(0 if finish else 1)
             ctl = _lib.CifStreamCtl(online.data_ptr(), done.data_ptr(), delays.data_ptr(), hyp.data_ptr(), cap,
-                                    src.elapsed_ms(), int(self.max_len(src.pos)), 0, None, None, None, None, None, None, None)
+                                    sched.ms[c], sched.max_len[c], 0, None, None, None, None, None, None, None)
             while True:
-                if src.finished:
+                if finish:
                     n_iter = 8                                     # rows write until EOS / the length cap
                 else:
-                    n_iter = max([cif_len_h[b] - n_written[b] for b in alive] + [0])
+                    n_iter = max([cif_len_h[b] - log.n_written[b] for b in log.alive] + [0])
                 if n_iter > 0:
                     dec.stream_steps(st, ctl, n_iter, self.overshoot_weight)
-                n_prev = st["n_prev"].tolist()
-                done_h = done.tolist()
-                for b in alive:
-                    actions[b].extend("W" * (n_prev[b] - n_written[b]))
-                    n_written[b] = n_prev[b]
-                alive = [b for b in alive if not done_h[b]]
-                if not src.finished or not alive:
+                log.wrote(st["n_prev"].tolist(), done.tolist())
+                if not finish or not log.alive:
                     break
-        hyp_h, delays_h = hyp.tolist(), delays.tolist()
-        recs = []
-        for b in range(B):
-            n = n_written[b]
-            d = [int(x) for x in delays_h[b][:n]]
-            recs.append({"tokens": hyp_h[b][:n], "delays_ms": d, "actions": "".join(actions[b]),
-                         "AL": average_lagging(d, src.total_ms()), "n_cif": cif_len_h[b]})
-        return recs
+        return log.records(hyp, delays, sched.total_ms, "n_cif", lambda b: cif_len_h[b])
 
 
 @register_model_architecture("cif_transformer", "cif_transformer_s")

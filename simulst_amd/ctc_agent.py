@@ -6,16 +6,15 @@ taken over those rows only (Ops.linear_pick: no logits in memory) and collapsed 
 before, so a run of one label that spans a chunk boundary is written once, at its first row.  Every new token is a WRITE stamped with
 the source milliseconds released by that READ; EOS is written when the source ends.
 
-This is the synthetic harness's loop (agent.FrameSource), not a SimulEval-facing agent.  Any model whose encoder carries the head
+This is the synthetic harness's loop (stream_source.py), not a SimulEval-facing agent.  Any model whose encoder carries the head
 streams here, the offline s2t_emformer included: there is no decoder and no read/write policy to ask for.
 """
 import torch
 
-from .agent import SHIFT_SIZE, FrameSource, chunk_positions
-from .encoder import S2TEmformerEncoder
+from .stream_source import ChunkedAgent, encoder_chunks
 
 
-class CTCAgent:
+class CTCAgent(ChunkedAgent):
     """One stream (B = 1).  Record keys are the other agents': "tokens" (EOS last), "delays_ms", "actions", "AL", plus "frames": the
     encoder row at which each token's run starts (EOS: the number of rows the source gave)."""
 
@@ -24,30 +23,22 @@ class CTCAgent:
         if getattr(enc.w, "ctc", None) is None:
             raise ValueError(f"{type(self).__name__}: this model has no CTC head (ModelConfig.ctc_layer is off)")
         self.model, self.blank = model, int(blank)
-        self.stride_ms = enc.conv_layer_stride() * SHIFT_SIZE
-        self.right_context, self.segment_length = enc.right_context, enc.segment_length
-        self.eos = model.cfg.eos
-
-    def _chunk_positions(self, T: int):
-        return chunk_positions(T, self.segment_length, self.right_context, self.stride_ms)
+        self._init_chunks(model)
 
     def _run(self, fbank: torch.Tensor, return_states: bool):
         """fbank [B, T, 80], rows advancing in lockstep -> (records, rows seen [B, n, D] or None)"""
         from .latency import average_lagging
         model, enc = self.model, self.model.encoder
         B, T = fbank.size(0), fbank.size(1)
-        src = FrameSource(fbank[0] if B else fbank.new_zeros(0, 80))
+        sched = self._schedule(T)
         recs = [{"tokens": [], "delays_ms": [], "frames": [], "actions": []} for _ in range(B)]
-        enc_state, seen, n_rows = {}, [], 0
+        seen, n_rows, now = [], 0, 0
         carry = torch.full((B, 1), -1, device=model.device, dtype=torch.int32)       # no label yet: row 0 never continues a run
-        for pos in self._chunk_positions(T):
-            src.read(pos - src.pos)
+        # the Emformer's own rows: what a subclass adds behind them (the CIF layer) is nothing the head reads
+        for c, _, _, new in encoder_chunks(enc, fbank, sched):
             for r in recs:
                 r["actions"].append("R")
-            # the READ that ends the source flushes the encoder's look-ahead rows (agents/default_agent.py:303-342).  The Emformer's own
-            # infer: what a subclass adds behind the encoder rows (the CIF layer) is nothing the head reads
-            new = S2TEmformerEncoder.infer(enc, fbank[:, :pos], torch.full((B,), pos), enc_state, finish=src.finished)["encoder_out_btd"]
-            n = new.size(1)
+            n, now = new.size(1), sched.ms[c]
             if n == 0:
                 continue
             if return_states:
@@ -57,16 +48,15 @@ class CTCAgent:
             keep = (pick != self.blank) & (pick != before)
             b_idx, t_idx = keep.nonzero(as_tuple=True)                                 # row-major: each stream's tokens in row order
             labels = pick[b_idx, t_idx].tolist()
-            now = src.elapsed_ms()
             for b, t, tok in zip(b_idx.tolist(), t_idx.tolist(), labels):
                 r = recs[b]
                 r["tokens"].append(tok), r["frames"].append(n_rows + t), r["delays_ms"].append(now), r["actions"].append("W")
             carry = pick[:, -1:].clone()
             n_rows += n
         for r in recs:
-            r["tokens"].append(self.eos), r["frames"].append(n_rows), r["delays_ms"].append(src.elapsed_ms()), r["actions"].append("W")
+            r["tokens"].append(self.eos), r["frames"].append(n_rows), r["delays_ms"].append(now), r["actions"].append("W")
             r["actions"] = "".join(r["actions"])
-            r["AL"] = average_lagging(r["delays_ms"], src.total_ms())
+            r["AL"] = average_lagging(r["delays_ms"], sched.total_ms)
         states = None
         if return_states:
             states = torch.cat(seen, dim=1) if seen else fbank.new_zeros(B, 0, model.cfg.embed_dim)

@@ -20,7 +20,7 @@ from typing import List, Sequence
 
 import torch
 
-from .agent import SHIFT_SIZE, WINDOW_SIZE, FrameSource, chunk_positions
+from .stream_source import ChunkedAgent, FrameSource, encoder_chunks, offline_states, source_ms
 
 
 def emit_delays(emit: Sequence[int], n_tokens: int, enc_len: int, k: int, schedule: Sequence[int]) -> List[int]:
@@ -55,7 +55,7 @@ def records_from_chunks(tokens, emit, chunks, positions, max_len, eos, total_ms,
     toks, delays, emits, tc = [], [], [], []
     for t, e, c in zip(tokens, emit, chunks):
         toks.append(int(t)), emits.append(int(e)), tc.append(c)
-        delays.append(positions[c] * SHIFT_SIZE + (WINDOW_SIZE - SHIFT_SIZE))
+        delays.append(source_ms(positions[c]))
         if int(t) == eos or len(toks) > max_len(positions[c]):
             break
     n_read = tc[-1] + 1 if tc else len(positions)
@@ -64,7 +64,7 @@ def records_from_chunks(tokens, emit, chunks, positions, max_len, eos, total_ms,
             "n_enc": n_enc_of(n_read - 1), "emit": emits}
 
 
-class TransducerAgent:
+class TransducerAgent(ChunkedAgent):
     """One simultaneous stream (B = 1) over TransducerModel: READ while the row waits and the source has not ended, otherwise
     WRITE.  Tokens are picked as greedy_offline picks them (pad masked, EOS masked at the first step); the hypothesis ends at EOS
     or when it outgrows max_len(frames read), FairseqSimulSTAgent's rule.  What is written is what generate_offline writes up to
@@ -74,20 +74,8 @@ class TransducerAgent:
         if getattr(model.cfg, "model", None) != "transducer_model":
             raise ValueError(f"{type(self).__name__} decodes transducer_model, not {getattr(model.cfg, 'model', None)!r}")
         self.model = model
-        enc = model.encoder
-        self.stride_ms = enc.conv_layer_stride() * SHIFT_SIZE
-        self.right_context, self.segment_length = enc.right_context, enc.segment_length
+        self._init_chunks(model)
         self.max_len = lambda x: min(max_len_a * x + max_len_b, model.max_decoder_positions())
-        self.eos = model.cfg.eos
-
-    def _first_chunk(self):
-        return (self.segment_length + self.right_context) * self.stride_ms // SHIFT_SIZE
-
-    def _next_chunk(self):
-        return self.segment_length * self.stride_ms // SHIFT_SIZE
-
-    def _chunk_positions(self, T: int):
-        return chunk_positions(T, self.segment_length, self.right_context, self.stride_ms)
 
     def _new_state(self, B: int, T: int):
         dec, k = self.model.decoder, self.model.cfg.downsample
@@ -104,8 +92,8 @@ class TransducerAgent:
         from .latency import average_lagging
         model, dec, dev = self.model, self.model.decoder, self.model.device
         src = FrameSource(fbank)
-        enc_state, st, last_update = {}, None, 0
-        expected = self._first_chunk()
+        enc_state, st = {}, None
+        expected = self.first_frames
         tokens, delays, emits, actions = [], [], [], []
         toks = torch.full((1,), self.eos, device=dev, dtype=torch.int64)
         while True:
@@ -119,14 +107,12 @@ class TransducerAgent:
                         break                                              # ... existed: the hypothesis ends empty
                     raise RuntimeError("READ after source finished")
                 actions.append("R")
-                src.read(expected)
-                update_len = src.pos - last_update
-                finish = update_len < expected or src.finished            # agents/default_agent.py:303-342
+                finish = src.take(expected)                                # agents/default_agent.py:303-342
                 new = model.encoder.infer(fbank[:src.pos].unsqueeze(0), torch.tensor([src.pos]), enc_state, finish=finish)["encoder_out_btd"]
                 if st is None:
                     st = self._new_state(1, fbank.size(0))
                 dec.append_source(st, new, new.size(1), finish)
-                last_update, expected = src.pos, self._next_chunk()
+                expected = self.next_frames
                 continue
             actions.append("W")
             toks = self._pick(logits, first=not tokens)
@@ -165,38 +151,24 @@ class BatchedTransducerStreamingAgent(TransducerAgent):
             return self._run_batch_self_paced(fbank, encoder, Ls)
         return self._run_batch_lockstep(fbank[:, :Ls[0]], encoder)
 
-    def _offline_states(self, fbank, Ls, schedules):
-        e = self.model.encoder.forward(fbank, torch.tensor(Ls, device=self.model.device))
-        if e["encoder_lengths"].tolist() != [s[-1] for s in schedules]:
-            raise RuntimeError("offline encoder lengths differ from the rows the streaming schedule releases")
-        return e["encoder_out_btd"]
-
     def _run_batch_lockstep(self, fbank: torch.Tensor, encoder: str):
         from .latency import average_lagging
         model, dec, enc, dev = self.model, self.model.decoder, self.model.encoder, self.model.device
         B, T = fbank.size(0), fbank.size(1)
         fbank = fbank.to(dev)
-        positions = self._chunk_positions(T)
-        schedule = enc.stream_row_schedule(positions)
-        states = self._offline_states(fbank, [T] * B, [schedule] * B) if encoder == "offline" else None
+        sched = self._schedule(T)
+        schedule = sched.rows
+        chunks = encoder_chunks(enc, fbank, sched, encoder)
         st = self._new_state(B, T)
-        enc_state = {}
         toks = torch.full((B,), self.eos, device=dev, dtype=torch.int64)
         tokens, delays, emits, actions = ([[] for _ in range(B)] for _ in range(4))
         done = [False] * B
-        for c, pos in enumerate(positions):
-            if all(done):
-                break
-            finish = c == len(positions) - 1
+        for c, pos, finish, new in chunks:
             for b in range(B):
                 if not done[b]:
                     actions[b].append("R")
-            if states is None:
-                new = enc.infer(fbank[:, :pos], torch.full((B,), pos), enc_state, finish=finish)["encoder_out_btd"]
-            else:
-                new = states[:, (schedule[c - 1] if c else 0):schedule[c]]
             dec.append_source(st, new, new.size(1), finish)
-            ms, cap = pos * SHIFT_SIZE + (WINDOW_SIZE - SHIFT_SIZE), self.max_len(pos)
+            ms, cap = sched.ms[c], self.max_len(pos)
             while True:                                                    # rounds until every row waits or has ended
                 logits, wrote = dec.step_online(st, toks)
                 if st.n_wrote:                                             # some row wrote
@@ -217,13 +189,12 @@ class BatchedTransducerStreamingAgent(TransducerAgent):
                         dec.sync_source(st)
                     continue
                 break
-            if finish and not all(done) and any(a == 0 for a in st.avail_host):
-                break                                                      # no pooled position at all: the hypotheses end empty
+            if all(done) or (finish and any(a == 0 for a in st.avail_host)):
+                break                                  # every row has ended, or no pooled position at all: the hypotheses end empty
         if not all(done) and all(a > 0 for a in st.avail_host):
             raise RuntimeError("rows still waiting after the source finished")
-        total_ms = T * SHIFT_SIZE + (WINDOW_SIZE - SHIFT_SIZE)
         return [{"tokens": tokens[b], "delays_ms": delays[b], "actions": "".join(actions[b]),
-                 "AL": average_lagging(delays[b], total_ms), "n_enc": schedule[len(actions[b]) - len(tokens[b]) - 1], "emit": emits[b]}
+                 "AL": average_lagging(delays[b], sched.total_ms), "n_enc": schedule[len(actions[b]) - len(tokens[b]) - 1], "emit": emits[b]}
                 for b in range(B)]
 
     def _run_batch_self_paced(self, fbank: torch.Tensor, encoder: str, Ls):
@@ -231,20 +202,12 @@ class BatchedTransducerStreamingAgent(TransducerAgent):
         k = model.cfg.downsample
         B, T = fbank.size(0), fbank.size(1)
         fbank = fbank.to(dev)
-        per_T = {}
-        for t in set(Ls):
-            positions = self._chunk_positions(t)
-            per_T[t] = (positions, enc.stream_row_schedule(positions))
+        per_T = {t: self._schedule(t) for t in set(Ls)}
         if encoder == "offline":
-            states = self._offline_states(fbank, Ls, [per_T[t][1] for t in Ls])
+            states, _ = offline_states(enc, fbank, Ls, [per_T[t] for t in Ls])
         else:
-            enc_state, positions, outs = {}, per_T[T][0], []
-            for i, pos in enumerate(positions):
-                outs.append(enc.infer(fbank[:, :pos], torch.full((B,), pos), enc_state, finish=i == len(positions) - 1)["encoder_out_btd"])
-            states = torch.cat(outs, 1)
-            if states.size(1) != per_T[T][1][-1]:
-                raise RuntimeError(f"streaming encoder released {states.size(1)} rows, stream_row_schedule predicted {per_T[T][1][-1]}")
-        enc_len = [per_T[t][1][-1] for t in Ls]
+            states = torch.cat([new for _, _, _, new in encoder_chunks(enc, fbank, per_T[T])], 1)
+        enc_len = [per_T[t].rows[-1] for t in Ls]
         empty = [n == 0 for n in enc_len]
         # every row is its own utterance: pooled over whole windows (the buffer padded to a multiple of k), a row's partial last
         # window is the mean of its valid rows, as append_source flushes it
@@ -256,9 +219,9 @@ class BatchedTransducerStreamingAgent(TransducerAgent):
         hyp, emit = hyp.tolist(), emit.tolist()
         recs = []
         for b, t in enumerate(Ls):
-            positions, schedule = per_T[t]
+            s = per_T[t]
             n = 0 if empty[b] else len(hyp[b])
-            chunks = emit_delays(emit[b], n, enc_len[b], k, schedule)
-            recs.append(records_from_chunks(hyp[b][:n], emit[b][:n], chunks, positions, self.max_len, self.eos,
-                                            t * SHIFT_SIZE + (WINDOW_SIZE - SHIFT_SIZE), lambda c, s=schedule: s[c]))
+            chunks = emit_delays(emit[b], n, enc_len[b], k, s.rows)
+            recs.append(records_from_chunks(hyp[b][:n], emit[b][:n], chunks, s.positions, self.max_len, self.eos, s.total_ms,
+                                            lambda c, s=s: s.rows[c]))
         return recs

@@ -129,17 +129,14 @@ def _mma_pass(cfg, model, dec, enc, agent, fb, recs, traces, n_utt, copies, T, w
     from simulst_amd import _lib
     dev = model.device
     B, H, Ld, V = fb.size(0), cfg.num_heads, cfg.decoder_layers, cfg.vocab
-    positions = agent._chunk_positions(T)
-    plan_rows = enc.stream_row_schedule(positions)
+    from simulst_amd.stream_source import encoder_chunks
+    sched = agent._schedule(T)
     cap = int(agent.max_len(T)) + 6
-    st = dec.new_state(B, cap=cap, S_cap=max(plan_rows[-1], 1))
+    st = dec.new_state(B, cap=cap, S_cap=max(sched.rows[-1], 1))
     st.lockstep = False
-    enc_state = {}
     with torch.no_grad():
-        for i, pos in enumerate(positions):          # every chunk through the streaming encoder, as the self-paced form does
-            new = enc.infer(fb[:, :pos], torch.full((B,), pos), enc_state, finish=i == len(positions) - 1)["encoder_out_btd"]
+        for _, _, _, new in encoder_chunks(enc, fb, sched):     # every chunk through the streaming encoder, as the self-paced form does
             dec.append_encoder_out(st, new, torch.full((B,), st.enc_rows + new.size(1)))
-    assert st.enc_rows == plan_rows[-1]
     P_cap = st.S_cap // cfg.pre_decision_ratio + 2
     i32, u8, i64 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.uint8), dict(device=dev, dtype=torch.int64)
     active, read_flag, online, done = torch.zeros(B, **u8), torch.zeros(B, **u8), torch.zeros(B, **u8), torch.zeros(B, **u8)
@@ -231,7 +228,7 @@ def audit_cif(cfg, w, utts, copies=9, dtype=torch.bfloat16, device="cuda:0", log
     from oracle.configs import from_model_config
     from simulst_amd import _lib
     from simulst_amd.cif import BatchedCIFStreamingAgent, CIFTransformerModel
-    from simulst_amd.encoder import S2TEmformerEncoder
+    from simulst_amd.stream_source import encoder_chunks
     ecfg, dcfg = from_model_config(cfg)
     recs, traces = [], []
     torch.set_num_threads(min(os.cpu_count() or 1, 16))
@@ -247,24 +244,16 @@ def audit_cif(cfg, w, utts, copies=9, dtype=torch.bfloat16, device="cuda:0", log
     agent = BatchedCIFStreamingAgent(model, max_len_a=MAX_LEN_A, max_len_b=MAX_LEN_B)
     dev = model.device
     fb = torch.stack(utts).repeat(copies, 1, 1).to(device=dev, dtype=dtype)
-    first = (agent.segment_length + agent.right_context) * agent.stride_ms // 10
-    nxt = agent.segment_length * agent.stride_ms // 10
-    positions, pos = [], 0
-    while pos < T:
-        pos = min(pos + (nxt if positions else first), T)
-        positions.append(pos)
-    plan_rows = enc.stream_row_schedule(positions)
-    n_cap = int((plan_rows[-1] + 1) / beta) + 4
+    sched = agent._schedule(T)
+    positions = sched.positions
+    n_cap = int((sched.rows[-1] + 1) / beta) + 4
     cap = int(agent.max_len(T)) + 6
     # ---- encoder side: every chunk through the streaming encoder and the batched integrate-and-fire (trajectory-independent)
     cst = enc.cif_layer.new_batched_state(B, cfg.embed_dim, n_cap)
-    enc_state, ctrace, r0 = {}, [], 0
+    ctrace = []
     with torch.no_grad():
-        for i, pos in enumerate(positions):
-            o = S2TEmformerEncoder.infer(enc, fb[:, :pos], torch.full((B,), pos), enc_state, finish=i == len(positions) - 1)["encoder_out_btd"]
-            assert r0 + o.size(1) == plan_rows[i]
-            r0 = plan_rows[i]
-            enc.cif_layer.infer_batched(o.contiguous(), cst, i == len(positions) - 1, trace=ctrace)
+        for _, _, finish, o in encoder_chunks(enc, fb, sched):
+            enc.cif_layer.infer_batched(o.contiguous(), cst, finish, trace=ctrace)
     cum_err, cum_signed, count_diffs, copy_mismatch = [], [], [], 0
     got_counts = torch.stack([(c["n"] - (0 if c["finish"] else 1)).cpu() for c in ctrace], 1)           # [B][chunks] vectors released per update
     got_asum = torch.stack([c["alpha_sum"].cpu() for c in ctrace], 1)

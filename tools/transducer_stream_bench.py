@@ -120,9 +120,10 @@ def main(argv=None):
                          "distinct_emit_positions": len({e for r in recs for e in r["emit"]})}
         res["records_equal"] = all(a[k] == b[k] for a, b in zip(agent.run_batch(fb), agent.run_batch(fb, self_paced=True))
                                    for k in ("tokens", "delays_ms", "actions", "emit"))
-        positions = agent._chunk_positions(T)
-        schedule = model.encoder.stream_row_schedule(positions)
-        states = agent._offline_states(fb, [T] * B, [schedule] * B)
+        from simulst_amd.stream_source import offline_states
+        sched = agent._schedule(T)
+        positions, schedule = sched.positions, sched.rows
+        states, _ = offline_states(model.encoder, fb, [T] * B, [sched] * B)
         for name, rc in (("cached_g", False), ("recompute_g", True)):
             resume_steps(agent, states, positions, schedule, rc)           # warm-up
             ev, km, written = resume_steps(agent, states, positions, schedule, rc)
