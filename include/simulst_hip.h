@@ -56,7 +56,7 @@ enum {
   SIMULST_EPI_BIAS_F32OUT = 5, /* C (always fp32) = A W^T + b   (logits, energies)  */
   SIMULST_EPI_BIAS_RES_GELU = 6, /* C = gelu_erf(A W^T + b + R)   (CIF FakeCrossAttn, models/cif_transformer.py:357-362) */
   /* (7 is skipped: it is the value the plan tests record as refused with "unknown epilogue", and stays refused) */
-  SIMULST_EPI_ROW_PICK = 8     /* z = A W^T + b in fp32 is never written: C (int32, ONE element per row at the row's C address) = the
+  SIMULST_EPI_ROW_PICK = 8,    /* z = A W^T + b in fp32 is never written: C (int32, ONE element per row at the row's C address) = the
                                   lowest column at which z is largest, aux (fp32 [M][2], logical row order) = (max z, logsumexp z).
                                   The best path of a CTC head (criterion/joint_ctc_criterion.py:92-101) and its log-probabilities,
                                   aux[r][0] - aux[r][1].  aux is required; a residual, a LayerNorm prologue, a_lead, c_head_dim and
@@ -64,6 +64,17 @@ enum {
                                   N % 16 == 0, K % 32 == 0, K <= 448).  bf16 with K % 32 == 0 and K <= 448 runs on the matrix
                                   cores (csrc/gemm_pick.hip), other shapes on the VALU.  Fewer than 128 panels of 64 rows: the columns are
                                   split over workgroups and the parts folded from the library's own scratch (no caller buffer). */
+  SIMULST_EPI_ROW_GATHER = 9   /* z as above, never written: C (fp32) [b * c_batch_stride + i * c_row_stride + j] = z[r][lab[b][j]] -
+                                  logsumexp_n z[r][n] for j < aux_rows: the log-probabilities of the caller's labels, which is all a CTC
+                                  recursion over a given transcript reads (F.ctc_loss of criterion/joint_ctc_criterion.py:78-90 without
+                                  the [B, Te, V] logits).  aux is an INPUT here: int32 labels, lab[b][j] at aux + b * aux_batch_stride + j
+                                  (device memory, so not checked on the host: a label outside [0, N) is CLAMPED into it).  Any
+                                  c_batch_stride / c_row_stride (a time-major result is a choice of strides).  aux is required,
+                                  aux_rows >= 1 (E_SHAPE); a residual, a LayerNorm prologue, a_lead, c_head_dim and c_tensor_heads are
+                                  refused (E_ARG) as for ROW_PICK; W is row-major ONLY (w_fragment_major: E_SHAPE -- the gather reads
+                                  whole rows of W by label).  Same kernels, same forms and the same column split as ROW_PICK; the
+                                  gathered z runs the sweep's own instruction sequence.  (No new entry point, no descriptor field:
+                                  the value was refused as unknown before, so simulst_version() stays 108.) */
 };
 
 /* monotonic attention flavours (modules/__init__.py:11-16 registry names minus the
@@ -217,8 +228,8 @@ typedef struct {
   int64_t r_batch_stride, r_row_stride;
   int32_t epilogue, dtype;
   float scale;                 /* GLU output scale (embed_scale), else unused */
-  int32_t n_main, aux_rows;    /* EMF_OUT only */
-  int64_t aux_batch_stride;    /* EMF_OUT only */
+  int32_t n_main, aux_rows;    /* EMF_OUT; ROW_GATHER: aux_rows = labels per batch (n_main unused) */
+  int64_t aux_batch_stride;    /* EMF_OUT; ROW_GATHER: elements between two batches' label lists */
   const float* ln_gamma;       /* optional LayerNorm PROLOGUE: A rows are normalised (eps 1e-5, fp32 stats,   */
   const float* ln_beta;        /* rounded to the operand dtype) before the contraction; NULL = none.          */
                                /* Supported when M <= 128 and rows do not overlap (decode-step shapes).       */
@@ -574,7 +585,13 @@ int simulst_pack_fragment_major(simulst_handle* h, const void* W, void* out, int
  *              frames >= input_lengths[b] get state 0 / blank, as the reference returns
  *   scratch    simulst_ctc_best_alignment_scratch_bytes(N, S, max_target_length) bytes (1-byte back-pointers)
  *   neg_log_likelihood  optional fp32 [N]: -log of the two final Viterbi scores' sum (the kernel's first output)
- * Tie rules are the reference's: predecessor preference s, s-1, s-2 under strict '>', first maximum at the end. */
+ * Tie rules are the reference's: predecessor preference s, s-1, s-2 under strict '>', first maximum at the end.
+ * out == NULL (pointer presence, as simulst_rnnt_forward): the SUM over alignments instead.  neg_log_likelihood is then required
+ * (E_NULL) and receives the true CTC negative log-likelihood of each utterance -- F.ctc_loss(reduction="none"),
+ * criterion/joint_ctc_criterion.py:78-90: the same state recursion with log-add over the legal predecessors in place of max (s-2 only
+ * between different labels), -log of the two final states' sum, +inf when no alignment exists (never NaN), T = 0 the sum of the
+ * blanks.  No back-pointers: scratch is not read and may be NULL; as_labels is ignored; the 1023-label limit is the same.  The
+ * arguments existed before with a refused value, so simulst_version() stays 108. */
 int64_t simulst_ctc_best_alignment_scratch_bytes(int32_t N, int32_t S, int32_t max_target_length);
 int simulst_ctc_best_alignment(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
                                int64_t lp_stride_v, const int64_t* targets, int64_t tg_stride_b,

@@ -133,6 +133,68 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict_
   }
 }
 
+// log(e^a + e^b + e^c) over the legal predecessors; -inf when all are (no NaN from -inf - -inf)
+__device__ __forceinline__ float log_add3(float a, float b, float c) {
+  const float m = fmaxf(a, fmaxf(b, c));
+  if (m == -INFINITY) return -INFINITY;
+  return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
+}
+
+// The sum over alignments (the CTC negative log-likelihood, F.ctc_loss(reduction="none") of criterion/joint_ctc_criterion.py:78-90):
+// the recursion above with log-add in place of max, no back-pointers, alpha in the same two LDS rows.  +inf when no alignment exists.
+__global__ __launch_bounds__(256) void ctc_nll_kernel(const float* __restrict__ lp, long lp_t, long lp_b, long lp_v,
+                                                      const long* __restrict__ targets, long tg_b, const long* __restrict__ in_len,
+                                                      const long* __restrict__ tg_len, int ns_max, int blank, float* __restrict__ nll) {
+  extern __shared__ unsigned char smem_raw[];
+  float* a0 = reinterpret_cast<float*>(smem_raw);          // [ns_max + 2], index shifted by 2 so s-1, s-2 exist
+  float* a1 = a0 + ns_max + 2;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int L = (int)in_len[b], T = (int)tg_len[b];
+  const int sl = 2 * T + 1;
+  const long* tg = targets + (long)b * tg_b;
+  const float* lpb = lp + (long)b * lp_b;
+  if (L <= 0) {                                            // no frame: only the empty transcript has an (empty) alignment
+    if (tid == 0) nll[b] = T == 0 ? 0.f : INFINITY;
+    return;
+  }
+  int cur[MAX_SPT];
+  bool three[MAX_SPT];
+#pragma unroll
+  for (int j = 0; j < MAX_SPT; ++j) {
+    const int s = tid + 256 * j;
+    cur[j] = blank; three[j] = false;
+    if (s < sl && T > 0) {
+      cur[j] = (s & 1) ? (int)tg[s >> 1] : blank;
+      three[j] = s > 1 && ((s & 1) ? (int)tg[(s - 2) >> 1] : blank) != cur[j];
+    }
+  }
+  if (tid < 2) { a0[tid] = -INFINITY; a1[tid] = -INFINITY; }
+  for (int s = tid; s < ns_max; s += 256) {
+    float v = -INFINITY;
+    if (s == 0) v = lpb[(long)blank * lp_v];
+    else if (s == 1 && T > 0) v = lpb[(long)tg[0] * lp_v];
+    a0[s + 2] = v;
+  }
+  __syncthreads();
+  float* prev = a0;
+  float* nxt = a1;
+  for (int t = 1; t < L; ++t) {
+    const float* lpt = lpb + (long)t * lp_t;
+#pragma unroll
+    for (int j = 0; j < MAX_SPT; ++j) {
+      const int s = tid + 256 * j;
+      if (s < ns_max) {
+        float v = -INFINITY;
+        if (s < sl) v = log_add3(prev[s + 2], prev[s + 1], three[j] ? prev[s] : -INFINITY) + lpt[(long)cur[j] * lp_v];
+        nxt[s + 2] = v;
+      }
+    }
+    __syncthreads();
+    float* tmp = prev; prev = nxt; nxt = tmp;
+  }
+  if (tid == 0) nll[b] = -log_add3(prev[2 * T + 2], T > 0 ? prev[2 * T + 1] : -INFINITY, -INFINITY);
+}
+
 }  // namespace
 
 extern "C" int64_t simulst_ctc_best_alignment_scratch_bytes(int32_t N, int32_t S, int32_t max_target_length) {
@@ -147,10 +209,19 @@ extern "C" int simulst_ctc_best_alignment(simulst_handle* h, const float* log_pr
                                           int64_t* out, float* neg_log_likelihood) {
   if (!h) return SIMULST_E_NULL;
   SL_CHECK_NULL(h, log_probs); SL_CHECK_NULL(h, targets); SL_CHECK_NULL(h, input_lengths); SL_CHECK_NULL(h, target_lengths);
-  SL_CHECK_NULL(h, out);
+  // out == NULL (the pointer-presence convention of simulst_rnnt_forward): the sum over alignments, which has no path to write
+  if (!out) SL_CHECK_NULL(h, neg_log_likelihood);
   SL_REQUIRE(h, S > 0 && max_target_length >= 0 && blank >= 0, SIMULST_E_SHAPE, "simulst_ctc_best_alignment: shape");
   const int ns = 2 * max_target_length + 1;
   SL_REQUIRE(h, ns <= 256 * MAX_SPT, SIMULST_E_SHAPE, "simulst_ctc_best_alignment: more than 1023 target labels");
+  if (!out) {
+    if (N <= 0) return SIMULST_OK;
+    KTimer t(h, SIMULST_K_SCAN);                            // (at most 16 KB of LDS: no raise)
+    hipLaunchKernelGGL(ctc_nll_kernel, dim3(N), dim3(256), (size_t)2 * (ns + 2) * sizeof(float), h->stream, log_probs,
+                       (long)lp_stride_t, (long)lp_stride_b, (long)lp_stride_v, (const long*)targets, (long)tg_stride_b,
+                       (const long*)input_lengths, (const long*)target_lengths, ns, blank, neg_log_likelihood);
+    return sl_launch_status(h, "simulst_ctc_best_alignment (sum)");
+  }
   const size_t lds = (size_t)2 * (ns + 2) * sizeof(float) + (size_t)BT_CHUNK * ns;
   SL_REQUIRE(h, lds <= 144 * 1024, SIMULST_E_SHAPE, "simulst_ctc_best_alignment: LDS");
   if (N <= 0) return SIMULST_OK;

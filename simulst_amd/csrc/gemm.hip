@@ -445,6 +445,16 @@ extern "C" int simulst_linear(simulst_handle* h, const simulst_linear_desc* d, c
     SL_REQUIRE(h, d->a_lead == 0, SIMULST_E_ARG, "simulst_linear: row pick takes no a_lead");
     SL_CHECK_NULL(h, aux);
   }
+  if (d->epilogue == SIMULST_EPI_ROW_GATHER) {
+    // C holds aux_rows fp32 per row, aux the labels they are gathered at: the same operands mean nothing here as for the row pick
+    SL_REQUIRE(h, R == nullptr, SIMULST_E_ARG, "simulst_linear: row gather takes no residual");
+    SL_REQUIRE(h, !d->ln_gamma && !d->ln_beta, SIMULST_E_ARG, "simulst_linear: row gather takes no LayerNorm prologue");
+    SL_REQUIRE(h, d->c_head_dim == 0 && d->c_tensor_heads == 0, SIMULST_E_ARG, "simulst_linear: row gather writes aux_rows elements per row (no head-major output)");
+    SL_REQUIRE(h, d->a_lead == 0, SIMULST_E_ARG, "simulst_linear: row gather takes no a_lead");
+    SL_CHECK_NULL(h, aux);
+    SL_REQUIRE(h, d->aux_rows >= 1, SIMULST_E_SHAPE, "simulst_linear: row gather needs aux_rows >= 1 labels per batch");
+    SL_REQUIRE(h, !d->w_fragment_major, SIMULST_E_SHAPE, "simulst_linear: row gather reads rows of W by label: row-major weights only (no fragment-major)");
+  }
   if (d->M_batches == 0) return SIMULST_OK;
   long M = (long)d->M_batches * d->rows_per_batch;
   SL_REQUIRE(h, M < (1L << 31), SIMULST_E_SHAPE, "simulst_linear: too many rows");

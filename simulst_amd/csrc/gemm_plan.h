@@ -35,7 +35,8 @@ enum sl_linear_family {
   SL_LIN_TILE256,        // 256 x 256 GLU tiles, register-staged or on the LDS-DMA ring (gemm_tile256.hip)
   SL_LIN_TILE128,        // 128 x 128 tiles (gemm.hip)
   SL_LIN_TILE64,         // 64 x 64 tiles (gemm.hip)
-  SL_LIN_ROW_PICK,       // SIMULST_EPI_ROW_PICK: per-row (argmax, max, logsumexp), logits never written (gemm_pick.hip)
+  SL_LIN_ROW_PICK,       // SIMULST_EPI_ROW_PICK: per-row (argmax, max, logsumexp), logits never written (gemm_pick.hip);
+                         //   SIMULST_EPI_ROW_GATHER (plan.epi): log-probabilities at the caller's labels, same kernels
 };
 
 struct sl_linear_plan {

@@ -351,6 +351,18 @@ class S2TEmformerEncoder:
         from .ctc import ctc_greedy
         return ctc_greedy(self.ops, self.w.ctc, enc_btd, enc_len, blank=blank, pad=self.cfg.padding_idx)
 
+    def ctc_score(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, targets: torch.Tensor, target_lengths: torch.Tensor, *,
+                  blank: int = 0, align: bool = False):
+        """CTC negative log-likelihood of given transcripts under the head over encoder rows (forward()'s "encoder_out_btd" /
+        "encoder_lengths"): {"nll", "lprobs"} and, with align, {"alignment", "best_nll"} as ctc.ctc_score describes them.  The head's
+        logits are not written: only the log-probabilities of the blank and of the transcript's labels leave the projection
+        (Ops.linear_gather).  ValueError without a head."""
+        if self.w.ctc is None:
+            raise ValueError("ctc_score: this model has no CTC head (ModelConfig.ctc_layer is off / no encoder.ctc_layer.weight)")
+        from .ctc import ctc_score
+        return ctc_score(self.ops, self.w.ctc, enc_btd, enc_len, targets, target_lengths, blank=blank, pad=self.cfg.padding_idx,
+                         align=align)
+
 
     # ================================================================== streaming (Emformer.infer)
     def new_stream_state(self, B: int):

@@ -125,6 +125,35 @@ class Ops:
             return (out[0], zmax[0], lse[0]) if Bb else (out.reshape(0), zmax.reshape(0), lse.reshape(0))
         return out, zmax, lse
 
+    def linear_gather(self, x, W, bias, labels, out=None):
+        """Log-probabilities of given labels under z = x @ W[N, K]^T + bias without the logits (simulst_linear, SIMULST_EPI_ROW_GATHER):
+        out[b, t, j] = z[b, t, labels[b, j]] - logsumexp_n z[b, t, n], fp32.
+
+        x: [B, T, K] (rows K-contiguous, any batch and row stride -- the encoder's output rows are read where they lie); W [N, K]
+        row-major in x's dtype; labels int32 [B, L'] on the device, L' >= 1, rows L'-contiguous (values outside [0, N) are clamped into
+        it); out: an fp32 tensor or view [B, T, L'] whose last dimension is contiguous, any other strides (a time-major buffer viewed
+        as [B, T, L'] is how ctc.ctc_rescore lays its result out); default a new contiguous one."""
+        _chk_contig(W)
+        _p(x), _p(W), _p(labels)
+        if x.dim() != 3 or (x.stride(-1) != 1 and x.numel()):
+            raise ValueError("linear_gather: x is [B, T, K] with contiguous rows")
+        Bb, T, K = x.shape
+        N = W.shape[0]
+        if W.shape[1] != K or W.dtype != x.dtype:
+            raise ValueError("linear_gather: W is [N, K] in x's dtype")
+        if labels.dtype != torch.int32 or labels.dim() != 2 or labels.size(0) != Bb or labels.size(1) < 1 or labels.stride(1) != 1:
+            raise ValueError("linear_gather: labels is an int32 [B, L' >= 1] tensor with contiguous rows")
+        Lp = labels.size(1)
+        if out is None:
+            out = torch.empty(Bb, T, Lp, device=x.device, dtype=torch.float32)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (Bb, T, Lp) or (out.stride(2) != 1 and out.numel()):
+            raise ValueError("linear_gather: out is an fp32 [B, T, L'] tensor or view with a contiguous last dimension")
+        if Bb * T:
+            self.linear_raw(x, W, bias, out, M_batches=Bb, rows_per_batch=T, N=N, K=K, a_bs=x.stride(0), a_rs=x.stride(1),
+                            c_bs=out.stride(0), c_rs=out.stride(1), epilogue=_lib.EPI_ROW_GATHER, aux=labels, aux_rows=Lp,
+                            aux_bs=labels.stride(0))
+        return out
+
     def causal_conv1d_glu(self, x, Wp, bp, *, ksize, stride, scale=1.0, out=None):
         """Strided causal Conv1d + GLU over channel-last frames.
         x [B, T_in, C_in] whose first (ksize-1) frames are LEFT CONTEXT (zeros at utterance start,
