@@ -64,7 +64,7 @@ enum {
                                   N % 16 == 0, K % 32 == 0, K <= 448).  bf16 with K % 32 == 0 and K <= 448 runs on the matrix
                                   cores (csrc/gemm_pick.hip), other shapes on the VALU.  Fewer than 128 panels of 64 rows: the columns are
                                   split over workgroups and the parts folded from the library's own scratch (no caller buffer). */
-  SIMULST_EPI_ROW_GATHER = 9   /* z as above, never written: C (fp32) [b * c_batch_stride + i * c_row_stride + j] = z[r][lab[b][j]] -
+  SIMULST_EPI_ROW_GATHER = 9,  /* z as above, never written: C (fp32) [b * c_batch_stride + i * c_row_stride + j] = z[r][lab[b][j]] -
                                   logsumexp_n z[r][n] for j < aux_rows: the log-probabilities of the caller's labels, which is all a CTC
                                   recursion over a given transcript reads (F.ctc_loss of criterion/joint_ctc_criterion.py:78-90 without
                                   the [B, Te, V] logits).  aux is an INPUT here: int32 labels, lab[b][j] at aux + b * aux_batch_stride + j
@@ -75,6 +75,17 @@ enum {
                                   whole rows of W by label).  Same kernels, same forms and the same column split as ROW_PICK; the
                                   gathered z runs the sweep's own instruction sequence.  (No new entry point, no descriptor field:
                                   the value was refused as unknown before, so simulst_version() stays 108.) */
+  /* (10 is skipped like 7: the tests record it as refused with "unknown epilogue", and it stays refused) */
+  SIMULST_EPI_ROW_TOPK = 11    /* z as above, never written: the best k = aux_rows columns of every row (1 <= k <= 8, E_SHAPE) and their
+                                  log-probabilities -- the per-frame candidates of a CTC prefix beam search.  n_main = keep: a column
+                                  that is always reported (the blank), or -1 for none (keep >= N or < -1: E_SHAPE); k' = k +
+                                  (keep >= 0) slots a row.  C (int32, k' elements at the row's C address, b * c_batch_stride + i *
+                                  c_row_stride): slot 0 = keep when given, then the k columns other than keep with the largest z,
+                                  descending, on equal z the lower column first; slots past the columns that exist hold -1.  aux
+                                  (fp32 [M][k' + 1], logical row order, required): z - logsumexp(z) of every slot (-inf for a -1
+                                  slot), then the row's logsumexp.  Refusals, fragment-major rule, kernel classes and column split
+                                  as for ROW_PICK; a column's z runs the pick sweep's instruction sequence, so the rank-0 column
+                                  without keep is ROW_PICK's pick.  (No new entry point, no descriptor field, version 108.) */
 };
 
 /* monotonic attention flavours (modules/__init__.py:11-16 registry names minus the
@@ -228,7 +239,7 @@ typedef struct {
   int64_t r_batch_stride, r_row_stride;
   int32_t epilogue, dtype;
   float scale;                 /* GLU output scale (embed_scale), else unused */
-  int32_t n_main, aux_rows;    /* EMF_OUT; ROW_GATHER: aux_rows = labels per batch (n_main unused) */
+  int32_t n_main, aux_rows;    /* EMF_OUT; ROW_GATHER: aux_rows = labels per batch (n_main unused); ROW_TOPK: aux_rows = k, n_main = keep */
   int64_t aux_batch_stride;    /* EMF_OUT; ROW_GATHER: elements between two batches' label lists */
   const float* ln_gamma;       /* optional LayerNorm PROLOGUE: A rows are normalised (eps 1e-5, fp32 stats,   */
   const float* ln_beta;        /* rounded to the operand dtype) before the contraction; NULL = none.          */

@@ -19,6 +19,7 @@ F32, BF16 = 0, 1
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_GLU, EPI_EMF_OUT, EPI_BIAS_F32OUT, EPI_BIAS_RES_GELU = range(7)
 EPI_ROW_PICK = 8           # (7 is skipped: the value the plan tests hold refused as an unknown epilogue)
 EPI_ROW_GATHER = 9         # log-probabilities at the caller's labels (aux: int32 labels, an input), logits never written
+EPI_ROW_TOPK = 11          # the best k columns of a row with their log-probabilities (10 stays refused as unknown, like 7)
 ATTN_HARD, ATTN_INFINITE_LOOKBACK, ATTN_WAITK, ATTN_CHUNKWISE, ATTN_FULL = range(5)
 (K_LINEAR, K_LAYERNORM, K_EMF_ATTN, K_CONV_POS, K_DEC_SELF_ATTN, K_DEC_CROSS_ATTN, K_SCAN, K_ARGMAX,
  K_MISC, K_LINEAR_SKINNY, K_LINEAR_TILE64, K_DEC_QKV_CHAIN, K_DEC_PROJ_CHAIN, K_DEC_FFN_CHAIN, K_DEC_ATTN_CHAIN,

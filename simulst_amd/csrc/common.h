@@ -42,6 +42,7 @@ enum sl_lds_slot {
   SL_LDS_TILE256_RING,      //   ... and the LDS-DMA ring
   SL_LDS_WSTAT,             // gemm_wstat.hip
   SL_LDS_JOINER_LATTICE,    // transducer.hip joiner_lattice_kernel
+  SL_LDS_ROW_TOPK,          // gemm_pick.hip row_topk_mfma_kernel
   SL_LDS_COUNT
 };
 

@@ -455,6 +455,16 @@ extern "C" int simulst_linear(simulst_handle* h, const simulst_linear_desc* d, c
     SL_REQUIRE(h, d->aux_rows >= 1, SIMULST_E_SHAPE, "simulst_linear: row gather needs aux_rows >= 1 labels per batch");
     SL_REQUIRE(h, !d->w_fragment_major, SIMULST_E_SHAPE, "simulst_linear: row gather reads rows of W by label: row-major weights only (no fragment-major)");
   }
+  if (d->epilogue == SIMULST_EPI_ROW_TOPK) {
+    // C holds k' int32 per row and aux k' + 1 fp32: the row pick's operands, with aux_rows = k and n_main = the column always reported
+    SL_REQUIRE(h, R == nullptr, SIMULST_E_ARG, "simulst_linear: row top-k takes no residual");
+    SL_REQUIRE(h, !d->ln_gamma && !d->ln_beta, SIMULST_E_ARG, "simulst_linear: row top-k takes no LayerNorm prologue");
+    SL_REQUIRE(h, d->c_head_dim == 0 && d->c_tensor_heads == 0, SIMULST_E_ARG, "simulst_linear: row top-k writes k' elements per row (no head-major output)");
+    SL_REQUIRE(h, d->a_lead == 0, SIMULST_E_ARG, "simulst_linear: row top-k takes no a_lead");
+    SL_CHECK_NULL(h, aux);
+    SL_REQUIRE(h, d->aux_rows >= 1 && d->aux_rows <= PICK_TOPK_MAX, SIMULST_E_SHAPE, "simulst_linear: row top-k needs 1 <= aux_rows (k) <= 8");
+    SL_REQUIRE(h, d->n_main >= -1 && d->n_main < d->N, SIMULST_E_SHAPE, "simulst_linear: row top-k needs n_main (keep) = -1 or a column of [0, N)");
+  }
   if (d->M_batches == 0) return SIMULST_OK;
   long M = (long)d->M_batches * d->rows_per_batch;
   SL_REQUIRE(h, M < (1L << 31), SIMULST_E_SHAPE, "simulst_linear: too many rows");

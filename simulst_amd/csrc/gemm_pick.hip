@@ -18,6 +18,9 @@
 // gather phase over the SAME staged rows computes z at the caller's labels of the row's batch -- C[row][j] = z[row][lab[b][j]] - lse,
 // the log-probabilities a CTC recursion over a given transcript reads.  The gathered z runs the sweep's instruction sequence (same k
 // order, same accumulator start), so it is the value the sweep saw for that column.  Labels outside [0, N) are clamped into it.
+//
+// SIMULST_EPI_ROW_TOPK has kernels of its own further down (row_topk_*): the same sweep and the same plan, with per-row candidate
+// lists in place of the single running index.
 #include "gemm_plan.h"
 #include "gemv_mfma.h"
 
@@ -354,12 +357,385 @@ __global__ __launch_bounds__(256) void row_pick_valu_kernel(const T* __restrict_
   }
 }
 
+// ---- SIMULST_EPI_ROW_TOPK: the best k columns of a row (value descending, on equal values the lower column first) ------------------------
+// A candidate is ONE 64-bit key: the order-preserving integer image of its fp32 z in the high word, ~column in the low one.  A larger
+// key is a better candidate, keys of different columns differ, so every selection below is a total order and its result does not depend
+// on the order in which tiles, lanes, waves or column parts meet.  0 is "no candidate" (below the key of every real value).
+//   sweep: the pick's (same k order, same accumulator start), with the running (max, sum) of the gather form.  Every row has a bound
+//     thr[row] -- the key of the k-th best candidate some wave has seen so far, never above the true k-th -- and each WAVE its own
+//     candidate list cand[wave][row][TOPK_CAP]: a column at or above the bound is appended (one compare per element in the common case,
+//     about k ln(N / k) appends a row); a full list is reduced to its best k by rank (16 lanes a row, every lane counts the entries
+//     that beat its own), which raises the bound.  The lists are the wave's own: no barrier inside the sweep.
+//   close: every list is reduced to its best k, then 32 lanes a row rank the 4 x k survivors and store the row (or its part record).
+typedef unsigned long long topk_key;
+constexpr int TOPK_MAX = PICK_TOPK_MAX, TOPK_CAP = PICK_TOPK_CAP;
+constexpr int TOPK_REC = PICK_TOPK_REC_BYTES / 4;           // floats of a part record: (max, sum, z at keep, -) and TOPK_MAX keys
+static_assert(TOPK_REC * 4 == 16 + TOPK_MAX * 8, "part record");
+
+__device__ __forceinline__ topk_key topk_make(float x, int c) {
+  x = x == 0.f ? 0.f : x;                                   // (-0 and +0 are one value)
+  const int b = __float_as_int(x);
+  const unsigned hi = (unsigned)(b ^ ((b >> 31) & 0x7fffffff)) ^ 0x80000000u;
+  return ((topk_key)hi << 32) | (unsigned)~c;
+}
+__device__ __forceinline__ int topk_col(topk_key v) { return v ? (int)~(unsigned)v : -1; }
+__device__ __forceinline__ float topk_val(topk_key v) {
+  const int k = (int)((unsigned)(v >> 32) ^ 0x80000000u);
+  return v ? __int_as_float(k ^ ((k >> 31) & 0x7fffffff)) : -INFINITY;
+}
+__device__ __forceinline__ topk_key topk_shfl_xor(topk_key v, int o) {
+  const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
+  return ((topk_key)hi << 32) | lo;
+}
+
+// one row's k' ids at C, its k' log-probabilities and its logsumexp at aux: slot j of the k non-keep columns
+__device__ __forceinline__ void topk_store_slot(const LinArgs& p, int32_t* __restrict__ C, float* __restrict__ aux, int row, int j,
+                                                topk_key v, float lse) {
+  const int b = row / p.rpb, ii = row - b * p.rpb, kb = p.n_main >= 0, kp = p.aux_rows + kb;
+  C[(long)b * p.c_bs + (long)ii * p.c_rs + kb + j] = topk_col(v);
+  aux[(long)row * (kp + 1) + kb + j] = topk_val(v) - lse;
+}
+__device__ __forceinline__ void topk_store_row(const LinArgs& p, int32_t* __restrict__ C, float* __restrict__ aux, int row, float zkeep,
+                                               float lse) {
+  const int b = row / p.rpb, ii = row - b * p.rpb, kb = p.n_main >= 0, kp = p.aux_rows + kb;
+  if (kb) {
+    C[(long)b * p.c_bs + (long)ii * p.c_rs] = p.n_main;
+    aux[(long)row * (kp + 1)] = zkeep - lse;
+  }
+  aux[(long)row * (kp + 1) + kp] = lse;
+}
+
+// a wave's lists reduced to their best k, sorted: the full ones (all = false) or every one.  16 lanes a row, 4 rows a step.
+__device__ __noinline__ void topk_compact(volatile topk_key* cand_w, volatile int* cnt_w, topk_key* thr, int k, bool all, int lane) {
+  const int g = lane >> 4, i = lane & 15;
+  for (int step = 0; step < PICK_M / 4; ++step) {
+    const int row = step * 4 + g;
+    const int n_raw = cnt_w[row];
+    const bool act = all || n_raw >= TOPK_CAP;
+    if (!__any(act)) continue;                              // (uniform over the wave)
+    const int n = min(n_raw, TOPK_CAP);
+    topk_key my = 0;
+    int rank = 0;
+    if (act) {
+      my = i < n ? cand_w[row * TOPK_CAP + i] : 0;
+#pragma unroll
+      for (int j = 0; j < TOPK_CAP; ++j) {
+        const topk_key o = cand_w[row * TOPK_CAP + j];
+        rank += (j < n && o > my) ? 1 : 0;
+      }
+    }
+    __threadfence_block();                                  // every lane has read the list before one writes into it
+    if (act && i < n && rank < k) {
+      cand_w[row * TOPK_CAP + rank] = my;
+      if (rank == k - 1) atomicMax(&thr[row], my);
+    }
+    if (act && i == 0) cnt_w[row] = min(n, k);
+    __threadfence_block();
+  }
+}
+
+template <bool W_FM>
+__global__ __launch_bounds__(256, 2) void row_topk_mfma_kernel(const bf16* __restrict__ A, const bf16* __restrict__ W,
+                                                            const float* __restrict__ bias, int32_t* __restrict__ C,
+                                                            float* __restrict__ aux, float* __restrict__ part, LinArgs p) {
+  constexpr int KS = gemv::MF<bf16>::KS, G = gemv::MF<bf16>::G, R = PICK_M / 16;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  bf16* zs = reinterpret_cast<bf16*>(smem_raw);
+  __shared__ float red_m[4][PICK_M], red_s[4][PICK_M], zkeep[PICK_M];
+  __shared__ int cnt[4][PICK_M];
+  __shared__ topk_key thr[PICK_M];
+  const int ldz = p.K + G;
+  topk_key* cand = reinterpret_cast<topk_key*>(smem_raw + (size_t)PICK_M * ldz * sizeof(bf16));     // [4][PICK_M][TOPK_CAP]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m0 = blockIdx.x * PICK_M;
+  const int n_rt = min(R, (p.M - m0 + 15) >> 4);
+  const int k = p.aux_rows, keep = p.n_main;
+  topk_key* cand_w = cand + (size_t)wave * PICK_M * TOPK_CAP;
+
+  cnt[wave][lane] = 0;
+  if (tid < PICK_M) { thr[tid] = 0; zkeep[tid] = -INFINITY; }
+  const int groups = p.K / G;
+  for (int i = tid; i < 16 * n_rt * groups; i += 256) {
+    const int r = i / groups, c = (i - r * groups) * G, row = m0 + r;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (row < p.M) {
+      const int b = row / p.rpb, ii = row - b * p.rpb;
+      v = ld16(A + (long)b * p.a_bs + (long)ii * p.a_rs + c);
+    }
+    *reinterpret_cast<uint4*>(zs + (long)r * ldz + c) = v;
+  }
+  __syncthreads();
+
+  const int n_vt = (p.N + 15) >> 4, nks = p.K / KS;
+  const int per = (n_vt + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int vt0 = blockIdx.y * per, vt1 = min(vt0 + per, n_vt);
+  const int col = lane & 15, lg = lane >> 4;
+  float rm[R][4], rs[R][4];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { rm[r][e] = LAT_NEG; rs[r][e] = 0.f; }
+
+  for (int vt = vt0 + 2 * wave; vt < vt1; vt += 8) {
+    const bool two = vt + 1 < vt1;
+    const int c0 = vt * 16 + col, c1 = c0 + 16;
+    const bool ok0 = c0 < p.N, ok1 = two && c1 < p.N;
+    const bf16 *w0, *w1;
+    long step;
+    if constexpr (W_FM) {
+      w0 = W + ((long)vt * nks * 64 + lane) * G;
+      w1 = two ? w0 + (long)nks * 64 * G : w0;
+      step = 64 * G;
+    } else {
+      w0 = W + (long)(ok0 ? c0 : p.N - 1) * p.K + lg * G;
+      w1 = W + (long)(ok1 ? c1 : p.N - 1) * p.K + lg * G;
+      step = KS;
+    }
+    f32x4 acc0[R], acc1[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { acc0[r] = f32x4{0.f, 0.f, 0.f, 0.f}; acc1[r] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    uint4 wa = ld16(w0), wb = ld16(w1);
+    for (int ks = 0; ks < nks; ++ks) {
+      const uint4 ca = wa, cb = wb;
+      if (ks + 1 < nks) { wa = ld16(w0 + (ks + 1) * step); wb = ld16(w1 + (ks + 1) * step); }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (r >= n_rt) continue;                            // uniform over the workgroup
+        const uint4 a = *reinterpret_cast<const uint4*>(zs + (long)(16 * r + col) * ldz + ks * KS + lg * G);
+        acc0[r] = lat_mma<bf16>(a, ca, acc0[r]);
+        acc1[r] = lat_mma<bf16>(a, cb, acc1[r]);
+      }
+    }
+    const float b0 = (bias && ok0) ? bias[c0] : 0.f, b1 = (bias && ok1) ? bias[c1] : 0.f;
+    const bool in0 = ok0 && c0 != keep, in1 = ok1 && c1 != keep;
+    unsigned pend = 0;                                      // bit 2 (4 r + e) + j: column cj of row 16 r + 4 lg + e waits for a slot
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int lr = 16 * r + 4 * lg + e;
+        const float x0 = ok0 ? acc0[r][e] + b0 : -INFINITY, x1 = ok1 ? acc1[r][e] + b1 : -INFINITY;
+        lse_pair(rm[r][e], rs[r][e], x0, x1);
+        if (ok0 && c0 == keep) zkeep[lr] = x0;
+        if (ok1 && c1 == keep) zkeep[lr] = x1;
+        const topk_key t = __hip_atomic_load(&thr[lr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // (one 8-byte read)
+        if (r >= n_rt) continue;                            // (a row tile without rows collects nothing)
+        if (in0 && topk_make(x0, c0) >= t) pend |= 1u << (2 * (4 * r + e));
+        if (in1 && topk_make(x1, c1) >= t) pend |= 2u << (2 * (4 * r + e));
+      }
+    while (__any(pend != 0)) {
+      unsigned fail = 0;
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int lr = 16 * r + 4 * lg + e;
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const unsigned bit = (1u << j) << (2 * (4 * r + e));
+            if (!(pend & bit)) continue;
+            const topk_key v = j ? topk_make(acc1[r][e] + b1, c1) : topk_make(acc0[r][e] + b0, c0);
+            if (v < __hip_atomic_load(&thr[lr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) continue;                // the bound has passed it meanwhile
+            const int slot = atomicAdd(&cnt[wave][lr], 1);
+            if (slot < TOPK_CAP) cand_w[lr * TOPK_CAP + slot] = v;
+            else fail |= bit;
+          }
+        }
+      pend = fail;
+      __threadfence_block();
+      if (__any(fail != 0)) topk_compact(cand_w, cnt[wave], thr, k, false, lane);
+    }
+  }
+  __threadfence_block();
+  topk_compact(cand_w, cnt[wave], thr, k, true, lane);
+  // fold the 16 columns of a lane group; the 4 waves meet below
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        const float om = __shfl_xor(rm[r][e], o, 64), os = __shfl_xor(rs[r][e], o, 64);
+        lse_join(rm[r][e], rs[r][e], om, os);
+      }
+      const int lr = 16 * r + 4 * lg + e;
+      if (col == 0) { red_m[wave][lr] = rm[r][e]; red_s[wave][lr] = rs[r][e]; }
+    }
+  __syncthreads();
+  // 32 lanes a row: lane j holds entry j & 7 of wave j >> 3 and counts the survivors that beat it
+  const int half = lane >> 5, j = lane & 31, jw = j >> 3, ji = j & 7;
+  for (int step = 0; step < PICK_M / 8; ++step) {
+    const int lr = wave * (PICK_M / 4) + step * 2 + half, row = m0 + lr;
+    if (row >= p.M) continue;
+    const topk_key my = ji < cnt[jw][lr] ? cand[((size_t)jw * PICK_M + lr) * TOPK_CAP + ji] : 0;
+    int rank = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int n = cnt[w][lr];
+      total += n;
+#pragma unroll
+      for (int i = 0; i < TOPK_MAX; ++i) {
+        const topk_key o = cand[((size_t)w * PICK_M + lr) * TOPK_CAP + i];
+        rank += (i < n && o > my) ? 1 : 0;
+      }
+    }
+    total = min(total, k);
+    float m = red_m[0][lr], s = red_s[0][lr];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) lse_join(m, s, red_m[w][lr], red_s[w][lr]);
+    if (part) {
+      float* rec = part + ((long)row * gridDim.y + blockIdx.y) * TOPK_REC;
+      topk_key* keys = reinterpret_cast<topk_key*>(rec + 4);
+      if (my && rank < k) keys[rank] = my;
+      if (j < TOPK_MAX && j >= total) keys[j] = 0;
+      if (j == 0) *reinterpret_cast<float4*>(rec) = make_float4(m, s, zkeep[lr], 0.f);
+    } else {
+      const float lse = m + logf(s);
+      if (my && rank < k) topk_store_slot(p, C, aux, row, rank, my, lse);
+      if (j < k && j >= total) topk_store_slot(p, C, aux, row, j, 0, lse);
+      if (j == 0) topk_store_row(p, C, aux, row, zkeep[lr], lse);
+    }
+  }
+}
+
+// a wave per row: the (max, sum) of the parts joined in part order, then k rounds of "the best key below the last one"
+__global__ __launch_bounds__(256) void row_topk_fold_kernel(const float* __restrict__ part, int n_split, int32_t* __restrict__ C,
+                                                            float* __restrict__ aux, LinArgs p) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= p.M) return;
+  const float* rec0 = part + (long)row * n_split * TOPK_REC;
+  float m = LAT_NEG, s = 0.f, zk = -INFINITY;
+  for (int q = 0; q < n_split; ++q) {
+    const float4 v = *reinterpret_cast<const float4*>(rec0 + (long)q * TOPK_REC);
+    lse_join(m, s, v.x, v.y);
+    zk = fmaxf(zk, v.z);
+  }
+  const float lse = m + logf(s);
+  topk_key prev = ~0ull;
+  for (int r = 0; r < p.aux_rows; ++r) {
+    topk_key best = 0;
+    for (int c = lane; c < n_split * TOPK_MAX; c += 64) {
+      const topk_key v = reinterpret_cast<const topk_key*>(rec0 + (long)(c / TOPK_MAX) * TOPK_REC + 4)[c % TOPK_MAX];
+      if (v < prev && v > best) best = v;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const topk_key ov = topk_shfl_xor(best, o);
+      best = ov > best ? ov : best;
+    }
+    if (lane == 0) topk_store_slot(p, C, aux, row, r, best, lse);
+    prev = best;
+  }
+  if (lane == 0) topk_store_row(p, C, aux, row, zk, lse);
+}
+
+// VALU: the pick's sweep once per rank -- round r takes, per row, the best key below round r - 1's.  Correctness only.
+template <typename T>
+__global__ __launch_bounds__(256) void row_topk_valu_kernel(const T* __restrict__ A, const T* __restrict__ W,
+                                                            const float* __restrict__ bias, int32_t* __restrict__ C,
+                                                            float* __restrict__ aux, LinArgs p) {
+  __shared__ float red_m[4][PICK_VM], red_s[4][PICK_VM], zkeep[PICK_VM], lse_s[PICK_VM];
+  __shared__ topk_key red_k[4][PICK_VM];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m0 = blockIdx.x * PICK_VM;
+  const T* arow[PICK_VM];
+#pragma unroll
+  for (int r = 0; r < PICK_VM; ++r) {
+    const int row = min(m0 + r, p.M - 1);                   // rows past the end repeat the last one and are not stored
+    const int b = row / p.rpb, ii = row - b * p.rpb;
+    arow[r] = A + (long)b * p.a_bs + (long)ii * p.a_rs;
+  }
+  if (tid < PICK_VM) zkeep[tid] = -INFINITY;
+  __syncthreads();
+  topk_key prev[PICK_VM];
+#pragma unroll
+  for (int r = 0; r < PICK_VM; ++r) prev[r] = ~0ull;
+  for (int round = 0; round < p.aux_rows; ++round) {
+    float rm[PICK_VM], rs[PICK_VM];
+    topk_key best[PICK_VM];
+#pragma unroll
+    for (int r = 0; r < PICK_VM; ++r) { rm[r] = LAT_NEG; rs[r] = 0.f; best[r] = 0; }
+    for (int c = tid; c < p.N; c += 256) {
+      float x[PICK_VM];
+      valu_column<T>(arow, W + (long)c * p.K, p.K, bias ? bias[c] : 0.f, x);
+#pragma unroll
+      for (int r = 0; r < PICK_VM; ++r) {
+        if (round == 0) {
+          lse_pair(rm[r], rs[r], x[r], -INFINITY);
+          if (c == p.n_main) zkeep[r] = x[r];
+        }
+        const topk_key v = topk_make(x[r], c);
+        if (c != p.n_main && v < prev[r] && v > best[r]) best[r] = v;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < PICK_VM; ++r) {
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const topk_key ov = topk_shfl_xor(best[r], o);
+        best[r] = ov > best[r] ? ov : best[r];
+        if (round == 0) {
+          const float om = __shfl_xor(rm[r], o, 64), os = __shfl_xor(rs[r], o, 64);
+          lse_join(rm[r], rs[r], om, os);
+        }
+      }
+      if (lane == 0) { red_k[wave][r] = best[r]; if (round == 0) { red_m[wave][r] = rm[r]; red_s[wave][r] = rs[r]; } }
+    }
+    __syncthreads();
+    if (round == 0 && tid < PICK_VM) {
+      float m = red_m[0][tid], s = red_s[0][tid];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) lse_join(m, s, red_m[w][tid], red_s[w][tid]);
+      lse_s[tid] = m + logf(s);
+    }
+#pragma unroll
+    for (int r = 0; r < PICK_VM; ++r) {
+      topk_key b = red_k[0][r];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) b = red_k[w][r] > b ? red_k[w][r] : b;
+      prev[r] = b;
+    }
+    __syncthreads();
+    if (tid < PICK_VM && m0 + tid < p.M) {
+      topk_key mine = prev[0];
+#pragma unroll
+      for (int r = 1; r < PICK_VM; ++r) mine = tid == r ? prev[r] : mine;
+      topk_store_slot(p, C, aux, m0 + tid, round, mine, lse_s[tid]);
+      if (round == 0) topk_store_row(p, C, aux, m0 + tid, zkeep[tid], lse_s[tid]);
+    }
+  }
+}
+
 }  // namespace
+
+static int sl_launch_row_topk(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p, float* part) {
+  // panel + lists pass the default dynamic-LDS limit from K = 224 on
+  static const sl_lds_limit limits[] = {{(const void*)row_topk_mfma_kernel<false>, 100 * 1024}, {(const void*)row_topk_mfma_kernel<true>, 100 * 1024}};
+  const dim3 grid(pl.grid[0], pl.grid[1]), block(256);
+  int32_t* C = (int32_t*)o.C;
+  float* aux = (float*)o.aux;
+  if (pl.pick_mfma) {
+    if (int rc = sl_raise_lds(h, SL_LDS_ROW_TOPK, limits, "simulst_linear (row top-k)")) return rc;
+    KTimer t(h, pl.timer);
+    const bf16 *A = (const bf16*)o.A, *W = (const bf16*)o.W;
+    if (p.w_packed) hipLaunchKernelGGL((row_topk_mfma_kernel<true>), grid, block, pl.lds, h->stream, A, W, o.bias, C, aux, part, p);
+    else hipLaunchKernelGGL((row_topk_mfma_kernel<false>), grid, block, pl.lds, h->stream, A, W, o.bias, C, aux, part, p);
+    if (part) hipLaunchKernelGGL(row_topk_fold_kernel, dim3((p.M + 3) / 4), block, 0, h->stream, part, pl.splits, C, aux, p);
+  } else {
+    KTimer t(h, pl.timer);
+    if (pl.dtype == SIMULST_F32)
+      hipLaunchKernelGGL((row_topk_valu_kernel<float>), grid, block, 0, h->stream, (const float*)o.A, (const float*)o.W, o.bias, C, aux, p);
+    else
+      hipLaunchKernelGGL((row_topk_valu_kernel<bf16>), grid, block, 0, h->stream, (const bf16*)o.A, (const bf16*)o.W, o.bias, C, aux, p);
+  }
+  return sl_launch_status(h, "simulst_linear (row top-k)");
+}
 
 int sl_launch_row_pick(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops& o, const LinArgs& p) {
   float4* part = nullptr;
   if (pl.splits > 1) {                                       // the library's own scratch, as simulst_linear's split-K partials
-    const size_t need = (size_t)pl.splits * p.M * sizeof(float4);
+    const bool topk = pl.epi == SIMULST_EPI_ROW_TOPK;
+    const size_t need = (size_t)pl.splits * p.M * (topk ? TOPK_REC * sizeof(float) : sizeof(float4));
     if (h->ws_bytes < need) {
       if (h->capturing) { h->err = "simulst_linear: scratch too small while capturing a graph"; return SIMULST_E_ARG; }
       if (h->ws) (void)hipFree(h->ws);
@@ -370,6 +746,7 @@ int sl_launch_row_pick(simulst_handle* h, const sl_linear_plan& pl, const sl_lin
     }
     part = (float4*)h->ws;
   }
+  if (pl.epi == SIMULST_EPI_ROW_TOPK) return sl_launch_row_topk(h, pl, o, p, (float*)part);
   KTimer t(h, pl.timer);
   const dim3 grid(pl.grid[0], pl.grid[1]), block(256);
   const bool gather = pl.epi == SIMULST_EPI_ROW_GATHER;

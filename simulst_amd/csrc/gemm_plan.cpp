@@ -195,6 +195,8 @@ static bool tile256_ok(const simulst_handle* h, int dtype, int epi, const LinArg
 // (a stream's chunk, a lockstep round: under 8192 rows) split the column tiles over blockIdx.y, at least 8 tiles a part (one pair per
 // wave), towards one workgroup per compute unit -- the parts fold through the library's scratch in a second launch.
 // SIMULST_EPI_ROW_GATHER takes the same plan (row-major weights only): its gather phase rides behind the sweep of the same launch.
+// SIMULST_EPI_ROW_TOPK takes it too, column split included (a part's record is PICK_TOPK_REC_BYTES a row, in the same scratch: 2 MB at
+// most, 127 panels in 3 parts); its per-wave candidate lists follow the panel in dynamic LDS.
 static sl_linear_plan plan_row_pick(sl_linear_plan pl, const LinArgs& p) {
   const long panel = (long)PICK_M * (p.K + 8) * 2;
   pl.family = SL_LIN_ROW_PICK;
@@ -205,7 +207,7 @@ static sl_linear_plan plan_row_pick(sl_linear_plan pl, const LinArgs& p) {
   if (p.w_packed && !(pl.pick_mfma && p.N % 16 == 0))
     return refused(pl, SIMULST_E_SHAPE, "simulst_linear: row pick takes fragment-major weights in bf16 with N % 16 == 0, K % 32 == 0, K <= 448");
   pl.grid[0] = cdiv(p.M, pl.pick_mfma ? PICK_M : PICK_VM);
-  pl.lds = pl.pick_mfma ? (unsigned)panel : 0;
+  pl.lds = pl.pick_mfma ? (unsigned)panel + (pl.epi == SIMULST_EPI_ROW_TOPK ? PICK_TOPK_LDS : 0) : 0;
   pl.splits = 1;
   if (pl.pick_mfma && pl.grid[0] < 128) {
     const unsigned by_width = cdiv(cdiv(p.N, 16), 8), by_chip = cdiv(256, pl.grid[0]);
@@ -220,7 +222,7 @@ sl_linear_plan sl_plan_linear(const simulst_handle* h, int dtype, int epi, const
   sl_linear_plan pl = {};
   pl.dtype = dtype; pl.epi = epi; pl.ln = p.ln_g != nullptr;
   pl.grid[0] = pl.grid[1] = pl.grid[2] = 1;
-  if (epi == SIMULST_EPI_ROW_PICK || epi == SIMULST_EPI_ROW_GATHER) return plan_row_pick(pl, p);
+  if (epi == SIMULST_EPI_ROW_PICK || epi == SIMULST_EPI_ROW_GATHER || epi == SIMULST_EPI_ROW_TOPK) return plan_row_pick(pl, p);
   const int G = dtype == SIMULST_F32 ? 4 : 8;
   const bool skinny_ok = p.M <= (p.w_packed ? SKINNY_MAX_ROWS_PACKED : SKINNY_MAX_ROWS) && p.a_lead == 0 && p.a_rs >= p.K &&
                          epi != SIMULST_EPI_GLU && epi != SIMULST_EPI_EMF_OUT;

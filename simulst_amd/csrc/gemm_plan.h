@@ -22,6 +22,10 @@ constexpr int SKINNY_MAX_ROWS = 2048, SKINNY_MAX_ROWS_PACKED = 8192;
 // row pick (gemm_pick.hip): rows of a workgroup's LDS panel on the matrix cores, the panel's byte limit (with the kernel's 3 KB of
 // static LDS inside the default 64 KB: no raise), rows per workgroup of the VALU form
 constexpr int PICK_M = 64, PICK_LDS_MAX = 60 * 1024, PICK_VM = 4;
+// SIMULST_EPI_ROW_TOPK: at most 8 columns a row; every wave keeps a list of 16 eight-byte candidates per row behind the panel (the
+// launcher raises the kernel's dynamic-LDS limit); bytes of a column part's record of one row in the library's scratch
+constexpr int PICK_TOPK_MAX = 8, PICK_TOPK_CAP = 16, PICK_TOPK_REC_BYTES = 80;
+constexpr unsigned PICK_TOPK_LDS = 4 * PICK_M * PICK_TOPK_CAP * 8;
 
 enum sl_linear_family {
   SL_LIN_REFUSED = 0,
@@ -36,7 +40,8 @@ enum sl_linear_family {
   SL_LIN_TILE128,        // 128 x 128 tiles (gemm.hip)
   SL_LIN_TILE64,         // 64 x 64 tiles (gemm.hip)
   SL_LIN_ROW_PICK,       // SIMULST_EPI_ROW_PICK: per-row (argmax, max, logsumexp), logits never written (gemm_pick.hip);
-                         //   SIMULST_EPI_ROW_GATHER (plan.epi): log-probabilities at the caller's labels, same kernels
+                         //   SIMULST_EPI_ROW_GATHER (plan.epi): log-probabilities at the caller's labels, same kernels;
+                         //   SIMULST_EPI_ROW_TOPK (plan.epi): the best k columns of a row, same sweep and plan
 };
 
 struct sl_linear_plan {

@@ -9,7 +9,13 @@ token, ``ctc_report`` is the accuracy report of the reference's JointCTCCriterio
 and the CTC term of criterion/cif_criterion.py), optionally with the forced alignment: the projection writes only the log-probabilities
 of the blank and of the transcript's own labels, [B, Te, L + 1] (Ops.linear_gather: SIMULST_EPI_ROW_GATHER), and the recursion of
 ctc_align.ctc_nll runs over them.  ``ctc_rescore`` re-ranks n-best lists with that score, one gather per utterance for all its
-hypotheses, and ``CTCTranscriber.score_ctc`` is the model-level call.  Prefix beam search is not here, and no gradient is computed.
+hypotheses, and ``CTCTranscriber.score_ctc`` is the model-level call.
+
+``ctc_topk`` is the head's per-frame candidate list -- the blank and the best k other labels with their log-probabilities, again
+without the logits (Ops.linear_topk: SIMULST_EPI_ROW_TOPK) --, ``ctc_prefix_beam_advance`` the time-synchronous prefix beam search over
+such lists (device tensor operations, no host synchronisation inside the frame loop; the state goes in and comes out, so that chunks of
+rows continue one search), ``ctc_prefix_beam_search`` the two together and ``CTCTranscriber.transcribe_ctc_nbest`` the model-level call,
+whose hypotheses ``ctc_rescore`` gives their exact likelihoods.  No language model is fused in, and no gradient is computed.
 
 The blank index is a keyword everywhere (default 0, the criterion's fallback, joint_ctc_criterion.py:76).
 """
@@ -180,6 +186,137 @@ def ctc_rescore(ops, head_w: torch.Tensor, enc_btd: torch.Tensor, enc_len: torch
     return ranked
 
 
+def ctc_topk(ops, head_w: torch.Tensor, enc_btd: torch.Tensor, enc_len: torch.Tensor, *, k: int = 8, blank: int = 0,
+             head_b: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The head's candidates of every frame of enc_btd [B, Te, D] (any batch stride), enc_len [B] valid rows ->
+    {"ids" [B, Te, k + 1] int32: slot 0 the blank, then the k other labels with the largest logits, descending, lower label first on
+     equal logits, -1 where the vocabulary has fewer; "lprob" [B, Te, k + 1] fp32 their log-probabilities (-inf at -1); "lse" [B, Te]}.
+    Past the length a frame holds ids -1 except the blank slot and lprob 0 at the blank, -inf elsewhere.  The logits are never
+    written (Ops.linear_topk)."""
+    ids, lprob, lse = ops.linear_topk(enc_btd, head_w, head_b, k=k, keep=blank)
+    Te = enc_btd.size(1)
+    enc_len = torch.as_tensor(enc_len, device=ids.device).to(torch.int64)
+    inside = (torch.arange(Te, device=ids.device).unsqueeze(0) < enc_len.unsqueeze(1)).unsqueeze(-1)
+    pad_ids = torch.full_like(ids, -1)
+    pad_ids[..., 0] = blank
+    pad_lp = torch.full_like(lprob, float("-inf"))
+    pad_lp[..., 0] = 0.0
+    return {"ids": torch.where(inside, ids, pad_ids), "lprob": torch.where(inside, lprob, pad_lp), "lse": lse}
+
+
+BEAM_MAX = 16
+
+
+def _lae(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """log(exp a + exp b), -inf where both are: max + log1p(exp(-|a - b|))"""
+    d = -(a - b).abs()
+    d = torch.where(torch.isnan(d), torch.full_like(d, float("-inf")), d)
+    return torch.maximum(a, b) + torch.log1p(torch.exp(d))
+
+
+def ctc_prefix_beam_init(B: int, beam: int, device, pad: int = 1):
+    """The state before the first frame: (strings [B, beam, 0] int64, lengths [B, beam] int64, p_b [B, beam], p_nb [B, beam] fp32) --
+    slot 0 the empty prefix at (0, -inf), the other slots empty (-inf, -inf).  Slots are kept in descending order of p_b (+) p_nb."""
+    ninf = float("-inf")
+    p_b = torch.full((B, beam), ninf, dtype=torch.float32, device=device)
+    p_b[:, 0] = 0.0
+    return (torch.full((B, beam, 0), pad, dtype=torch.int64, device=device), torch.zeros(B, beam, dtype=torch.int64, device=device),
+            p_b, torch.full((B, beam), ninf, dtype=torch.float32, device=device))
+
+
+def ctc_prefix_beam_advance(ids: torch.Tensor, lprob: torch.Tensor, enc_len: torch.Tensor, state, *, pad: int = 1):
+    """Time-synchronous CTC prefix beam search over candidate lists: ids [B, T, k + 1] (slot 0 the blank, -1 = no candidate), lprob
+    [B, T, k + 1] fp32 (ctc_topk's outputs, or any lists of that form), enc_len [B] frames to take of each row of the batch, state
+    (strings, lengths, p_b, p_nb) as ctc_prefix_beam_init makes it -> the state after the frames; strings grows to hold them.
+
+    Per frame and kept prefix l with last label e (pool index order: the beam's own entries first, then prefix-major, candidate-minor
+    extensions):
+      p_b'(l) = (p_b (+) p_nb) + lp[blank];  p_nb'(l) = p_nb + lp[e] if e is a candidate;
+      p_nb'(l + c) = p_b + lp[c] if c == e else (p_b (+) p_nb) + lp[c].
+    An extension that spells a prefix already in the beam is added to that entry's p_nb' (the strings are compared, label by label: a
+    beam entry has ONE parent string, so at most one extension reaches it and the sum has one order) and leaves the pool; the beam
+    best of the pool by p_b' (+) p_nb' survive, ties in pool index order (a stable sort).  A frame at or past enc_len[b] leaves row b's
+    state as it is.  Device tensor operations only, no read-back: this is the interface a recursion kernel would take over -- candidates
+    in, state in and out."""
+    strings, lengths, p_b, p_nb = state
+    B, T, kp = ids.shape
+    k, beam, dev = kp - 1, p_b.size(1), ids.device
+    ninf = float("-inf")
+    enc_len = torch.as_tensor(enc_len, device=dev).to(torch.int64)
+    if T:
+        strings = torch.cat([strings, torch.full((B, beam, T), pad, dtype=torch.int64, device=dev)], dim=2)
+    Lcap = strings.size(2)
+    pos_l = torch.arange(Lcap, device=dev)
+    ids = ids.to(torch.int64)
+    for t in range(T):
+        cid, lp = ids[:, t, 1:], lprob[:, t, 1:]                                    # [B, k] the non-blank candidates
+        lp_blank = lprob[:, t, :1]                                                   # [B, 1]
+        has = lengths > 0
+        last = torch.where(has, strings.gather(2, (lengths - 1).clamp(min=0).unsqueeze(-1)).squeeze(-1), torch.full_like(lengths, -2))
+        tot = _lae(p_b, p_nb)                                                        # [B, beam]
+        live = tot > ninf
+        same = (cid.unsqueeze(1) == last.unsqueeze(2)) & (cid.unsqueeze(1) >= 0)     # [B, beam, k]: candidate j repeats the last label
+        lp_e = torch.where(same, lp.unsqueeze(1).expand(B, beam, k), torch.full((), ninf, device=dev)).amax(2)
+        stay_b = tot + lp_blank
+        stay_nb = torch.where(lp_e > ninf, p_nb + lp_e, torch.full_like(p_nb, ninf))
+        ext = torch.where(same, p_b.unsqueeze(2), tot.unsqueeze(2)) + lp.unsqueeze(1)   # [B, beam, k]
+        ext = torch.where((cid.unsqueeze(1) >= 0) & live.unsqueeze(2), ext, torch.full_like(ext, ninf))
+        # entry i2 spells prefix i + one label: same first lengths[i] labels, one label longer
+        eq = (strings.unsqueeze(2) == strings.unsqueeze(1)) | (pos_l.view(1, 1, 1, Lcap) >= lengths.view(B, beam, 1, 1))
+        child = eq.all(3) & (lengths.unsqueeze(1) == lengths.unsqueeze(2) + 1) & live.unsqueeze(1) & live.unsqueeze(2)   # [B, i, i2]
+        nxt = strings.gather(2, lengths.clamp(max=Lcap - 1).unsqueeze(1).expand(B, beam, beam))    # [B, i2, i] = strings[i2][lengths[i]]
+        hit = child.unsqueeze(3) & (nxt.transpose(1, 2).unsqueeze(3) == cid.view(B, 1, 1, k))      # [B, i, i2, j]
+        gain = torch.where(hit, ext.unsqueeze(2), torch.full((), ninf, device=dev)).amax(dim=(1, 3))   # [B, i2]: at most one term
+        stay_nb = _lae(stay_nb, gain)
+        ext = torch.where(hit.any(2), torch.full_like(ext, ninf), ext)
+        pool_b = torch.cat([stay_b, torch.full((B, beam * k), ninf, device=dev)], dim=1)
+        pool_nb = torch.cat([stay_nb, ext.reshape(B, beam * k)], dim=1)
+        order = torch.sort(_lae(pool_b, pool_nb), dim=1, descending=True, stable=True).indices[:, :beam]     # [B, beam] pool indices
+        n_b, n_nb = pool_b.gather(1, order), pool_nb.gather(1, order)
+        grown = order >= beam
+        e_idx = (order - beam).clamp(min=0)
+        src = torch.where(grown, e_idx // max(k, 1), order)
+        tok = cid.gather(1, e_idx % max(k, 1)) if k else torch.zeros_like(order)
+        n_len = lengths.gather(1, src)
+        n_str = strings.gather(1, src.unsqueeze(-1).expand(B, beam, Lcap))
+        at = n_len.clamp(max=Lcap - 1).unsqueeze(-1)
+        n_str = n_str.scatter(2, at, torch.where(grown.unsqueeze(-1), tok.unsqueeze(-1), n_str.gather(2, at)))
+        n_len = n_len + grown.to(torch.int64)
+        dead = ~(_lae(n_b, n_nb) > ninf)
+        n_len = torch.where(dead, torch.zeros_like(n_len), n_len)
+        n_str = torch.where(dead.unsqueeze(-1), torch.full_like(n_str, pad), n_str)
+        on = (enc_len > t).unsqueeze(1)
+        strings = torch.where(on.unsqueeze(-1), n_str, strings)
+        lengths = torch.where(on, n_len, lengths)
+        p_b, p_nb = torch.where(on, n_b, p_b), torch.where(on, n_nb, p_nb)
+    return strings, lengths, p_b, p_nb
+
+
+def ctc_prefix_beam_search(ops, head_w: torch.Tensor, enc_btd: torch.Tensor, enc_len: torch.Tensor, *, beam: int = 8, candidates: int = 8,
+                           nbest: int = 1, blank: int = 0, pad: int = 1, head_b: Optional[torch.Tensor] = None, state=None,
+                           return_state: bool = False):
+    """Prefix beam search over the head's top `candidates` labels of every frame (ctc_topk + ctc_prefix_beam_advance) ->
+    {"tokens" [B, nbest, Lmax] int64 padded with `pad`, "n" [B, nbest], "score" [B, nbest] = log(p_b + p_nb), descending; a slot the
+    search has no prefix for holds n = 0 and score -inf} and, with return_state, "state" to pass to the next call: rows released chunk
+    by chunk (encoder.infer) give the bits one call over all rows gives.  1 <= nbest <= beam <= 16, 1 <= candidates <= 8.  The frame
+    loop runs on the device; the one read-back is Lmax."""
+    if not (1 <= nbest <= beam <= BEAM_MAX):
+        raise ValueError("ctc_prefix_beam_search: 1 <= nbest <= beam <= 16")
+    B = enc_btd.size(0)
+    cand = ctc_topk(ops, head_w, enc_btd, enc_len, k=candidates, blank=blank, head_b=head_b)
+    if state is None:
+        state = ctc_prefix_beam_init(B, beam, enc_btd.device, pad)
+    elif state[2].shape != (B, beam):
+        raise ValueError("ctc_prefix_beam_search: state belongs to another batch or beam")
+    strings, lengths, p_b, p_nb = ctc_prefix_beam_advance(cand["ids"], cand["lprob"], enc_len, state, pad=pad)
+    Lmax = int(lengths.max().item()) if B else 0
+    strings = strings[:, :, :Lmax].contiguous()
+    out = {"tokens": strings[:, :nbest], "n": lengths[:, :nbest], "score": _lae(p_b, p_nb)[:, :nbest]}
+    if return_state:
+        out["state"] = (strings, lengths, p_b, p_nb)
+    return out
+
+
 class CTCTranscriber:
     """transcribe_ctc for the models whose encoder can carry the head (SimulSTModel and its registered subclasses, CIFTransformerModel)."""
 
@@ -200,6 +337,44 @@ class CTCTranscriber:
         s = self.encoder.ctc_score(enc["encoder_out_btd"], enc["encoder_lengths"], tgt, n, blank=blank)
         nll, n = s["nll"].cpu(), n.cpu()
         return [{"nll": float(nll[b]), "score": -float(nll[b]) / max(int(n[b]), 1)} for b in range(nll.numel())]
+
+    def transcribe_ctc_nbest(self, src_tokens, src_lengths, *, beam: int = 8, nbest: int = 1, candidates: int = 8, blank: int = 0,
+                             rescore: bool = True) -> List[List[dict]]:
+        """Encoder forward + prefix beam search over the head.  Per utterance a list of up to nbest hypotheses {"tokens" (list),
+        "beam_score" (the search's log(p_b + p_nb): the likelihood mass of the alignments it kept)}, best first.  With rescore every
+        hypothesis gets "nll", its exact CTC negative log-likelihood (ctc_rescore: one gather per utterance for all its hypotheses),
+        the list is sorted by nll, and its first hypothesis gets "frames" / "frames_ms": the encoder row at which each token's run
+        starts on its best alignment (ctc_score(align=True)).  Raises ValueError when the model has no CTC head."""
+        enc = self.encoder.forward(src_tokens, src_lengths)
+        rows, lens = enc["encoder_out_btd"], enc["encoder_lengths"]
+        pad = self.encoder.cfg.padding_idx
+        r = self.encoder.ctc_prefix_beam_search(rows, lens, beam=beam, candidates=candidates, nbest=nbest, blank=blank, pad=pad)
+        tokens, n, score = r["tokens"].cpu(), r["n"].cpu(), r["score"].cpu()
+        hyps = []
+        for b in range(tokens.size(0)):
+            keep = [j for j in range(tokens.size(1)) if float(score[b, j]) > float("-inf")] or [0]
+            hyps.append([(tokens[b, j, :int(n[b, j])].tolist(), float(score[b, j])) for j in keep])
+        if not rescore:
+            return [[{"tokens": t, "beam_score": s} for t, s in h] for h in hyps]
+        ranked = ctc_rescore(self.encoder.ops, self.encoder.w.ctc, rows, lens, hyps, weight=1.0, blank=blank)
+        out = [[{"tokens": x["tokens"], "beam_score": x["score"], "nll": x["nll"]} for x in h] for h in ranked]
+        B = len(out)
+        Lb = max((len(h[0]["tokens"]) for h in out), default=0)
+        for h in out:
+            h[0]["frames"], h[0]["frames_ms"] = [], []
+        if B and Lb:
+            tgt = torch.full((B, max(Lb, 1)), pad, dtype=torch.int64)
+            for b, h in enumerate(out):
+                tgt[b, :len(h[0]["tokens"])] = torch.as_tensor(h[0]["tokens"], dtype=torch.int64)
+            tl = torch.tensor([len(h[0]["tokens"]) for h in out], dtype=torch.int64)
+            al = self.encoder.ctc_score(rows, lens, tgt, tl, blank=blank, align=True)["alignment"]
+            _, _, frames = ctc_collapse(al, lens, blank, pad)
+            frames = frames.cpu()
+            step_ms = self.encoder.conv_layer_stride() * SHIFT_MS
+            for b, h in enumerate(out):
+                fr = frames[b, :len(h[0]["tokens"])].tolist()
+                h[0]["frames"], h[0]["frames_ms"] = fr, [f * step_ms for f in fr]
+        return out
 
     def transcribe_ctc(self, src_tokens, src_lengths, *, blank: int = 0) -> List[dict]:
         """Encoder forward + the head's greedy path.  One {"tokens" (list), "score" (float: sum of the picked labels' log-probabilities

@@ -351,6 +351,24 @@ class S2TEmformerEncoder:
         from .ctc import ctc_greedy
         return ctc_greedy(self.ops, self.w.ctc, enc_btd, enc_len, blank=blank, pad=self.cfg.padding_idx)
 
+    def ctc_topk(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, *, k: int = 8, blank: int = 0):
+        """The head's per-frame candidates over encoder rows: {"ids", "lprob", "lse"} as ctc.ctc_topk describes them; the logits are not
+        written (Ops.linear_topk).  ValueError without a head."""
+        if self.w.ctc is None:
+            raise ValueError("ctc_topk: this model has no CTC head (ModelConfig.ctc_layer is off / no encoder.ctc_layer.weight)")
+        from .ctc import ctc_topk
+        return ctc_topk(self.ops, self.w.ctc, enc_btd, enc_len, k=k, blank=blank)
+
+    def ctc_prefix_beam_search(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, *, beam: int = 8, candidates: int = 8, nbest: int = 1,
+                               blank: int = 0, pad: Optional[int] = None, state=None, return_state: bool = False):
+        """Prefix beam search over the head's candidates: {"tokens", "n", "score"} (and "state") as ctc.ctc_prefix_beam_search describes
+        them; pad defaults to the model's padding index.  ValueError without a head."""
+        if self.w.ctc is None:
+            raise ValueError("ctc_prefix_beam_search: this model has no CTC head (ModelConfig.ctc_layer is off / no encoder.ctc_layer.weight)")
+        from .ctc import ctc_prefix_beam_search
+        return ctc_prefix_beam_search(self.ops, self.w.ctc, enc_btd, enc_len, beam=beam, candidates=candidates, nbest=nbest, blank=blank,
+                                      pad=self.cfg.padding_idx if pad is None else pad, state=state, return_state=return_state)
+
     def ctc_score(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, targets: torch.Tensor, target_lengths: torch.Tensor, *,
                   blank: int = 0, align: bool = False):
         """CTC negative log-likelihood of given transcripts under the head over encoder rows (forward()'s "encoder_out_btd" /

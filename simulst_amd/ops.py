@@ -125,6 +125,52 @@ class Ops:
             return (out[0], zmax[0], lse[0]) if Bb else (out.reshape(0), zmax.reshape(0), lse.reshape(0))
         return out, zmax, lse
 
+    def linear_topk(self, x, W, bias=None, *, k, keep=None, rows_per_batch=None, out=None, w_fragment_major=False):
+        """The best k columns of every row of z = x @ W[N, K]^T + bias without the logits (simulst_linear, SIMULST_EPI_ROW_TOPK):
+        -> (ids int32 [..., k'], lprob fp32 [..., k'], lse fp32 [...]), k' = k + (keep is not None), the leading dimensions those of x
+        without its last.  keep: a column that is always reported, in slot 0 (a CTC head's blank); the other k slots hold the columns
+        other than keep with the largest z, descending, on equal z the lower column first (rank 0 without keep is linear_pick's pick);
+        slots past the columns that exist hold -1 and lprob -inf.  lprob = z - lse.  1 <= k <= 8.
+
+        x, rows_per_batch and w_fragment_major as for linear_pick.  out: an int32 tensor (or view) [batches, rows_per_batch, k'] to take
+        the ids, last dimension contiguous, any other strides.  CPU tensors raise."""
+        _chk_contig(W)
+        _p(x), _p(W)                                           # (CPU tensors raise here, whatever the row count)
+        if x.dim() == 3:
+            if rows_per_batch is not None and rows_per_batch != x.shape[1]:
+                raise ValueError("linear_topk: rows_per_batch belongs to 2-D x")
+            Bb, rpb, K = x.shape
+            a_bs, a_rs = x.stride(0), x.stride(1)
+        elif x.dim() == 2:
+            rows, K = x.shape
+            rpb = max(rows, 1) if rows_per_batch is None else int(rows_per_batch)
+            if rpb <= 0 or rows % rpb:
+                raise ValueError("linear_topk: rows_per_batch must divide the rows")
+            Bb, a_rs = rows // rpb, x.stride(0)
+            a_bs = rpb * a_rs
+        else:
+            raise ValueError("linear_topk: x is [rows, K] or [B, T, K]")
+        if x.stride(-1) != 1 and x.numel():
+            raise ValueError("linear_topk: the rows of x must be contiguous")
+        N = W.shape[0]
+        if W.shape[1] != K or W.dtype != x.dtype:
+            raise ValueError("linear_topk: W is [N, K] in x's dtype")
+        k = int(k)
+        kp = k + (keep is not None)
+        if out is None:
+            out = torch.empty(Bb, rpb, kp, device=x.device, dtype=torch.int32)
+        elif out.dtype != torch.int32 or tuple(out.shape) != (Bb, rpb, kp) or (out.stride(2) != 1 and out.numel()):
+            raise ValueError("linear_topk: out is an int32 [batches, rows_per_batch, k'] tensor with a contiguous last dimension")
+        aux = torch.empty(Bb * rpb, kp + 1, device=x.device, dtype=torch.float32)
+        if Bb * rpb:                                           # (no rows: nothing to launch, and nothing to point at)
+            self.linear_raw(x, W, bias, out, M_batches=Bb, rows_per_batch=rpb, N=N, K=K, a_bs=a_bs, a_rs=a_rs, c_bs=out.stride(0),
+                            c_rs=out.stride(1), epilogue=_lib.EPI_ROW_TOPK, aux=aux, aux_rows=k, n_main=-1 if keep is None else int(keep),
+                            w_fragment_major=w_fragment_major)
+        lprob, lse = aux[:, :kp].view(Bb, rpb, kp), aux[:, kp].view(Bb, rpb)
+        if x.dim() == 2 and rows_per_batch is None:
+            return (out[0], lprob[0], lse[0]) if Bb else (out.reshape(0, kp), lprob.reshape(0, kp), lse.reshape(0))
+        return out, lprob, lse
+
     def linear_gather(self, x, W, bias, labels, out=None):
         """Log-probabilities of given labels under z = x @ W[N, K]^T + bias without the logits (simulst_linear, SIMULST_EPI_ROW_GATHER):
         out[b, t, j] = z[b, t, labels[b, j]] - logsumexp_n z[b, t, n], fp32.
