@@ -58,7 +58,8 @@ def fbank(ops: Ops, tables: FbankTables, wave: torch.Tensor, out_dtype=torch.flo
     out = torch.empty(B, n_frames, tables.n_mel, device=wave.device, dtype=out_dtype)
     if B == 0 or n_frames == 0:
         return out
-    ops.h.check(ops.lib.simulst_fbank(ops.h.ptr, _p(wave), wave.stride(0), _p(tables.window), _p(tables.tw_cos),
+    row_stride = wave.stride(0) if B > 1 else n      # a single row's stride(0) is arbitrary (0 after a broadcast or numpy's [None])
+    ops.h.check(ops.lib.simulst_fbank(ops.h.ptr, _p(wave), row_stride, _p(tables.window), _p(tables.tw_cos),
                                       _p(tables.tw_sin), _p(tables.mel_lo), _p(tables.mel_w), _p(out), B, n_frames,
                                       tables.n_mel, preemphasis,
                                       _lib.F32 if out_dtype == torch.float32 else _lib.BF16), "simulst_fbank")
