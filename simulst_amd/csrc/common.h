@@ -183,6 +183,11 @@ static inline int sl_raise_lds(simulst_handle* h, sl_lds_slot slot, const sl_lds
   return h->lds_raised[slot] ? SIMULST_OK : sl_raise_lds_limits(h, slot, list, N, who);
 }
 
+// The library's own scratch h->ws grown to at least `need` bytes (at least floor_bytes when it has to be allocated anew).  No
+// allocation may happen inside a graph capture: there a scratch that is too small is SIMULST_E_ARG.  On failure h->err names the
+// caller and the positive hipError_t comes back.
+int sl_workspace(simulst_handle* h, size_t need, size_t floor_bytes, const char* who);      // handle.cpp
+
 // ---- fixed pre-decision pooling (modules/fixed_pre_decision.py:23-52,97-131) ------------------------------------
 // The C ABI carries the pooling type in the SIGN of `ratio`: ratio > 0 is --fixed-pre-decision-type average,
 // ratio < 0 is 'last' with ratio |ratio|.  pooled_count: number of pooled positions of a source of len frames --

@@ -589,15 +589,7 @@ int launch_policy_cross(simulst_handle* h, const void* qm, const void* qs, const
     // the row's length is live)
     const int nblk = (S_cap + KB_KEYS - 1) / KB_KEYS;
     const size_t need = (size_t)B * H * nblk * (d + 2) * sizeof(float);
-    if (h->ws_bytes < need) {
-      if (h->capturing) { h->err = "simulst_policy_cross_attention: scratch too small while capturing a graph"; return SIMULST_E_ARG; }
-      if (h->ws) (void)hipFree(h->ws);
-      h->ws = nullptr; h->ws_bytes = 0;
-      const size_t want = need < ((size_t)4 << 20) ? ((size_t)4 << 20) : need;
-      hipError_t e = hipMalloc(&h->ws, want);
-      if (e != hipSuccess) { h->err = "simulst_policy_cross_attention: scratch allocation failed"; return (int)e; }
-      h->ws_bytes = want;
-    }
+    if (int rc = sl_workspace(h, need, (size_t)4 << 20, "simulst_policy_cross_attention")) return rc;
     float* part = (float*)h->ws;
 #define KB_LAUNCH(NP)                                                                                                  \
     hipLaunchKernelGGL((waitk_cross_attn_block_kernel<T, NP>), dim3(H, B, nblk), dim3(256), 0, h->stream, (const T*)qs,     \

@@ -1,13 +1,13 @@
 // simulst_linear, SIMULST_EPI_ROW_PICK: per logical row r of z = A . W^T + bias, the lowest column at which z is largest (int32 at C's
 // row address) and (max z, logsumexp z) (fp32 pairs at aux[r]) -- the best path of a CTC head and its log-probabilities.  The [M][N]
-// logits stay in registers: a row panel of A is staged once in LDS, W streams past it in 16-column tiles, every lane keeps a running
-// (max, index, sum of exp(z - max)) for the rows and the column stripe it sees, and one fold per row closes the launch.  Comparison is
-// on the fp32 accumulators (+ bias); on equal values the lower column wins at every join, so the pick does not depend on the order in
-// which tiles, lanes or waves meet.
+// logits stay in registers: a row panel of A is staged once in LDS, W streams past it in 16-column tiles (the column sweep of
+// row_sweep.h), every lane keeps a running (max, index, sum of exp(z - max)) for the rows and the column stripe it sees, and one fold
+// per row closes the launch.  Comparison is on the fp32 accumulators (+ bias); on equal values the lower column wins at every join,
+// so the pick does not depend on the order in which tiles, lanes or waves meet.
 //
 //   bf16, K % 32 == 0, panel within 60 KB of LDS: v_mfma_f32_16x16x32_bf16, the fragment layout of gemv_mfma.h and the (max, sum)
-//     bookkeeping of transducer.hip's joiner_lattice_kernel.  W row-major (a lane's 16 bytes of a fragment are 16 bytes of a row:
-//     every 64-byte segment a wave touches is used whole) or fragment-major.
+//     bookkeeping of row_sweep.h.  W row-major (a lane's 16 bytes of a fragment are 16 bytes of a row: every 64-byte segment a wave
+//     touches is used whole) or fragment-major.
 //   everything else (fp32, other K): a thread per column over 4 rows on the VALU, fmaf chains in four partial sums.  Correctness only.
 //
 // Neither output has room for per-part partials: tall problems give one workgroup the whole width; where the row panels alone would
@@ -16,13 +16,13 @@
 //
 // SIMULST_EPI_ROW_GATHER runs the same kernels (GATHER = true): the same sweep, without the index, gives the row's logsumexp, and a
 // gather phase over the SAME staged rows computes z at the caller's labels of the row's batch -- C[row][j] = z[row][lab[b][j]] - lse,
-// the log-probabilities a CTC recursion over a given transcript reads.  The gathered z runs the sweep's instruction sequence (same k
-// order, same accumulator start), so it is the value the sweep saw for that column.  Labels outside [0, N) are clamped into it.
+// the log-probabilities a CTC recursion over a given transcript reads.  The gathered z is sweep_one_tile's, one accumulator of the
+// sweep, so it is the value the sweep saw for that column.  Labels outside [0, N) are clamped into it.
 //
-// SIMULST_EPI_ROW_TOPK has kernels of its own further down (row_topk_*): the same sweep and the same plan, with per-row candidate
-// lists in place of the single running index.
+// SIMULST_EPI_ROW_TOPK has kernels of its own further down (row_topk_*): the same sweep (sweep_columns) and the same plan, with
+// per-row candidate lists in place of the single running index (tests/test_hip_row_sweep.py: the three agree bit for bit).
 #include "gemm_plan.h"
-#include "gemv_mfma.h"
+#include "row_sweep.h"
 
 namespace {
 
@@ -51,13 +51,6 @@ __device__ __forceinline__ void pick_store(const LinArgs& p, int32_t* __restrict
   *reinterpret_cast<float2*>(aux + 2 * (long)row) = make_float2(m, m + logf(s));
 }
 
-// GATHER: the running state without the index
-__device__ __forceinline__ void lse_pair(float& m, float& s, float x0, float x1) {
-  const float mx = fmaxf(m, fmaxf(x0, x1));
-  s = s * __expf(m - mx) + __expf(x0 - mx) + __expf(x1 - mx);
-  m = mx;
-}
-
 // label j of batch b, clamped into [0, N); j past the list reads W's row 0
 __device__ __forceinline__ int gather_label(const LinArgs& p, const int32_t* __restrict__ lab, int b, int j) {
   return j < p.aux_rows ? min(max(lab[(long)b * p.aux_bs + j], 0), p.N - 1) : 0;
@@ -81,16 +74,7 @@ __global__ __launch_bounds__(256) void row_pick_mfma_kernel(const bf16* __restri
   const int m0 = blockIdx.x * PICK_M;
   const int n_rt = min(R, (p.M - m0 + 15) >> 4);           // row tiles with a row in them
 
-  const int groups = p.K / G;
-  for (int i = tid; i < 16 * n_rt * groups; i += 256) {
-    const int r = i / groups, c = (i - r * groups) * G, row = m0 + r;
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (row < p.M) {
-      const int b = row / p.rpb, ii = row - b * p.rpb;
-      v = ld16(A + (long)b * p.a_bs + (long)ii * p.a_rs + c);
-    }
-    *reinterpret_cast<uint4*>(zs + (long)r * ldz + c) = v;
-  }
+  sweep_stage_rows<bf16>(zs, ldz, A, p, m0, n_rt, tid);
   __syncthreads();
 
   const int n_vt = (p.N + 15) >> 4, nks = p.K / KS;
@@ -104,6 +88,7 @@ __global__ __launch_bounds__(256) void row_pick_mfma_kernel(const bf16* __restri
 #pragma unroll
     for (int e = 0; e < 4; ++e) { rm[r][e] = LAT_NEG; rs[r][e] = 0.f; ri[r][e] = PICK_NONE; }
 
+  // sweep_columns (row_sweep.h) as a loop of its own: through the helper tools/ctc_pick_bench.py's 64 x 250 rows took 0.142, not 0.139 ms
   for (int vt = vt0 + 2 * wave; vt < vt1; vt += 8) {
     const bool two = vt + 1 < vt1;
     const int c0 = vt * 16 + col, c1 = c0 + 16;
@@ -146,26 +131,23 @@ __global__ __launch_bounds__(256) void row_pick_mfma_kernel(const bf16* __restri
       }
   }
   // fold the 16 columns of a lane group, then the 4 waves
+  if constexpr (GATHER) {
+    fold_lane_group<R>(rm, rs, red_m[wave], red_s[wave], 0);
+  } else {                                                   // fold_lane_group with the index
 #pragma unroll
-  for (int r = 0; r < R; ++r)
+    for (int r = 0; r < R; ++r)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
+      for (int e = 0; e < 4; ++e) {
 #pragma unroll
-      for (int o = 1; o < 16; o <<= 1) {
-        const float om = __shfl_xor(rm[r][e], o, 64), os = __shfl_xor(rs[r][e], o, 64);
-        if constexpr (GATHER) {
-          lse_join(rm[r][e], rs[r][e], om, os);
-        } else {
+        for (int o = 1; o < 16; o <<= 1) {
+          const float om = __shfl_xor(rm[r][e], o, 64), os = __shfl_xor(rs[r][e], o, 64);
           const int oi = __shfl_xor(ri[r][e], o, 64);
           pick_join(rm[r][e], ri[r][e], rs[r][e], om, oi, os);
         }
+        const int row = 16 * r + 4 * lg + e;
+        if (col == 0) { red_m[wave][row] = rm[r][e]; red_s[wave][row] = rs[r][e]; red_i[wave][row] = ri[r][e]; }
       }
-      const int row = 16 * r + 4 * lg + e;
-      if (col == 0) {
-        red_m[wave][row] = rm[r][e]; red_s[wave][row] = rs[r][e];
-        if constexpr (!GATHER) red_i[wave][row] = ri[r][e];
-      }
-    }
+  }
   __syncthreads();
   if constexpr (!GATHER) {
     int32_t* C = static_cast<int32_t*>(Cv);
@@ -183,9 +165,8 @@ __global__ __launch_bounds__(256) void row_pick_mfma_kernel(const bf16* __restri
     const int32_t* lab = static_cast<const int32_t*>(auxv);
     float my_lse = 0.f;
     if (tid < PICK_M && m0 + tid < p.M) {
-      float m = red_m[0][tid], s = red_s[0][tid];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) lse_join(m, s, red_m[w][tid], red_s[w][tid]);
+      float m, s;
+      join_waves_lse(red_m, red_s, tid, m, s);
       if (part) part[(long)(m0 + tid) * gridDim.y + blockIdx.y] = make_float4(m, s, 0.f, 0.f);
       else my_lse = m + logf(s);
     }
@@ -202,15 +183,7 @@ __global__ __launch_bounds__(256) void row_pick_mfma_kernel(const bf16* __restri
       const int b_lo = row_lo / p.rpb, b_hi = row_hi / p.rpb;
       for (int bb = b_lo; bb <= b_hi; ++bb) {
         const int lb = gather_label(p, lab, bb, j);
-        const bf16* w0 = W + (long)lb * p.K + lg * G;
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-        uint4 wa = ld16(w0);
-        for (int ks = 0; ks < nks; ++ks) {
-          const uint4 ca = wa;
-          if (ks + 1 < nks) wa = ld16(w0 + (ks + 1) * KS);
-          const uint4 a = *reinterpret_cast<const uint4*>(zs + (long)(16 * r + col) * ldz + ks * KS + lg * G);
-          acc = lat_mma<bf16>(a, ca, acc);
-        }
+        const f32x4 acc = sweep_one_tile<bf16>(zs, ldz, r, W + (long)lb * p.K + lg * G, p.K);
         const float bv = bias ? bias[lb] : 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -255,12 +228,14 @@ __global__ void row_gather_fold_kernel(const float4* __restrict__ part, int n_sp
 }
 
 // ---- VALU: PICK_VM rows per workgroup, thread t takes columns t, t + 256, ... -------------------------------------------------------------
-template <typename T> __device__ __forceinline__ void load_g(const T* p, float (&o)[gemv::MF<T>::G]);
-template <> __device__ __forceinline__ void load_g<float>(const float* p, float (&o)[4]) { load4(p, o); }
-template <> __device__ __forceinline__ void load_g<bf16>(const bf16* p, float (&o)[8]) {
-  float t[4];
-  load4(p, t); o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3];
-  load4(p + 4, t); o[4] = t[0]; o[5] = t[1]; o[6] = t[2]; o[7] = t[3];
+// the PICK_VM rows of a workgroup: rows past the end repeat the last one and are not stored
+template <typename T> __device__ __forceinline__ void valu_rows(const T* __restrict__ A, const LinArgs& p, int m0, const T* (&arow)[PICK_VM]) {
+#pragma unroll
+  for (int r = 0; r < PICK_VM; ++r) {
+    const int row = min(m0 + r, p.M - 1);
+    const int b = row / p.rpb, ii = row - b * p.rpb;
+    arow[r] = A + (long)b * p.a_bs + (long)ii * p.a_rs;
+  }
 }
 
 // z of PICK_VM rows at one column: the fmaf chains of the sweep and of the gather phase
@@ -297,12 +272,7 @@ __global__ __launch_bounds__(256) void row_pick_valu_kernel(const T* __restrict_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m0 = blockIdx.x * PICK_VM;
   const T* arow[PICK_VM];
-#pragma unroll
-  for (int r = 0; r < PICK_VM; ++r) {
-    const int row = min(m0 + r, p.M - 1);                   // rows past the end repeat the last one and are not stored
-    const int b = row / p.rpb, ii = row - b * p.rpb;
-    arow[r] = A + (long)b * p.a_bs + (long)ii * p.a_rs;
-  }
+  valu_rows<T>(A, p, m0, arow);
   float rm[PICK_VM], rs[PICK_VM];
   int ri[PICK_VM];
 #pragma unroll
@@ -438,7 +408,7 @@ template <bool W_FM>
 __global__ __launch_bounds__(256, 2) void row_topk_mfma_kernel(const bf16* __restrict__ A, const bf16* __restrict__ W,
                                                             const float* __restrict__ bias, int32_t* __restrict__ C,
                                                             float* __restrict__ aux, float* __restrict__ part, LinArgs p) {
-  constexpr int KS = gemv::MF<bf16>::KS, G = gemv::MF<bf16>::G, R = PICK_M / 16;
+  constexpr int G = gemv::MF<bf16>::G, R = PICK_M / 16;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   bf16* zs = reinterpret_cast<bf16*>(smem_raw);
   __shared__ float red_m[4][PICK_M], red_s[4][PICK_M], zkeep[PICK_M];
@@ -454,58 +424,22 @@ __global__ __launch_bounds__(256, 2) void row_topk_mfma_kernel(const bf16* __res
 
   cnt[wave][lane] = 0;
   if (tid < PICK_M) { thr[tid] = 0; zkeep[tid] = -INFINITY; }
-  const int groups = p.K / G;
-  for (int i = tid; i < 16 * n_rt * groups; i += 256) {
-    const int r = i / groups, c = (i - r * groups) * G, row = m0 + r;
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (row < p.M) {
-      const int b = row / p.rpb, ii = row - b * p.rpb;
-      v = ld16(A + (long)b * p.a_bs + (long)ii * p.a_rs + c);
-    }
-    *reinterpret_cast<uint4*>(zs + (long)r * ldz + c) = v;
-  }
+  sweep_stage_rows<bf16>(zs, ldz, A, p, m0, n_rt, tid);
   __syncthreads();
 
-  const int n_vt = (p.N + 15) >> 4, nks = p.K / KS;
+  const int n_vt = (p.N + 15) >> 4;
   const int per = (n_vt + (int)gridDim.y - 1) / (int)gridDim.y;
   const int vt0 = blockIdx.y * per, vt1 = min(vt0 + per, n_vt);
-  const int col = lane & 15, lg = lane >> 4;
+  const int lg = lane >> 4;
   float rm[R][4], rs[R][4];
 #pragma unroll
   for (int r = 0; r < R; ++r)
 #pragma unroll
     for (int e = 0; e < 4; ++e) { rm[r][e] = LAT_NEG; rs[r][e] = 0.f; }
 
-  for (int vt = vt0 + 2 * wave; vt < vt1; vt += 8) {
-    const bool two = vt + 1 < vt1;
-    const int c0 = vt * 16 + col, c1 = c0 + 16;
-    const bool ok0 = c0 < p.N, ok1 = two && c1 < p.N;
-    const bf16 *w0, *w1;
-    long step;
-    if constexpr (W_FM) {
-      w0 = W + ((long)vt * nks * 64 + lane) * G;
-      w1 = two ? w0 + (long)nks * 64 * G : w0;
-      step = 64 * G;
-    } else {
-      w0 = W + (long)(ok0 ? c0 : p.N - 1) * p.K + lg * G;
-      w1 = W + (long)(ok1 ? c1 : p.N - 1) * p.K + lg * G;
-      step = KS;
-    }
-    f32x4 acc0[R], acc1[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) { acc0[r] = f32x4{0.f, 0.f, 0.f, 0.f}; acc1[r] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    uint4 wa = ld16(w0), wb = ld16(w1);
-    for (int ks = 0; ks < nks; ++ks) {
-      const uint4 ca = wa, cb = wb;
-      if (ks + 1 < nks) { wa = ld16(w0 + (ks + 1) * step); wb = ld16(w1 + (ks + 1) * step); }
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        if (r >= n_rt) continue;                            // uniform over the workgroup
-        const uint4 a = *reinterpret_cast<const uint4*>(zs + (long)(16 * r + col) * ldz + ks * KS + lg * G);
-        acc0[r] = lat_mma<bf16>(a, ca, acc0[r]);
-        acc1[r] = lat_mma<bf16>(a, cb, acc1[r]);
-      }
-    }
+  sweep_columns<bf16, R, W_FM>(zs, ldz, n_rt, W, p.K, p.N, vt0, vt1, wave, [&](int c0, bool ok0, bool ok1, const f32x4(&acc0)[R],
+                                                                               const f32x4(&acc1)[R]) {
+    const int c1 = c0 + 16;
     const float b0 = (bias && ok0) ? bias[c0] : 0.f, b1 = (bias && ok1) ? bias[c1] : 0.f;
     const bool in0 = ok0 && c0 != keep, in1 = ok1 && c1 != keep;
     unsigned pend = 0;                                      // bit 2 (4 r + e) + j: column cj of row 16 r + 4 lg + e waits for a slot
@@ -545,22 +479,10 @@ __global__ __launch_bounds__(256, 2) void row_topk_mfma_kernel(const bf16* __res
       __threadfence_block();
       if (__any(fail != 0)) topk_compact(cand_w, cnt[wave], thr, k, false, lane);
     }
-  }
+  });
   __threadfence_block();
   topk_compact(cand_w, cnt[wave], thr, k, true, lane);
-  // fold the 16 columns of a lane group; the 4 waves meet below
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) {
-        const float om = __shfl_xor(rm[r][e], o, 64), os = __shfl_xor(rs[r][e], o, 64);
-        lse_join(rm[r][e], rs[r][e], om, os);
-      }
-      const int lr = 16 * r + 4 * lg + e;
-      if (col == 0) { red_m[wave][lr] = rm[r][e]; red_s[wave][lr] = rs[r][e]; }
-    }
+  fold_lane_group<R>(rm, rs, red_m[wave], red_s[wave], 0);      // the 16 columns of a lane group; the 4 waves meet below
   __syncthreads();
   // 32 lanes a row: lane j holds entry j & 7 of wave j >> 3 and counts the survivors that beat it
   const int half = lane >> 5, j = lane & 31, jw = j >> 3, ji = j & 7;
@@ -580,9 +502,8 @@ __global__ __launch_bounds__(256, 2) void row_topk_mfma_kernel(const bf16* __res
       }
     }
     total = min(total, k);
-    float m = red_m[0][lr], s = red_s[0][lr];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) lse_join(m, s, red_m[w][lr], red_s[w][lr]);
+    float m, s;
+    join_waves_lse(red_m, red_s, lr, m, s);
     if (part) {
       float* rec = part + ((long)row * gridDim.y + blockIdx.y) * TOPK_REC;
       topk_key* keys = reinterpret_cast<topk_key*>(rec + 4);
@@ -639,12 +560,7 @@ __global__ __launch_bounds__(256) void row_topk_valu_kernel(const T* __restrict_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m0 = blockIdx.x * PICK_VM;
   const T* arow[PICK_VM];
-#pragma unroll
-  for (int r = 0; r < PICK_VM; ++r) {
-    const int row = min(m0 + r, p.M - 1);                   // rows past the end repeat the last one and are not stored
-    const int b = row / p.rpb, ii = row - b * p.rpb;
-    arow[r] = A + (long)b * p.a_bs + (long)ii * p.a_rs;
-  }
+  valu_rows<T>(A, p, m0, arow);
   if (tid < PICK_VM) zkeep[tid] = -INFINITY;
   __syncthreads();
   topk_key prev[PICK_VM];
@@ -736,14 +652,7 @@ int sl_launch_row_pick(simulst_handle* h, const sl_linear_plan& pl, const sl_lin
   if (pl.splits > 1) {                                       // the library's own scratch, as simulst_linear's split-K partials
     const bool topk = pl.epi == SIMULST_EPI_ROW_TOPK;
     const size_t need = (size_t)pl.splits * p.M * (topk ? TOPK_REC * sizeof(float) : sizeof(float4));
-    if (h->ws_bytes < need) {
-      if (h->capturing) { h->err = "simulst_linear: scratch too small while capturing a graph"; return SIMULST_E_ARG; }
-      if (h->ws) (void)hipFree(h->ws);
-      h->ws = nullptr; h->ws_bytes = 0;
-      hipError_t e = hipMalloc(&h->ws, need);
-      if (e != hipSuccess) { h->err = "simulst_linear: scratch allocation failed"; return (int)e; }
-      h->ws_bytes = need;
-    }
+    if (int rc = sl_workspace(h, need, 0, "simulst_linear")) return rc;
     part = (float4*)h->ws;
   }
   if (pl.epi == SIMULST_EPI_ROW_TOPK) return sl_launch_row_topk(h, pl, o, p, (float*)part);

@@ -281,14 +281,7 @@ int launch_all(simulst_handle* h, const sl_linear_plan& pl, const sl_linear_ops&
   float* partial = nullptr;
   if (splits > 1) {
     const size_t need = (size_t)splits * p.M * p.N * sizeof(float);
-    if (h->ws_bytes < need) {
-      if (h->capturing) { h->err = "simulst_linear: scratch too small while capturing a graph"; return SIMULST_E_ARG; }
-      if (h->ws) (void)hipFree(h->ws);
-      h->ws = nullptr; h->ws_bytes = 0;
-      hipError_t e = hipMalloc(&h->ws, need);
-      if (e != hipSuccess) { h->err = "simulst_linear: scratch allocation failed"; return (int)e; }
-      h->ws_bytes = need;
-    }
+    if (int rc = sl_workspace(h, need, 0, "simulst_linear")) return rc;
     partial = (float*)h->ws;
   }
   const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);

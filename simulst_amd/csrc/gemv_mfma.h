@@ -61,27 +61,3 @@ __device__ __forceinline__ void mac(f32x4& acc, const Frag<T, NS>& f, const T* x
 }
 
 }  // namespace gemv
-
-// ---- pieces of the kernels that reduce a vocabulary row on chip (transducer.hip joiner_lattice_kernel, gemm_pick.hip) ----------------
-// one 16 x 16 tile step: a = 16 bytes of an activation row (lane's row lane % 16, k-group lane / 16), w = the weight fragment
-template <typename T> __device__ __forceinline__ f32x4 lat_mma(const uint4& a, const uint4& w, f32x4 acc) {
-  if constexpr (std::is_same<T, float>::value) {
-    const float* af = reinterpret_cast<const float*>(&a);
-    const float* wf = reinterpret_cast<const float*>(&w);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[e], wf[e], acc, 0, 0, 0);
-    return acc;
-  } else {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(&a), *reinterpret_cast<const bf16x8_t*>(&w),
-                                                   acc, 0, 0, 0);
-  }
-}
-
-constexpr float LAT_NEG = -1e30f;         // "no column yet": finite, so that max - max never makes a NaN
-
-// (m, s) <- (m, s) joined with (om, os): s counts exp(x - m)
-__device__ __forceinline__ void lse_join(float& m, float& s, float om, float os) {
-  const float mx = fmaxf(m, om);
-  s = s * __expf(m - mx) + os * __expf(om - mx);
-  m = mx;
-}

@@ -152,6 +152,18 @@ int sl_raise_lds_limits(simulst_handle* h, sl_lds_slot slot, const sl_lds_limit*
   return SIMULST_OK;
 }
 
+int sl_workspace(simulst_handle* h, size_t need, size_t floor_bytes, const char* who) {
+  if (h->ws_bytes >= need) return SIMULST_OK;
+  if (h->capturing) { h->err = std::string(who) + ": scratch too small while capturing a graph"; return SIMULST_E_ARG; }
+  if (h->ws) (void)hipFree(h->ws);
+  h->ws = nullptr; h->ws_bytes = 0;
+  const size_t want = need < floor_bytes ? floor_bytes : need;
+  const hipError_t e = hipMalloc(&h->ws, want);
+  if (e != hipSuccess) { h->err = std::string(who) + ": scratch allocation failed"; return (int)e; }
+  h->ws_bytes = want;
+  return SIMULST_OK;
+}
+
 extern "C" int simulst_set_stream(simulst_handle* h, void* hip_stream) {
   if (!h) return SIMULST_E_NULL;
   h->stream = (hipStream_t)hip_stream;

@@ -28,7 +28,7 @@
 // (tanh of P + g, rounded to the model dtype) into LDS, the B operand is W_out in fragment-major order (gemv_mfma.h), one 16-byte
 // contiguous load per lane and k-step.  No workgroup waits for another one: every part of a vocabulary split writes its own
 // (max, index) pair and the emit kernel folds them.
-#include "gemv_mfma.h"
+#include "row_sweep.h"
 
 namespace {
 
@@ -182,15 +182,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void joiner_scan_kernel(
       for (int r = 0; r < R; ++r) {
         if (tile_lo[r] >= tile_hi[r]) continue;             // uniform over the workgroup
         const uint4 a = *reinterpret_cast<const uint4*>(zs + (long)(16 * r + col) * ldz + ks * KS + lg * G);
-        if constexpr (std::is_same<T, float>::value) {
-          const float* af = reinterpret_cast<const float*>(&a);
-          const float* wf = reinterpret_cast<const float*>(&w);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[e], wf[e], acc[r], 0, 0, 0);
-        } else {
-          acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(&a),
-                                                           *reinterpret_cast<const bf16x8_t*>(&w), acc[r], 0, 0, 0);
-        }
+        acc[r] = lat_mma<T>(a, w, acc[r]);
       }
     }
     // lane holds logits[row 4 lg + e][column v] of every row tile
@@ -311,7 +303,8 @@ template <typename T> struct LatCfg;
 template <> struct LatCfg<bf16> { static constexpr int R = 8, THREADS = 512; };
 template <> struct LatCfg<float> { static constexpr int R = 4, THREADS = 256; };
 
-// (lat_mma, lse_join and LAT_NEG live in gemv_mfma.h: the row-pick epilogue of simulst_linear shares them)
+// (everything but the pass loop is row_sweep.h's; the loop is a copy of its sweep_columns over the RW row tiles of a row group: through
+//  the helper this kernel measured 0.82 ms against 0.76 / 0.77 ms on the shape of tools/transducer_score_bench.py)
 
 // grid (ceil(B * S * u_tiles / R), n_split).  part[cell][p] = (max, sum, blank logit, label logit) of vocabulary part p.
 template <typename T>
@@ -415,26 +408,10 @@ __global__ __launch_bounds__(LatCfg<T>::THREADS, LatCfg<T>::THREADS / 128) void 
 #pragma unroll
     for (int r = 0; r < RW; ++r)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float x0 = ok0 ? acc0[r][e] : -INFINITY, x1 = ok1 ? acc1[r][e] : -INFINITY;
-        const float mx = fmaxf(rm[r][e], fmaxf(x0, x1));
-        rs[r][e] = rs[r][e] * __expf(rm[r][e] - mx) + __expf(x0 - mx) + __expf(x1 - mx);
-        rm[r][e] = mx;
-      }
+      for (int e = 0; e < 4; ++e) lse_pair(rm[r][e], rs[r][e], ok0 ? acc0[r][e] : -INFINITY, ok1 ? acc1[r][e] : -INFINITY);
   }
-  // fold the 16 columns of a lane group, then the 4 waves of the row group
-#pragma unroll
-  for (int r = 0; r < RW; ++r)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) {
-        const float om = __shfl_xor(rm[r][e], o, 64), os = __shfl_xor(rs[r][e], o, 64);
-        lse_join(rm[r][e], rs[r][e], om, os);
-      }
-      const int row = 16 * (rbase + r) + 4 * lg + e;
-      if (col == 0) { red_m[wave][row] = rm[r][e]; red_s[wave][row] = rs[r][e]; }
-    }
+  // fold the 16 columns of a lane group, then (below) the 4 waves of the row group
+  fold_lane_group<RW>(rm, rs, red_m[wave], red_s[wave], rbase);
   // the blank and label logits of every row: thread (row, which) takes one dot product over D if this part holds the column
   for (int i = tid; i < 2 * ROWS; i += THREADS) {
     const int r = i >> 1, which = i & 1;
@@ -447,16 +424,8 @@ __global__ __launch_bounds__(LatCfg<T>::THREADS, LatCfg<T>::THREADS / 128) void 
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float wv[G], zv[G];
-        if constexpr (std::is_same<T, float>::value) {
-          load4(wrow + ((long)ks * 64 + q * 16) * G, wv);
-          load4(zrow + ks * KS + q * G, zv);
-        } else {
-          float t4[4];
-          load4(wrow + ((long)ks * 64 + q * 16) * G, t4); wv[0] = t4[0]; wv[1] = t4[1]; wv[2] = t4[2]; wv[3] = t4[3];
-          load4(wrow + ((long)ks * 64 + q * 16) * G + 4, t4); wv[4] = t4[0]; wv[5] = t4[1]; wv[6] = t4[2]; wv[7] = t4[3];
-          load4(zrow + ks * KS + q * G, t4); zv[0] = t4[0]; zv[1] = t4[1]; zv[2] = t4[2]; zv[3] = t4[3];
-          load4(zrow + ks * KS + q * G + 4, t4); zv[4] = t4[0]; zv[5] = t4[1]; zv[6] = t4[2]; zv[7] = t4[3];
-        }
+        load_g<T>(wrow + ((long)ks * 64 + q * 16) * G, wv);
+        load_g<T>(zrow + ks * KS + q * G, zv);
 #pragma unroll
         for (int e = 0; e < G; ++e) acc = fmaf(zv[e], wv[e], acc);
       }
@@ -466,9 +435,8 @@ __global__ __launch_bounds__(LatCfg<T>::THREADS, LatCfg<T>::THREADS / 128) void 
   if (tid < ROWS) {
     const int rt = tid >> 4, i = tid & 15;
     if (i < tile_n[rt]) {
-      float m = red_m[0][tid], s = red_s[0][tid];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) lse_join(m, s, red_m[w][tid], red_s[w][tid]);
+      float m, s;
+      join_waves_lse(red_m, red_s, tid, m, s);
       const long cell = ((long)tile_b[rt] * S + tile_s[rt]) * U1 + tile_u0[rt] + i;
       *reinterpret_cast<float4*>(part + (cell * n_split + blockIdx.y) * 4) = make_float4(m, s, cap[tid][0], cap[tid][1]);
     }

@@ -37,6 +37,30 @@ def _chk_contig(*ts):
             raise ValueError("simulst_amd: tensor must be contiguous")
 
 
+def _row_view(who, x, W, rows_per_batch):
+    """x of linear_pick / linear_topk, [rows, K] (with rows_per_batch) or a [B, T, K] view, as simulst_linear addresses it:
+    -> (batches, rows per batch, K, batch stride, row stride)"""
+    if x.dim() == 3:
+        if rows_per_batch is not None and rows_per_batch != x.shape[1]:
+            raise ValueError(f"{who}: rows_per_batch belongs to 2-D x")
+        Bb, rpb, K = x.shape
+        a_bs, a_rs = x.stride(0), x.stride(1)
+    elif x.dim() == 2:
+        rows, K = x.shape
+        rpb = max(rows, 1) if rows_per_batch is None else int(rows_per_batch)
+        if rpb <= 0 or rows % rpb:
+            raise ValueError(f"{who}: rows_per_batch must divide the rows")
+        Bb, a_rs = rows // rpb, x.stride(0)
+        a_bs = rpb * a_rs
+    else:
+        raise ValueError(f"{who}: x is [rows, K] or [B, T, K]")
+    if x.stride(-1) != 1 and x.numel():
+        raise ValueError(f"{who}: the rows of x must be contiguous")
+    if W.shape[1] != K or W.dtype != x.dtype:
+        raise ValueError(f"{who}: W is [N, K] in x's dtype")
+    return Bb, rpb, K, a_bs, a_rs
+
+
 class Ops:
     """All kernels, bound to one Handle (one HIP stream)."""
 
@@ -93,25 +117,8 @@ class Ops:
         stream like every op here; CPU tensors raise."""
         _chk_contig(W)
         _p(x), _p(W)                                           # (CPU tensors raise here, whatever the row count)
-        if x.dim() == 3:
-            if rows_per_batch is not None and rows_per_batch != x.shape[1]:
-                raise ValueError("linear_pick: rows_per_batch belongs to 2-D x")
-            Bb, rpb, K = x.shape
-            a_bs, a_rs = x.stride(0), x.stride(1)
-        elif x.dim() == 2:
-            rows, K = x.shape
-            rpb = max(rows, 1) if rows_per_batch is None else int(rows_per_batch)
-            if rpb <= 0 or rows % rpb:
-                raise ValueError("linear_pick: rows_per_batch must divide the rows")
-            Bb, a_rs = rows // rpb, x.stride(0)
-            a_bs = rpb * a_rs
-        else:
-            raise ValueError("linear_pick: x is [rows, K] or [B, T, K]")
-        if x.stride(-1) != 1 and x.numel():
-            raise ValueError("linear_pick: the rows of x must be contiguous")
+        Bb, rpb, K, a_bs, a_rs = _row_view("linear_pick", x, W, rows_per_batch)
         N = W.shape[0]
-        if W.shape[1] != K or W.dtype != x.dtype:
-            raise ValueError("linear_pick: W is [N, K] in x's dtype")
         if out is None:
             out = torch.empty(Bb, rpb, device=x.device, dtype=torch.int32)
         elif out.dtype != torch.int32 or tuple(out.shape) != (Bb, rpb):
@@ -136,25 +143,8 @@ class Ops:
         the ids, last dimension contiguous, any other strides.  CPU tensors raise."""
         _chk_contig(W)
         _p(x), _p(W)                                           # (CPU tensors raise here, whatever the row count)
-        if x.dim() == 3:
-            if rows_per_batch is not None and rows_per_batch != x.shape[1]:
-                raise ValueError("linear_topk: rows_per_batch belongs to 2-D x")
-            Bb, rpb, K = x.shape
-            a_bs, a_rs = x.stride(0), x.stride(1)
-        elif x.dim() == 2:
-            rows, K = x.shape
-            rpb = max(rows, 1) if rows_per_batch is None else int(rows_per_batch)
-            if rpb <= 0 or rows % rpb:
-                raise ValueError("linear_topk: rows_per_batch must divide the rows")
-            Bb, a_rs = rows // rpb, x.stride(0)
-            a_bs = rpb * a_rs
-        else:
-            raise ValueError("linear_topk: x is [rows, K] or [B, T, K]")
-        if x.stride(-1) != 1 and x.numel():
-            raise ValueError("linear_topk: the rows of x must be contiguous")
+        Bb, rpb, K, a_bs, a_rs = _row_view("linear_topk", x, W, rows_per_batch)
         N = W.shape[0]
-        if W.shape[1] != K or W.dtype != x.dtype:
-            raise ValueError("linear_topk: W is [N, K] in x's dtype")
         k = int(k)
         kp = k + (keep is not None)
         if out is None:
