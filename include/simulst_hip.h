@@ -602,7 +602,50 @@ int simulst_pack_fragment_major(simulst_handle* h, const void* W, void* out, int
  * criterion/joint_ctc_criterion.py:78-90: the same state recursion with log-add over the legal predecessors in place of max (s-2 only
  * between different labels), -log of the two final states' sum, +inf when no alignment exists (never NaN), T = 0 the sum of the
  * blanks.  No back-pointers: scratch is not read and may be NULL; as_labels is ignored; the 1023-label limit is the same.  The
- * arguments existed before with a refused value, so simulst_version() stays 108. */
+ * arguments existed before with a refused value, so simulst_version() stays 108.
+ *
+ * max_target_length < 0 (refused as "shape" before; simulst_version() stays 108): no transcript is given, the call SEARCHES for it --
+ * every frame of the time-synchronous CTC prefix beam search over per-frame candidate lists in one launch (csrc/ctc_prefix.hip), the
+ * recursion simulst_amd/ctc.py ctc_prefix_beam_advance spells out, with its pool order and tie rule.  The mode is recognised before any
+ * other check; the arguments then mean
+ *   beam       = -max_target_length, 1..16 (E_SHAPE "beam" otherwise)
+ *   log_probs  the CANDIDATES' log-probabilities, fp32, element (t, b, j) at t*lp_stride_t + b*lp_stride_b + j*lp_stride_v, j = 0..k;
+ *              slot 0 is the blank
+ *   input_lengths  int64 [N]: the frames of this call to take of utterance b, t = 0 .. min(S, input_lengths[b]) - 1; with none
+ *              (<= 0) the utterance's state is not touched, bit for bit.  Candidates of frames at and past it are not read
+ *   S          the frames in the call (S > 0 as in the other modes);  N utterances (N <= 0: nothing is launched, OK)
+ *   out        int64 [N][beam][cap]: the beam's strings, read at entry and written at exit, `pad` behind each length and in dead slots
+ *   scratch    a HOST simulst_ctc_prefix_desc (below), read during the call like simulst_linear_desc
+ *   blank      >= 0 as before; informational (the blank is candidate slot 0 by construction)
+ *   targets, target_lengths, as_labels, neg_log_likelihood   ignored; may be NULL
+ * State of utterance b and beam slot i (in / out): lengths[b][i], p_b[b][i], p_nb[b][i] (log-probability of the prefix ending in a
+ * blank / in its last label) and the string out[b][i][:lengths].  Slots are in descending order of p_b (+) p_nb; a dead slot is
+ * (-inf, -inf), length 0, all `pad`.  Per frame and live prefix l with last label e, lp the frame's candidate log-probabilities:
+ *   p_b'(l) = (p_b (+) p_nb) + lp[blank];   p_nb'(l) = p_nb + lp[e] if e is a candidate;
+ *   p_nb'(l + c) = p_b + lp[c] if c == e else (p_b (+) p_nb) + lp[c]        for every candidate c >= 0 (candidates of a frame are distinct)
+ * An extension that spells a prefix already in the beam (decided on the labels; a hash only filters) is added to that entry's p_nb'
+ * and leaves the pool; the best `beam` pool entries by p_b' (+) p_nb' survive, ties in pool index order: the beam's own entries, then
+ * the extensions prefix-major, candidate-minor.  (+) is max + log1p(exp(-|a - b|)) in fp32 with the accurate expf / log1pf, -inf when
+ * both operands are, never NaN.  An utterance's result depends neither on its position in the batch nor on how its frames are cut into
+ * calls: the state after frames [0, a) then [a, T) is the state after [0, T) in every bit.
+ * The strings stay in LDS for the call (int32, two buffers), which bounds the capacity: cap <= SIMULST_CTC_PREFIX_CAP(beam) -- 1104
+ * labels at beam 16, 2208 at beam 8.  The caller provides cap >= the longest length at entry + the frames taken (a string grows by at
+ * most one label a frame; a label that would not fit is dropped).
+ * Refusals, before any launch: E_NULL for a NULL scratch, out, log_probs, input_lengths, cand_ids, lengths, p_b or p_nb; E_SHAPE for
+ * S <= 0 or blank < 0 ("shape"), beam > 16 ("beam"), k outside 0..8 ("k"), cap < 1 or above the limit ("cap"). */
+#define SIMULST_CTC_PREFIX_STRING_BYTES 141312                                        /* LDS for the two string buffers: 138 KB */
+#define SIMULST_CTC_PREFIX_CAP(beam) ((SIMULST_CTC_PREFIX_STRING_BYTES / (8 * (beam))) & ~3)
+typedef struct simulst_ctc_prefix_desc {
+  const int32_t* cand_ids;        /* device int32: the candidates' labels, element (b, t, j) at b*id_stride_b + t*id_stride_t + j,
+                                     j = 0..k (simulst_linear's SIMULST_EPI_ROW_TOPK output as it is); -1 = no candidate; slot 0 unused */
+  int64_t id_stride_b, id_stride_t;
+  int32_t k;                      /* non-blank candidates per frame, 0..8 */
+  int32_t pad;                    /* label written behind each string and into dead slots */
+  int32_t cap;                    /* labels per string of `out` */
+  int64_t* lengths;               /* device int64 [N][beam], in / out */
+  float* p_b;                     /* device fp32 [N][beam], in / out */
+  float* p_nb;                    /* device fp32 [N][beam], in / out */
+} simulst_ctc_prefix_desc;
 int64_t simulst_ctc_best_alignment_scratch_bytes(int32_t N, int32_t S, int32_t max_target_length);
 int simulst_ctc_best_alignment(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
                                int64_t lp_stride_v, const int64_t* targets, int64_t tg_stride_b,

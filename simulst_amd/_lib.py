@@ -52,6 +52,21 @@ class EmfAttnDesc(C.Structure):
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 
+class CtcPrefixDesc(C.Structure):
+    """simulst_ctc_prefix_desc: what the search mode of simulst_ctc_best_alignment (max_target_length < 0) reads through `scratch`"""
+    _fields_ = [("cand_ids", C.c_void_p), ("id_stride_b", C.c_int64), ("id_stride_t", C.c_int64),
+                ("k", C.c_int32), ("pad", C.c_int32), ("cap", C.c_int32),
+                ("lengths", C.c_void_p), ("p_b", C.c_void_p), ("p_nb", C.c_void_p)]
+
+
+CTC_PREFIX_STRING_BYTES = 141312           # SIMULST_CTC_PREFIX_STRING_BYTES
+
+
+def ctc_prefix_cap(beam: int) -> int:
+    """SIMULST_CTC_PREFIX_CAP(beam): the longest strings the search mode keeps on chip"""
+    return (CTC_PREFIX_STRING_BYTES // (8 * beam)) & ~3
+
+
 class DecLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("wqkv", "bqkv", "wo", "bo", "ln1_g", "ln1_b", "ln2_g", "ln2_b", "ln3_g",
                                           "ln3_b", "c_wq", "c_bq", "c_wq_soft", "c_bq_soft", "c_wo", "c_bo", "fc1",

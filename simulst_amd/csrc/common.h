@@ -36,6 +36,7 @@ enum sl_lds_slot {
   SL_LDS_QKV_ROWS,          // ffn_pipe.hip qkv_rows_kernel
   SL_LDS_CONV_POS,          // rowops.hip conv_pos_kernel
   SL_LDS_CTC,               // ctc_align.hip
+  SL_LDS_CTC_PREFIX,        // ctc_prefix.hip
   SL_LDS_DEC_CHAIN,         // dec_chain.hip: the layer chains (and experiments/dec_chain_launch.inc)
   SL_LDS_DEC_CHAIN_PROBE,   // dec_chain.hip: the chain-race probe kernels (DEBUG_HOOKS builds)
   SL_LDS_TILE256,           // gemm_tile256.hip: register-staged form
@@ -393,6 +394,12 @@ int sl_self_attention_fused(simulst_handle* h, const void* x, const float* ln_g,
                             const float* bqkv, const void* Wo, void* k_cache, void* v_cache, const int32_t* n_prev,
                             int np_uniform, float* partial, int32_t B, int32_t H, int32_t d, int32_t cap,
                             int32_t dtype);
+
+// the search mode of simulst_ctc_best_alignment (ctc_prefix.hip): beam = -max_target_length, desc the caller's simulst_ctc_prefix_desc;
+// makes every refusal of the mode itself
+int sl_ctc_prefix_beam(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b, int64_t lp_stride_v,
+                       const int64_t* input_lengths, int32_t S, int32_t N, int32_t beam, int32_t blank, const void* desc,
+                       int64_t* out);
 
 // beam-state reorder (beam.hip): the launch shared by simulst_beam_reorder (head_step: the layers' head_step / head_read move per
 // head) and simulst_transducer_beam_reorder (pe_src / pe_dst: one int32 per row moves); each front end makes its own refusals

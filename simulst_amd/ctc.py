@@ -13,8 +13,9 @@ hypotheses, and ``CTCTranscriber.score_ctc`` is the model-level call.
 
 ``ctc_topk`` is the head's per-frame candidate list -- the blank and the best k other labels with their log-probabilities, again
 without the logits (Ops.linear_topk: SIMULST_EPI_ROW_TOPK) --, ``ctc_prefix_beam_advance`` the time-synchronous prefix beam search over
-such lists (device tensor operations, no host synchronisation inside the frame loop; the state goes in and comes out, so that chunks of
-rows continue one search), ``ctc_prefix_beam_search`` the two together and ``CTCTranscriber.transcribe_ctc_nbest`` the model-level call,
+such lists (on the GPU every frame of a call in ONE launch, the search mode of simulst_ctc_best_alignment in csrc/ctc_prefix.hip, with
+the same recursion as device tensor operations kept as the comparison; the state goes in and comes out, so that chunks of rows continue
+one search), ``ctc_prefix_beam_search`` the two together and ``CTCTranscriber.transcribe_ctc_nbest`` the model-level call,
 whose hypotheses ``ctc_rescore`` gives their exact likelihoods.  No language model is fused in, and no gradient is computed.
 
 The blank index is a keyword everywhere (default 0, the criterion's fallback, joint_ctc_criterion.py:76).
@@ -224,10 +225,12 @@ def ctc_prefix_beam_init(B: int, beam: int, device, pad: int = 1):
             p_b, torch.full((B, beam), ninf, dtype=torch.float32, device=device))
 
 
-def ctc_prefix_beam_advance(ids: torch.Tensor, lprob: torch.Tensor, enc_len: torch.Tensor, state, *, pad: int = 1):
+def ctc_prefix_beam_advance(ids: torch.Tensor, lprob: torch.Tensor, enc_len: torch.Tensor, state, *, pad: int = 1, ops=None,
+                            composed: bool = False):
     """Time-synchronous CTC prefix beam search over candidate lists: ids [B, T, k + 1] (slot 0 the blank, -1 = no candidate), lprob
-    [B, T, k + 1] fp32 (ctc_topk's outputs, or any lists of that form), enc_len [B] frames to take of each row of the batch, state
-    (strings, lengths, p_b, p_nb) as ctc_prefix_beam_init makes it -> the state after the frames; strings grows to hold them.
+    [B, T, k + 1] fp32 (ctc_topk's outputs, or any lists of that form, any batch / frame strides), enc_len [B] frames to take of each row
+    of the batch, state (strings, lengths, p_b, p_nb) as ctc_prefix_beam_init makes it -> the state after the frames (new tensors; the
+    state given is not written); strings grows by T to hold them.
 
     Per frame and kept prefix l with last label e (pool index order: the beam's own entries first, then prefix-major, candidate-minor
     extensions):
@@ -236,8 +239,49 @@ def ctc_prefix_beam_advance(ids: torch.Tensor, lprob: torch.Tensor, enc_len: tor
     An extension that spells a prefix already in the beam is added to that entry's p_nb' (the strings are compared, label by label: a
     beam entry has ONE parent string, so at most one extension reaches it and the sum has one order) and leaves the pool; the beam
     best of the pool by p_b' (+) p_nb' survive, ties in pool index order (a stable sort).  A frame at or past enc_len[b] leaves row b's
-    state as it is.  Device tensor operations only, no read-back: this is the interface a recursion kernel would take over -- candidates
-    in, state in and out."""
+    state as it is.
+
+    On the GPU all T frames run in ONE launch (the search mode of simulst_ctc_best_alignment, csrc/ctc_prefix.hip: one wave per
+    utterance, the strings in LDS for the call), with no read-back; `ops` is the Ops whose stream it goes to (default: a new one).  The
+    same recursion as torch tensor operations -- about 120 small launches a frame -- is kept as the comparison and is what runs with
+    composed=True, for CPU tensors, and where the kernel has no place for the call: strings longer than _lib.ctc_prefix_cap(beam)
+    labels (1104 at beam 16, 2208 at beam 8), more than 16 prefixes or more than 8 candidates.  (Lists of the blank alone, k = 0, are the
+    kernel's only: the torch form reduces over the candidates.)  Both forms hold the fp64 reference's
+    bound; they need not agree in the last bit with each other, but each gives the same bits however the frames are cut into calls."""
+    from ._lib import ctc_prefix_cap
+    strings, lengths, p_b, p_nb = state
+    B, T, kp = ids.shape
+    beam = p_b.size(1)
+    if composed or not ids.is_cuda or kp - 1 > 8 or not (1 <= beam <= BEAM_MAX) or strings.size(2) + T > ctc_prefix_cap(beam):
+        return _prefix_beam_advance_composed(ids, lprob, enc_len, state, pad)
+    if T == 0 or B == 0:
+        return strings, lengths, p_b, p_nb
+    import ctypes
+    from ._lib import CtcPrefixDesc
+    from .ops import Ops, _p
+    ops = ops or Ops()
+    dev = ids.device
+    if ids.dtype != torch.int32 or ids.stride(2) != 1:
+        ids = ids.to(torch.int32).contiguous()
+    if lprob.dtype != torch.float32:
+        lprob = lprob.float()
+    il = torch.as_tensor(enc_len, device=dev).to(torch.int64).contiguous()
+    strings = torch.cat([strings.to(torch.int64), torch.full((B, beam, T), pad, dtype=torch.int64, device=dev)], dim=2)
+    lengths = lengths.to(torch.int64).clone(memory_format=torch.contiguous_format)
+    p_b = p_b.float().clone(memory_format=torch.contiguous_format)
+    p_nb = p_nb.float().clone(memory_format=torch.contiguous_format)
+    d = CtcPrefixDesc()
+    d.cand_ids, d.id_stride_b, d.id_stride_t = ids.data_ptr(), ids.stride(0), ids.stride(1)
+    d.k, d.pad, d.cap = kp - 1, int(pad), strings.size(2)
+    d.lengths, d.p_b, d.p_nb = lengths.data_ptr(), p_b.data_ptr(), p_nb.data_ptr()
+    ops.h.check(ops.lib.simulst_ctc_best_alignment(ops.h.ptr, _p(lprob), lprob.stride(1), lprob.stride(0), lprob.stride(2), _p(None), 0,
+                                                   _p(il), _p(None), T, B, -beam, 0, 0, ctypes.addressof(d), _p(strings), _p(None)),
+                "simulst_ctc_best_alignment (prefix beam)")
+    return strings, lengths, p_b, p_nb
+
+
+def _prefix_beam_advance_composed(ids, lprob, enc_len, state, pad):
+    """ctc_prefix_beam_advance as device tensor operations, no read-back (and the form for CPU tensors)"""
     strings, lengths, p_b, p_nb = state
     B, T, kp = ids.shape
     k, beam, dev = kp - 1, p_b.size(1), ids.device
@@ -294,12 +338,12 @@ def ctc_prefix_beam_advance(ids: torch.Tensor, lprob: torch.Tensor, enc_len: tor
 
 def ctc_prefix_beam_search(ops, head_w: torch.Tensor, enc_btd: torch.Tensor, enc_len: torch.Tensor, *, beam: int = 8, candidates: int = 8,
                            nbest: int = 1, blank: int = 0, pad: int = 1, head_b: Optional[torch.Tensor] = None, state=None,
-                           return_state: bool = False):
+                           return_state: bool = False, composed: bool = False):
     """Prefix beam search over the head's top `candidates` labels of every frame (ctc_topk + ctc_prefix_beam_advance) ->
     {"tokens" [B, nbest, Lmax] int64 padded with `pad`, "n" [B, nbest], "score" [B, nbest] = log(p_b + p_nb), descending; a slot the
     search has no prefix for holds n = 0 and score -inf} and, with return_state, "state" to pass to the next call: rows released chunk
     by chunk (encoder.infer) give the bits one call over all rows gives.  1 <= nbest <= beam <= 16, 1 <= candidates <= 8.  The frame
-    loop runs on the device; the one read-back is Lmax."""
+    loop runs on the device, in one launch (composed=True: as tensor operations, ctc_prefix_beam_advance); the one read-back is Lmax."""
     if not (1 <= nbest <= beam <= BEAM_MAX):
         raise ValueError("ctc_prefix_beam_search: 1 <= nbest <= beam <= 16")
     B = enc_btd.size(0)
@@ -308,7 +352,7 @@ def ctc_prefix_beam_search(ops, head_w: torch.Tensor, enc_btd: torch.Tensor, enc
         state = ctc_prefix_beam_init(B, beam, enc_btd.device, pad)
     elif state[2].shape != (B, beam):
         raise ValueError("ctc_prefix_beam_search: state belongs to another batch or beam")
-    strings, lengths, p_b, p_nb = ctc_prefix_beam_advance(cand["ids"], cand["lprob"], enc_len, state, pad=pad)
+    strings, lengths, p_b, p_nb = ctc_prefix_beam_advance(cand["ids"], cand["lprob"], enc_len, state, pad=pad, ops=ops, composed=composed)
     Lmax = int(lengths.max().item()) if B else 0
     strings = strings[:, :, :Lmax].contiguous()
     out = {"tokens": strings[:, :nbest], "n": lengths[:, :nbest], "score": _lae(p_b, p_nb)[:, :nbest]}

@@ -2,8 +2,11 @@
 """The CTC head's n-best path: (a) the per-frame candidates -- the fused call (Ops.linear_topk(k=8, keep=0): simulst_linear with
 SIMULST_EPI_ROW_TOPK, no logits in memory) against the composition the library offered before it -- ops.linear(..., EPI_BIAS_F32OUT) to
 fp32 logits [rows, V], then torch.topk and logsumexp over them; (b) the whole prefix beam search (ctc.ctc_prefix_beam_search, beam 8,
-8 candidates) at 64 x 250 rows against ctc.ctc_greedy and against the same search fed from materialised logits, with the number of
-device launches of one search per frame.
+8 candidates) at 64 x 250 and 1280 x 250 rows, and one chunk of 64 x 16 rows continuing a search over 234 rows from its state, in three
+forms: the search whose recursion is ONE launch (csrc/ctc_prefix.hip), the same search with the recursion as torch tensor operations
+(composed=True: the code path before the kernel) and ctc.ctc_greedy -- with the recursion launch's own time (the handle's timer over
+the launch; and HIP events around ctc_prefix_beam_advance, which adds the state's copies) beside the top-k launch's, and the device
+launches of one search in both forms.
 
 bf16, D = 256, V = 4096 (s2t_emformer_s / cif_transformer_s), no bias (the reference's head has none).  Shapes of (a):
   64 x 250 rows     the bench batch (64 utterances of 1000 frames)
@@ -18,7 +21,7 @@ events and reports the per-call time; the figure of a form is the median of its 
 form must move through HBM, computed from the shapes.
 
 Prints ONE JSON line and writes it to --out.  Run under a time limit:
-    timeout -k 10 400 python tools/ctc_beam_bench.py --out profiles/ctc_beam_bench.json
+    timeout -k 10 600 python tools/ctc_beam_bench.py --out profiles/ctc_prefix_beam_bench.json
 """
 import argparse
 import json
@@ -75,13 +78,64 @@ def count_launches(fn):
         return None, f"{type(ex).__name__}: {ex}"
 
 
+SEARCH_SHAPES = ("64x250", "1280x250", "64x16")
+
+
+def search_block(ops, W, view, B, T, passes, chunk_after=0, gen=None):
+    """(b): beam 8, 8 candidates over view [B, T, D]; chunk_after > 0: the T rows continue a search over that many earlier rows"""
+    from simulst_amd import _lib, ctc
+    lens = torch.full((B,), T, device="cuda", dtype=torch.int64)
+    state = None
+    if chunk_after:
+        before = torch.randn(B, chunk_after, D, generator=gen, device="cuda").to(torch.bfloat16)
+        state = ctc.ctc_prefix_beam_search(ops, W, before, torch.full_like(lens, chunk_after), beam=8, candidates=K_CAND, return_state=True)["state"]
+    cand = ctc.ctc_topk(ops, W, view, lens, k=K_CAND)
+    st0 = state if state is not None else ctc.ctc_prefix_beam_init(B, 8, "cuda")
+
+    def search(composed=False):
+        return ctc.ctc_prefix_beam_search(ops, W, view, lens, beam=8, candidates=K_CAND, nbest=1, state=state, composed=composed)
+
+    forms = {"search": search, "search_composed": lambda: search(True), "greedy": lambda: ctc.ctc_greedy(ops, W, view, lens),
+             "topk": lambda: ctc.ctc_topk(ops, W, view, lens, k=K_CAND),
+             "advance": lambda: ctc.ctc_prefix_beam_advance(cand["ids"], cand["lprob"], lens, st0, ops=ops)}
+    a, b = search(), search(True)
+    torch.cuda.synchronize()
+    same_best = float((a["n"] == b["n"]).float().mean())
+    for fn in forms.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in forms}
+    for _ in range(passes):
+        for k, fn in forms.items():
+            times[k].append(time_calls(fn, 1))
+    kern = []                                                      # the recursion launch alone: the handle's event pair around it
+    for _ in range(passes):
+        ops.h.timer_reset()
+        ops.h.timer_enable(_lib.K_SCAN, True)
+        forms["advance"]()
+        torch.cuda.synchronize()
+        kern.append(ops.h.timer_read(_lib.K_SCAN)[0])
+        ops.h.timer_enable(_lib.K_SCAN, False)
+    ops.h.timer_reset()
+    n_launch, why = count_launches(search)
+    n_comp, why_c = count_launches(lambda: search(True))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    return {"beam": 8, "candidates": K_CAND, "utterances": B, "frames": T, "frames_before_in_state": chunk_after,
+            **{k + "_ms": stats(v) for k, v in times.items()}, "recursion_kernel_ms": stats(kern),
+            "search_speedup_over_composed": med["search_composed"] / med["search"],
+            "search_over_greedy": med["search"] / med["greedy"],
+            "recursion_kernel_share_of_search": statistics.median(kern) / med["search"],
+            "topk_share_of_search": med["topk"] / med["search"],
+            "best_length_agreement_with_composed": same_best,
+            "launches_per_search": n_launch, "launches_per_search_composed": n_comp, "launch_count_note": why or why_c}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--passes", type=int, default=7)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
-    from simulst_amd import ctc
     from simulst_amd.ops import Ops
     ops = Ops()
     g = torch.Generator(device="cuda").manual_seed(4096)
@@ -125,36 +179,8 @@ def main():
                                   "hbm_roofline_fraction_fused": bytes_fused / (HBM_PEAK_TBS * 1e12) / (mf * 1e-3),
                                   "fused_tflops": 2.0 * rows * V * D / (mf * 1e-3) / 1e12, "id_agreement": agree}
         faster_everywhere = faster_everywhere and mf < mc
-        if name != "64x250":
-            del buf, view, flat, logits
-            continue
-        # (b) the whole search over these rows
-        lens = torch.full((B,), T, device="cuda", dtype=torch.int64)
-
-        def search():
-            return ctc.ctc_prefix_beam_search(ops, W, view, lens, beam=8, candidates=K_CAND, nbest=1)
-
-        def search_composed():
-            ids, lprob, _ = composed_candidates(ops, flat, W, logits, B, T)
-            st = ctc.ctc_prefix_beam_advance(ids, lprob, lens, ctc.ctc_prefix_beam_init(B, 8, "cuda"))
-            return st[0][:, :1, :int(st[1].max().item())]
-
-        def greedy():
-            return ctc.ctc_greedy(ops, W, view, lens)
-
-        forms = {"search": search, "search_from_logits": search_composed, "greedy": greedy}
-        for fn in forms.values():
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in forms}
-        for _ in range(args.passes):
-            for k, fn in forms.items():
-                times[k].append(time_calls(fn, 1))
-        n_launch, why = count_launches(search)
-        result["search_64x250"] = {"beam": 8, "candidates": K_CAND, "frames": T,
-                                   **{k + "_ms": stats(v) for k, v in times.items()},
-                                   "launches_per_search": n_launch, "launches_per_frame": None if n_launch is None else n_launch / T,
-                                   "launch_count_note": why}
+        if name in SEARCH_SHAPES:
+            result["search_" + name] = search_block(ops, W, view, B, T, args.passes, chunk_after=234 if name == "64x16" else 0, gen=g)
         del buf, view, flat, logits
     result["topk_faster_than_composition_at_every_shape"] = faster_everywhere
     line = json.dumps(result)
