@@ -646,6 +646,61 @@ typedef struct simulst_ctc_prefix_desc {
   float* p_b;                     /* device fp32 [N][beam], in / out */
   float* p_nb;                    /* device fp32 [N][beam], in / out */
 } simulst_ctc_prefix_desc;
+/* max_target_length < 0 AND targets != NULL (the search mode ignores targets and its callers pass NULL; simulst_version() stays 108):
+ * the call SCORES the candidates of one step of the attention beam search by their CTC prefix probability, or commits the step's
+ * selection (csrc/ctc_prefix_score.hip; DESIGN.md "Beam search", subsection "CTC prefix scores inside the beam").  The mode is
+ * recognised before the search mode's own checks; the arguments then mean
+ *   K          = -max_target_length, 1..32: the candidates of a row (2 * beam)
+ *   N          beam rows r = s * G + j of N / G sentences (N <= 0: nothing is launched, OK);  S the frames of the buffers
+ *   log_probs  the CANDIDATES' log-probabilities under the CTC head, fp32: element (t, s, j * K + k) at t*lp_stride_t + s*lp_stride_b
+ *              + (j * K + k)*lp_stride_v -- simulst_linear's SIMULST_EPI_ROW_GATHER over cand_tok viewed as [N / G][G * K]
+ *   targets    int64 [N]: the last label of each row's hypothesis (not read where the prefix is empty)
+ *   target_lengths  int64 [N]: the labels of each row's hypothesis, 0 = the empty prefix
+ *   input_lengths   int64 [N]: the frames T of each row, cut to S; frames at and past T are not read
+ *   scratch    a HOST simulst_ctc_score_desc (below), read during the call
+ *   blank      >= 0: a candidate equal to it, to pad, or negative has psi = -inf
+ *   tg_stride_b, as_labels, out, neg_log_likelihood   ignored; may be 0 / NULL
+ * op 0, score (one launch, a wave per row, a lane per candidate; rows of finished sentences, and with first_only the rows j > 0, are
+ * not touched).  The row's state is gn[t], gb[t] (state [N][S][2]: log-probability of the alignments of frames 0..t that spell the
+ * hypothesis g and end in its last label / in a blank) and psi [N].  For a candidate c that is a label, e the last label of g:
+ *   phi[t] = gb[t] if c == e else gn[t] (+) gb[t];  phi[-1] = 0 for the empty g, else -inf;  gn'[-1] = gb'[-1] = -inf
+ *   gn'[t] = (gn'[t-1] (+) phi[t-1]) + x[t][c];  gb'[t] = (gn'[t-1] (+) gb'[t-1]) + x[t][blank];  psi(g c) = (+)_t (phi[t-1] + x[t][c])
+ * (psi(g c) = -inf with T = 0); for c == eos psi = gn[T-1] (+) gb[T-1] (T = 0: 0 for the empty g, else -inf).  (+) as in the search
+ * mode.  delta = -1e4 if psi(h) is -inf, else max(psi(h) - psi(g), -1e4); the candidate's score becomes cand_lp unchanged where it is
+ * -inf or weight == 0, else (1 - weight) cand_lp + weight delta.  Outputs: cand_state [N][S][K][2] (gn', gb' of lane k; -inf for a
+ * candidate that is no label), cand_psi [N][K], and cand_lp / cand_tok REWRITTEN IN PLACE in candidate order (descending score, equal
+ * scores to the lower token) with cand_slot [N][K] = the slot each entry came from (the k of cand_state / cand_psi).  A candidate's
+ * result does not depend on its slot, its row or the other candidates.
+ * op 1, commit (behind simulst_beam_select): row r of an unfinished sentence takes cand_state / cand_psi of candidate next_tok[r] of
+ * row reorder[r] into state_out [N][S][2] / psi_out [N], with last_out[r] = next_tok[r] and len_out[r] = target_lengths[reorder[r]] + 1.
+ * A parent outside the row's sentence or a token that is not among the parent's candidates adds 1 to *result and leaves the row.
+ * Refusals, before any launch: E_NULL for a NULL scratch, targets, target_lengths, input_lengths, cand_state, cand_psi, cand_tok,
+ * cand_slot, and for op 0 log_probs, blank_lp, state, psi, cand_lp, for op 1 next_tok, reorder, state_out, psi_out, last_out, len_out,
+ * result; E_SHAPE for K outside 1..32, G < 1, S <= 0, blank < 0, an op other than 0 / 1, N not a multiple of G. */
+typedef struct simulst_ctc_score_desc {
+  int32_t op;                     /* 0 = score, 1 = commit */
+  int32_t G;                      /* rows per sentence (the beam) */
+  int32_t eos, pad;
+  float weight;                   /* lambda, the CTC weight of the combined score */
+  int32_t first_only;             /* score: only row j = 0 of every sentence (step 0 of the beam search) */
+  const float* blank_lp;          /* device fp32: the blank's log-probability, element (s, t) at s*blank_stride_b + t */
+  int64_t blank_stride_b;
+  const float* state;             /* device fp32 [N][S][2] */
+  const float* psi;               /* device fp32 [N] */
+  float* cand_state;              /* device fp32 [N][S][K][2]: written by score, read by commit */
+  float* cand_psi;                /* device fp32 [N][K] */
+  float* cand_lp;                 /* device fp32 [N][K], in / out (simulst_beam_topk's) */
+  int32_t* cand_tok;              /* device int32 [N][K], in / out */
+  int32_t* cand_slot;             /* device int32 [N][K] */
+  const int32_t* finished;        /* device int32 [N / G] or NULL */
+  const int64_t* next_tok;        /* commit: device int64 [N] (simulst_beam_select's) */
+  const int32_t* reorder;         /* commit: device int32 [N] */
+  float* state_out;               /* commit: device fp32 [N][S][2], the second state set */
+  float* psi_out;                 /* commit: device fp32 [N] */
+  int64_t* last_out;              /* commit: device int64 [N] */
+  int64_t* len_out;               /* commit: device int64 [N] */
+  int32_t* result;                /* commit: device int32, + 1 per row whose token was not found */
+} simulst_ctc_score_desc;
 int64_t simulst_ctc_best_alignment_scratch_bytes(int32_t N, int32_t S, int32_t max_target_length);
 int simulst_ctc_best_alignment(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
                                int64_t lp_stride_v, const int64_t* targets, int64_t tg_stride_b,

@@ -59,7 +59,16 @@ class CtcPrefixDesc(C.Structure):
                 ("lengths", C.c_void_p), ("p_b", C.c_void_p), ("p_nb", C.c_void_p)]
 
 
-CTC_PREFIX_STRING_BYTES = 141312           # SIMULST_CTC_PREFIX_STRING_BYTES
+class CtcScoreDesc(C.Structure):
+    """simulst_ctc_score_desc: what the scoring mode of simulst_ctc_best_alignment (max_target_length < 0 with targets) reads through
+    `scratch`"""
+    _fields_ = [("op", C.c_int32), ("G", C.c_int32), ("eos", C.c_int32), ("pad", C.c_int32), ("weight", C.c_float),
+                ("first_only", C.c_int32), ("blank_lp", C.c_void_p), ("blank_stride_b", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("state", "psi", "cand_state", "cand_psi", "cand_lp", "cand_tok", "cand_slot", "finished",
+                                          "next_tok", "reorder", "state_out", "psi_out", "last_out", "len_out", "result")]
+
+
+CTC_PREFIX_STRING_BYTES = 141312          # SIMULST_CTC_PREFIX_STRING_BYTES
 
 
 def ctc_prefix_cap(beam: int) -> int:

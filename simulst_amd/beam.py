@@ -4,8 +4,9 @@ constraints or n-gram blocking.  DESIGN.md section "Beam search" lists the seman
 
 BeamSearch owns the device buffers of one batch of Bs sentences x beam rows and runs the step loop over any source of logits: the
 decoder (MMADecoder.beam_offline) or a scripted model in a test.  Per step, on the handle's stream: the logits source,
-simulst_beam_topk, simulst_beam_select, then the caller's after_select (the decoder commits the step and reorders its incremental
-state, simulst_beam_reorder); once at the end simulst_beam_backtrack.  Every `chunk` steps the count of unfinished sentences is read
+simulst_beam_topk, the caller's rescore if there is one (joint CTC / attention decoding: ctc.CTCPrefixScorer.rescore rewrites the
+candidate lists with the combined scores), simulst_beam_select, then the caller's after_select (the decoder commits the step and
+reorders its incremental state, simulst_beam_reorder); once at the end simulst_beam_backtrack.  Every `chunk` steps the count of unfinished sentences is read
 back on the handle's stream, and the loop ends when it is zero.
 
 ReorderBuffers is the double buffer that reorder works on, for the MMA decoder's state and the transducer's alike.
@@ -120,7 +121,8 @@ class BeamSearch:
         self.fin_raw = torch.zeros(Bs, beam, **f32)
         self.fin_count = torch.zeros(Bs, **i32)
         self.finished = torch.zeros(Bs, **i32)
-        # [0] unfinished sentences after the last step, [1] select: sentences short of beam next rows, [2] reorders out of a block
+        # [0] unfinished sentences after the last step, [1] select: sentences short of beam next rows, [2] reorders out of a block,
+        # [3] a rescorer's commits of a token that was not among its parent's candidates
         self.result = torch.zeros(4, **i32)
         self.host = torch.zeros(4, dtype=torch.int32, pin_memory=True)
         self.event = torch.cuda.Event()
@@ -138,9 +140,11 @@ class BeamSearch:
         return [int(x) for x in self.host]
 
     def run(self, logits_fn: Callable[[int, torch.Tensor], torch.Tensor], after_select: Optional[Callable[[int], None]] = None,
-            chunk: int = 8):
+            chunk: int = 8, rescore: Optional[Callable[[int], None]] = None):
         """logits_fn(step, tokens [R] int64) -> fp32 logits [R, V] of the step; after_select(step) runs behind the selection (the
-        reorder index of the step is in self.reorder).  Returns (tokens [Bs, nbest, L] int64, lengths [Bs, nbest] int32,
+        reorder index of the step is in self.reorder); rescore(step), if given, runs between simulst_beam_topk and the selection and
+        may rewrite self.cand_lp / self.cand_tok (each row's list in candidate order again, and still beam finite candidates a
+        sentence: the selection, cum, lenpen, finalisation and the scores returned are then all of the rewritten score).  Returns (tokens [Bs, nbest, L] int64, lengths [Bs, nbest] int32,
         scores [Bs, nbest] fp32, positional scores [Bs, nbest, L] fp32), on the device."""
         ops, beam = self.ops, self.beam
         t = 0
@@ -149,6 +153,8 @@ class BeamSearch:
             assert logits.dtype == torch.float32 and tuple(logits.shape) == (self.R, self.V), "fp32 logits [R, V]"
             ops.beam_topk(logits, self.max_len, self.finished, self.cand_lp, self.cand_tok, beam=beam, step=t, pad_idx=self.pad,
                           eos_idx=self.eos)
+            if rescore is not None:
+                rescore(t)
             ops.beam_select(self.cand_lp, self.cand_tok, self.max_len, beam=beam, V=self.V, step=t, lenpen=self.lenpen,
                             eos_idx=self.eos, cum=self.cum, next_tok=self.next_tok, reorder=self.reorder, bp_parent=self.bp_parent,
                             bp_token=self.bp_token, bp_cum=self.bp_cum, fin_step=self.fin_step, fin_row=self.fin_row,
@@ -164,6 +170,7 @@ class BeamSearch:
         assert res[0] == 0, f"{res[0]} sentences unfinished after {t} steps"
         assert res[1] == 0, "a sentence ran short of beam finite non-EOS candidates (fairseq's cands_to_ignore case)"
         assert res[2] == 0, "a reorder left its sentence's block of beam rows"
+        assert res[3] == 0, "a rescorer committed a token that was not among its parent's candidates"
         Bs, nb, L, dev = self.Bs, self.nbest, self.L, self.device
         tokens = torch.empty(Bs, nb, L, device=dev, dtype=torch.int64)
         lengths = torch.empty(Bs, nb, device=dev, dtype=torch.int32)

@@ -401,6 +401,12 @@ int sl_ctc_prefix_beam(simulst_handle* h, const float* log_probs, int64_t lp_str
                        const int64_t* input_lengths, int32_t S, int32_t N, int32_t beam, int32_t blank, const void* desc,
                        int64_t* out);
 
+// the scoring mode of simulst_ctc_best_alignment (ctc_prefix_score.hip: max_target_length < 0 with targets): K = -max_target_length, desc
+// the caller's simulst_ctc_score_desc; makes every refusal of the mode itself
+int sl_ctc_prefix_score(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b, int64_t lp_stride_v,
+                        const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths, int32_t S, int32_t N,
+                        int32_t K, int32_t blank, const void* desc);
+
 // beam-state reorder (beam.hip): the launch shared by simulst_beam_reorder (head_step: the layers' head_step / head_read move per
 // head) and simulst_transducer_beam_reorder (pe_src / pe_dst: one int32 per row moves); each front end makes its own refusals
 constexpr int SL_REORDER_MAX_LAYERS = 16;

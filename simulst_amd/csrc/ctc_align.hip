@@ -209,6 +209,10 @@ extern "C" int simulst_ctc_best_alignment(simulst_handle* h, const float* log_pr
                                           int64_t* out, float* neg_log_likelihood) {
   if (!h) return SIMULST_E_NULL;
   // max_target_length < 0: no transcript is given, the call searches for it (ctc_prefix.hip); targets / target_lengths may be NULL
+  // ... and with targets (which the search ignores: its callers pass NULL) it scores the candidates of a beam step (ctc_prefix_score.hip)
+  if (max_target_length < 0 && targets)
+    return sl_ctc_prefix_score(h, log_probs, lp_stride_t, lp_stride_b, lp_stride_v, targets, input_lengths, target_lengths, S, N,
+                               max_target_length < -33 ? 33 : -max_target_length, blank, scratch);   // (33: refused like any K > 32)
   if (max_target_length < 0)
     return sl_ctc_prefix_beam(h, log_probs, lp_stride_t, lp_stride_b, lp_stride_v, input_lengths, S, N,
                               max_target_length < -17 ? 17 : -max_target_length, blank, scratch, out);   // (17: refused like any beam > 16)

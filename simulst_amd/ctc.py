@@ -18,6 +18,11 @@ the same recursion as device tensor operations kept as the comparison; the state
 one search), ``ctc_prefix_beam_search`` the two together and ``CTCTranscriber.transcribe_ctc_nbest`` the model-level call,
 whose hypotheses ``ctc_rescore`` gives their exact likelihoods.  No language model is fused in, and no gradient is computed.
 
+``CTCPrefixScorer`` is the CTC side of joint CTC / attention decoding: inside the attention beam search (beam.BeamSearch, rescore=)
+every candidate of every step is scored by the CTC prefix probability of the extended string -- ``ctc_prefix_score``, one launch a step
+(the scoring mode of simulst_ctc_best_alignment, csrc/ctc_prefix_score.hip) over log-probabilities gathered at the candidates alone --
+and ``ctc_prefix_commit`` moves the chosen candidates' states behind the selection; both have a torch form (composed=True).
+
 The blank index is a keyword everywhere (default 0, the criterion's fallback, joint_ctc_criterion.py:76).
 """
 from typing import Dict, List, Optional
@@ -359,6 +364,236 @@ def ctc_prefix_beam_search(ops, head_w: torch.Tensor, enc_btd: torch.Tensor, enc
     if return_state:
         out["state"] = (strings, lengths, p_b, p_nb)
     return out
+
+
+SCORE_FLOOR = -1.0e4      # the CTC term of an extension no alignment spells (PS_FLOOR of csrc/ctc_prefix_score.hip)
+SCORE_KMAX = 32
+
+
+def ctc_prefix_score(ops, x, xb, state, psi, last, plen, in_len, finished, cand_lp, cand_tok, cand_slot, cand_state, cand_psi, *,
+                     G: int, blank: int, eos: int, pad: int, weight: float, first_only: bool = False, composed: bool = False):
+    """One step's CTC prefix scores (DESIGN.md "Beam search", "CTC prefix scores inside the beam"; the scoring mode of
+    simulst_ctc_best_alignment, csrc/ctc_prefix_score.hip), for R = Bs * G beam rows of K candidates each:
+      x [Bs, S, G * K] fp32 (any strides): the candidates' log-probabilities under the head;  xb [Bs, S] fp32: the blank's
+      state [R, S, 2] fp32 (gn, gb), psi [R] fp32, last [R] int64, plen [R] int64: the rows' hypotheses;  in_len [R] int64 frames
+      finished [Bs] int32 or None;  cand_lp [R, K] fp32 / cand_tok [R, K] int32: simulst_beam_topk's lists, REWRITTEN in place
+      (combined score, candidate order);  cand_slot [R, K] int32, cand_state [R, S, K, 2], cand_psi [R, K]: outputs.
+    Rows of finished sentences, and with first_only the rows j > 0, are left as they are.  composed=True (and CPU tensors): the same
+    arithmetic as torch tensor operations over rows x candidates with a Python loop over the frames."""
+    R, K = cand_tok.shape
+    S = state.size(1)
+    if composed or not cand_tok.is_cuda:
+        return _prefix_score_composed(x, xb, state, psi, last, plen, in_len, finished, cand_lp, cand_tok, cand_slot, cand_state,
+                                      cand_psi, G=G, blank=blank, eos=eos, pad=pad, weight=weight, first_only=first_only)
+    import ctypes
+    from ._lib import CtcScoreDesc
+    from .ops import _chk_contig, _p
+    _chk_contig(xb[0] if xb.size(0) else xb, state, psi, last, plen, in_len, finished, cand_lp, cand_tok, cand_slot, cand_state, cand_psi)
+    assert x.dtype == torch.float32 and xb.dtype == torch.float32 and tuple(x.shape[:2]) == (R // G, S) and x.size(2) == G * K
+    assert cand_tok.dtype == torch.int32 and cand_slot.dtype == torch.int32 and last.dtype == plen.dtype == in_len.dtype == torch.int64
+    assert tuple(cand_state.shape) == (R, S, K, 2) and tuple(state.shape) == (R, S, 2)
+    d = CtcScoreDesc()
+    d.op, d.G, d.eos, d.pad, d.weight, d.first_only = 0, int(G), int(eos), int(pad), float(weight), int(bool(first_only))
+    d.blank_lp, d.blank_stride_b = xb.data_ptr(), xb.stride(0)
+    d.state, d.psi, d.cand_state, d.cand_psi = state.data_ptr(), psi.data_ptr(), cand_state.data_ptr(), cand_psi.data_ptr()
+    d.cand_lp, d.cand_tok, d.cand_slot = cand_lp.data_ptr(), cand_tok.data_ptr(), cand_slot.data_ptr()
+    d.finished = finished.data_ptr() if finished is not None else None
+    ops.h.check(ops.lib.simulst_ctc_best_alignment(ops.h.ptr, _p(x), x.stride(1), x.stride(0), x.stride(2), _p(last), 0, _p(in_len),
+                                                   _p(plen), S, R, -K, int(blank), 0, ctypes.addressof(d), _p(None), _p(None)),
+                "simulst_ctc_best_alignment (prefix score)")
+
+
+def ctc_prefix_commit(ops, cand_state, cand_psi, cand_tok, cand_slot, next_tok, reorder, finished, last, plen, in_len, state_out,
+                      psi_out, last_out, len_out, result, *, G: int, composed: bool = False):
+    """Behind simulst_beam_select: row r of an unfinished sentence takes the state and psi of candidate next_tok[r] (int64 [R]) of its
+    parent row reorder[r] (int32 [R]) into state_out [R, S, 2] / psi_out [R], last_out[r] = next_tok[r], len_out[r] = plen[parent] + 1.
+    A token that is not among the parent's candidates (or a parent outside the sentence) adds 1 to result[0] (int32) and leaves the
+    row.  `last` is not read (the entry wants it: it selects the mode)."""
+    R, K = cand_tok.shape
+    S = state_out.size(1)
+    if composed or not cand_tok.is_cuda:
+        return _prefix_commit_composed(cand_state, cand_psi, cand_tok, cand_slot, next_tok, reorder, finished, plen, in_len, state_out,
+                                       psi_out, last_out, len_out, result, G=G)
+    import ctypes
+    from ._lib import CtcScoreDesc
+    from .ops import _chk_contig, _p
+    _chk_contig(cand_state, cand_psi, cand_tok, cand_slot, next_tok, reorder, finished, last, plen, in_len, state_out, psi_out, last_out,
+                len_out)
+    assert next_tok.dtype == torch.int64 and reorder.dtype == torch.int32 and result.dtype == torch.int32
+    assert tuple(cand_state.shape) == (R, S, K, 2) and tuple(state_out.shape) == (R, S, 2)
+    d = CtcScoreDesc()
+    d.op, d.G = 1, int(G)
+    d.cand_state, d.cand_psi, d.cand_tok, d.cand_slot = cand_state.data_ptr(), cand_psi.data_ptr(), cand_tok.data_ptr(), cand_slot.data_ptr()
+    d.finished = finished.data_ptr() if finished is not None else None
+    d.next_tok, d.reorder, d.state_out, d.psi_out = next_tok.data_ptr(), reorder.data_ptr(), state_out.data_ptr(), psi_out.data_ptr()
+    d.last_out, d.len_out, d.result = last_out.data_ptr(), len_out.data_ptr(), result.data_ptr()
+    ops.h.check(ops.lib.simulst_ctc_best_alignment(ops.h.ptr, _p(None), 0, 0, 0, _p(last), 0, _p(in_len), _p(plen), S, R, -K, 0, 0,
+                                                   ctypes.addressof(d), _p(None), _p(None)),
+                "simulst_ctc_best_alignment (prefix score, commit)")
+
+
+def _score_rows(R, G, finished, first_only, dev):
+    """[R] bool: the rows a scoring step touches"""
+    act = torch.ones(R, dtype=torch.bool, device=dev)
+    if finished is not None:
+        act &= ~finished.bool().repeat_interleave(G)
+    if first_only:
+        act &= (torch.arange(R, device=dev) % G) == 0
+    return act
+
+
+def _prefix_score_composed(x, xb, state, psi, last, plen, in_len, finished, cand_lp, cand_tok, cand_slot, cand_state, cand_psi, *, G,
+                           blank, eos, pad, weight, first_only):
+    R, K = cand_tok.shape
+    S, dev = state.size(1), cand_tok.device
+    ninf = torch.full((), float("-inf"), device=dev)
+    act = _score_rows(R, G, finished, first_only, dev)
+    xr = x.reshape(R // G, S, G, K).permute(0, 2, 1, 3).reshape(R, S, K)
+    xbr = xb.repeat_interleave(G, 0)
+    tok = cand_tok.to(torch.int64)
+    special = (tok < 0) | (tok == blank) | (tok == pad)
+    ext = ~special & (tok != eos)
+    is_eos = ~special & (tok == eos)
+    empty = (plen <= 0).unsqueeze(1)
+    same = ext & ~empty & (tok == last.unsqueeze(1))
+    T = in_len.clamp(0, S)
+    inside = torch.arange(S, device=dev).unsqueeze(0) < T.unsqueeze(1)                 # [R, S]
+    gb_g = torch.where(inside, state[..., 1], ninf)
+    tot_g = torch.where(inside, _lae(torch.where(inside, state[..., 0], ninf), gb_g), ninf)
+    pn = torch.full((R, K), float("-inf"), device=dev)
+    pb, acc = pn.clone(), pn.clone()
+    phi = torch.where(empty, torch.zeros((), device=dev), ninf).expand(R, K)
+    new_state = cand_state.clone()
+    for t in range(S):
+        on = inside[:, t:t + 1]
+        if not bool(on.any()):
+            break
+        xt = torch.where(ext & on, xr[:, t], ninf)
+        gn = _lae(pn, phi) + xt
+        gb = _lae(pn, pb) + torch.where(on, xbr[:, t:t + 1], torch.zeros((), device=dev))
+        acc = torch.where(on, _lae(acc, phi + xt), acc)
+        new_state[:, t] = torch.where((on & act.unsqueeze(1)).unsqueeze(-1), torch.stack([gn, gb], dim=-1), new_state[:, t])
+        pn, pb = torch.where(on, gn, pn), torch.where(on, gb, pb)
+        phi = torch.where(on, torch.where(same, gb_g[:, t:t + 1], tot_g[:, t:t + 1]), phi)
+    psi_end = torch.where(T > 0, tot_g.gather(1, (T - 1).clamp(min=0).unsqueeze(1)).squeeze(1),
+                          torch.where(empty.squeeze(1), torch.zeros((), device=dev), ninf))
+    psi_h = torch.where(ext, acc, torch.where(is_eos, psi_end.unsqueeze(1), ninf))
+    floor = torch.full((), SCORE_FLOOR, device=dev)
+    dead = psi_h == ninf
+    delta = torch.where(dead, floor, torch.maximum(torch.where(dead, floor, psi_h) - psi.unsqueeze(1), floor))
+    delta = torch.where(torch.isnan(delta), floor, delta)
+    if weight == 0:
+        sc = cand_lp.clone()
+    else:
+        sc = torch.where(cand_lp == ninf, ninf, (1.0 - weight) * cand_lp + weight * delta)
+    # candidate order: descending score, equal scores to the lower token (then the lower slot): two stable sorts
+    by_tok = torch.sort(tok, dim=1, stable=True).indices
+    order = by_tok.gather(1, torch.sort(sc.gather(1, by_tok), dim=1, descending=True, stable=True).indices)
+    a = act.unsqueeze(1)
+    cand_state.copy_(new_state)
+    cand_psi.copy_(torch.where(a, psi_h, cand_psi))
+    cand_lp.copy_(torch.where(a, sc.gather(1, order), cand_lp))
+    cand_tok.copy_(torch.where(a, cand_tok.gather(1, order), cand_tok))
+    cand_slot.copy_(torch.where(a, order.to(torch.int32), cand_slot))
+
+
+def _prefix_commit_composed(cand_state, cand_psi, cand_tok, cand_slot, next_tok, reorder, finished, plen, in_len, state_out, psi_out,
+                            last_out, len_out, result, *, G):
+    R, K = cand_tok.shape
+    S, dev = state_out.size(1), cand_tok.device
+    rows = torch.arange(R, device=dev)
+    act = _score_rows(R, G, finished, False, dev)
+    par = reorder.to(torch.int64)
+    ok = (par >= 0) & (par < R) & (torch.div(par.clamp(0, R - 1), G, rounding_mode="floor") == torch.div(rows, G, rounding_mode="floor"))
+    par = torch.where(ok, par, rows)
+    hit = cand_tok[par].to(torch.int64) == next_tok.unsqueeze(1)
+    q = hit.to(torch.int32).argmax(1)                                              # the first match
+    slot = cand_slot[par, q].to(torch.int64)
+    ok = ok & hit.any(1) & (slot >= 0) & (slot < K)
+    slot = slot.clamp(0, K - 1)
+    result[:1] += (act & ~ok).sum().to(torch.int32)
+    good = act & ok
+    T = in_len[par].clamp(0, S)
+    take = good.unsqueeze(1) & (torch.arange(S, device=dev).unsqueeze(0) < T.unsqueeze(1))
+    state_out.copy_(torch.where(take.unsqueeze(-1), cand_state[par, :, slot], state_out))
+    psi_out.copy_(torch.where(good, cand_psi[par, slot], psi_out))
+    last_out.copy_(torch.where(good, next_tok, last_out))
+    len_out.copy_(torch.where(good, plen[par].clamp(min=0) + 1, len_out))
+
+
+class CTCPrefixScorer:
+    """The CTC side of joint CTC / attention beam search (DESIGN.md "Beam search", "CTC prefix scores inside the beam") over one
+    batch: enc_btd [Bs, S, D] encoder rows (any batch stride), enc_len [Bs] valid rows, head_w [V, D] the CTC head (same dictionary as
+    the decoder), `beam` rows per sentence, `weight` the lambda of the combined score.
+
+    The blank's column is gathered once; per beam step rescore(step, bs) gathers the log-probabilities of the K = 2 beam candidates
+    simulst_beam_topk left in bs.cand_tok (Ops.linear_gather over the list viewed as [Bs, beam * K]: no copy, no logits), runs the
+    scoring launch and leaves bs.cand_lp / bs.cand_tok combined and in candidate order for simulst_beam_select; commit(step, bs),
+    behind the selection, moves each new row's state into the second of the two state sets, which then swap.  A committed token that
+    was not among its parent's candidates is counted in bs.result[3], which BeamSearch.run asserts to be 0.
+
+    composed=True (and CPU tensors) runs the torch form of both steps; on CPU tensors the gather is a log_softmax of the full
+    product.  log_probs [Bs, S, V] fp32 may stand in for (head_w, enc_btd): the gathers then read it (tests, scripted models)."""
+
+    def __init__(self, ops, head_w, enc_btd, enc_len, *, beam: int, weight: float, blank: int = 0, pad: int, eos: int,
+                 head_b: Optional[torch.Tensor] = None, composed: bool = False, log_probs: Optional[torch.Tensor] = None):
+        if not 0.0 <= float(weight) <= 1.0:
+            raise ValueError(f"ctc_weight must be in [0, 1], got {weight}")
+        if not 1 <= 2 * beam <= SCORE_KMAX:
+            raise ValueError(f"beam must be in [1, {SCORE_KMAX // 2}], got {beam}")
+        src = log_probs if log_probs is not None else enc_btd
+        self.ops, self.w, self.b, self.enc, self.lp = ops, head_w, head_b, enc_btd, log_probs
+        self.G, self.K, self.weight, self.blank, self.pad, self.eos = beam, 2 * beam, float(weight), int(blank), int(pad), int(eos)
+        self.Bs, self.S = Bs, S = src.size(0), src.size(1)
+        self.dev = dev = src.device
+        self.composed = bool(composed) or not src.is_cuda
+        R, G, K = Bs * beam, beam, 2 * beam
+        self.R = R
+        f32, i64 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int64)
+        self.xb = self.gather(torch.full((Bs, 1), self.blank, device=dev, dtype=torch.int32))[:, :, 0].contiguous()      # [Bs, S]
+        il = torch.as_tensor(enc_len, device=dev).to(torch.int64).clamp(0, S)
+        self.in_len = il.repeat_interleave(G).contiguous()
+        # the empty prefix: gn = -inf, gb[t] = the blanks' running sum, psi = 0 (rows past a length are never read)
+        inside = torch.arange(S, device=dev).unsqueeze(0) < il.unsqueeze(1)
+        gb = torch.where(inside, self.xb, torch.zeros((), **f32)).cumsum(1)
+        st = torch.stack([torch.full_like(gb, float("-inf")), gb], dim=-1).repeat_interleave(G, 0).contiguous()           # [R, S, 2]
+        self.state = [st, torch.zeros_like(st)]
+        self.psi = [torch.zeros(R, **f32), torch.zeros(R, **f32)]
+        self.last = [torch.full((R,), -1, **i64), torch.full((R,), -1, **i64)]
+        self.plen = [torch.zeros(R, **i64), torch.zeros(R, **i64)]
+        self.cur = 0
+        self.xc = torch.empty(Bs, S, G * K, **f32)
+        self.cand_state = torch.empty(R, S, K, 2, **f32)
+        self.cand_psi = torch.empty(R, K, **f32)
+        self.cand_slot = torch.zeros(R, K, device=dev, dtype=torch.int32)
+
+    def gather(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """labels int32 [Bs, n] -> fp32 [Bs, S, n]: the head's log-probabilities at the labels (values outside the vocabulary are
+        clamped into it, as Ops.linear_gather does)"""
+        if self.lp is None and self.enc.is_cuda:
+            return self.ops.linear_gather(self.enc, self.w, self.b, labels, out=out)
+        if self.lp is None:
+            z = self.enc.float() @ self.w.float().t()
+            self.lp = torch.log_softmax(z if self.b is None else z + self.b.float(), dim=-1)
+        idx = labels.to(torch.int64).clamp(0, self.lp.size(2) - 1).unsqueeze(1).expand(-1, self.lp.size(1), -1)
+        g = self.lp.float().gather(2, idx)
+        return g if out is None else out.copy_(g)
+
+    def rescore(self, step: int, bs):
+        """between simulst_beam_topk and simulst_beam_select of step `step` of the BeamSearch bs"""
+        c = self.cur
+        self.gather(bs.cand_tok.view(self.Bs, self.G * self.K), out=self.xc)
+        ctc_prefix_score(self.ops, self.xc, self.xb, self.state[c], self.psi[c], self.last[c], self.plen[c], self.in_len, bs.finished,
+                         bs.cand_lp, bs.cand_tok, self.cand_slot, self.cand_state, self.cand_psi, G=self.G, blank=self.blank,
+                         eos=self.eos, pad=self.pad, weight=self.weight, first_only=step == 0, composed=self.composed)
+
+    def commit(self, step: int, bs):
+        """behind simulst_beam_select of step `step`: bs.next_tok / bs.reorder name each new row's candidate"""
+        c = self.cur
+        ctc_prefix_commit(self.ops, self.cand_state, self.cand_psi, bs.cand_tok, self.cand_slot, bs.next_tok, bs.reorder, bs.finished,
+                          self.last[c], self.plen[c], self.in_len, self.state[1 - c], self.psi[1 - c], self.last[1 - c],
+                          self.plen[1 - c], bs.result[3:4], G=self.G, composed=self.composed)
+        self.cur = 1 - c
 
 
 class CTCTranscriber:

@@ -742,14 +742,16 @@ class MMADecoder:
         return hyp, lengths, {"steps": s, "row_steps": row_steps, "calls": calls, "rows": rows_log}
 
     def beam_offline(self, enc_btd: torch.Tensor, enc_len: torch.Tensor, max_len, *, beam: int, lenpen: float = 1.0, nbest: int = 1,
-                     chunk: int = 8, s_cap: Optional[int] = None):
+                     chunk: int = 8, s_cap: Optional[int] = None, ctc=None):
         """Beam search with fairseq's SequenceGenerator semantics (search.BeamSearch, normalize_scores; simulst_amd/beam.py) over
         Bs sentences: enc_btd [Bs, S, D], enc_len [Bs], max_len an int or one cap per sentence (steps 0 .. max_len[s]: at most
         max_len[s] tokens and EOS).  The decoder step is the per-op step() over Bs * beam lockstep rows (row s * beam + j) of an offline
         state whose encoder output is repeated beam times; behind every selection the step is committed and simulst_beam_reorder
         gathers each row's self-attention prefix and monotonic step from its parent row into the state's second buffer set, and the
         two sets swap.  Returns (tokens [Bs, nbest, L] int64 with padding_idx behind each hypothesis, lengths [Bs, nbest] int32 (EOS
-        included), scores [Bs, nbest] fp32, positional scores [Bs, nbest, L] fp32, stats {"steps"}), on the device; L = max(max_len) + 1."""
+        included), scores [Bs, nbest] fp32, positional scores [Bs, nbest, L] fp32, stats {"steps"}), on the device; L = max(max_len) + 1.
+        ctc: a ctc.CTCPrefixScorer over the same sentences and beam (joint CTC / attention decoding): its rescore runs between the
+        candidate top-k and the selection of every step, its commit beside the state reorder; scores are then of the combined score."""
         from .beam import BeamSearch, ReorderBuffers, check_args, sentence_caps
         cfg = self.cfg
         Bs, S, D = enc_btd.shape
@@ -775,8 +777,13 @@ class MMADecoder:
             assert st.cap == cap0, "beam state outgrew its capacity"
             self.ops.beam_reorder(buf.desc, buf.src, buf.dst, bs.reorder, bs.finished, bs.result[2:3], beam=beam, n_prev=st.n_prev_host)
             buf.swap()
+            if ctc is not None:
+                ctc.commit(t, bs)
 
-        tokens, lengths, scores, pos = bs.run(logits_fn, after_select, chunk=chunk)
+        if ctc is not None:
+            assert (ctc.Bs, ctc.G) == (Bs, beam), "the scorer belongs to another batch or beam"
+        tokens, lengths, scores, pos = bs.run(logits_fn, after_select, chunk=chunk,
+                                              rescore=None if ctc is None else (lambda t: ctc.rescore(t, bs)))
         return tokens, lengths, scores, pos, {"steps": bs.steps}
 
     def _offline_state(self, B: int, U: int, S: int, s_cap: Optional[int], cap: Optional[int],

@@ -139,17 +139,40 @@ class SimulSTModel(FairseqModelSurface, CTCTranscriber):
                                                fused=fused)
         return toks, {"encoder": enc, "state": st}
 
-    def generate(self, src_tokens, src_lengths, *, beam=5, lenpen=1.0, nbest=1, max_len_a=0.1, max_len_b=10):
+    def ctc_scorer(self, enc, *, beam, ctc_weight, blank=0):
+        """The ctc.CTCPrefixScorer of joint CTC / attention beam search over an encoder output (forward()'s dict), or None at
+        ctc_weight 0.  ValueError for a weight outside [0, 1], a model without a CTC head, or a head over another dictionary."""
+        if not 0.0 <= float(ctc_weight) <= 1.0:
+            raise ValueError(f"ctc_weight must be in [0, 1], got {ctc_weight}")
+        if not ctc_weight:
+            return None
+        head = self.encoder.w.ctc
+        if head is None:
+            raise ValueError("ctc_weight: this model has no CTC head (ModelConfig.ctc_layer is off / no encoder.ctc_layer.weight)")
+        if head.size(0) != self.cfg.vocab:
+            raise ValueError(f"ctc_weight: the CTC head has {head.size(0)} rows, the decoder's dictionary {self.cfg.vocab}")
+        from .ctc import CTCPrefixScorer
+        return CTCPrefixScorer(self.ops, head, enc["encoder_out_btd"], enc["encoder_lengths"], beam=beam, weight=ctc_weight, blank=blank,
+                               pad=self.cfg.padding_idx, eos=self.cfg.eos)
+
+    def generate(self, src_tokens, src_lengths, *, beam=5, lenpen=1.0, nbest=1, max_len_a=0.1, max_len_b=10, ctc_weight=0.0, blank=0):
         """task.inference_step as eval/generate.py:200-275 calls it with --beam / --lenpen / --nbest: fairseq's SequenceGenerator
         with search.BeamSearch (simulst_amd/beam.py).  Sentence s decodes at most max_len[s] = min(int(max_len_a T_s + max_len_b),
         max_target_positions - 1) tokens and EOS, T_s its own frame count.  Returns per sentence a list of at most nbest
-        {"tokens" (EOS included), "score", "positional_scores", "alignment": None, "attention": None}, best first."""
+        {"tokens" (EOS included), "score", "positional_scores", "alignment": None, "attention": None}, best first.
+        ctc_weight > 0: joint CTC / attention decoding -- every candidate of every step is scored (1 - ctc_weight) x the decoder's
+        log-probability + ctc_weight x the CTC head's prefix log-probability ratio (DESIGN.md "Beam search", "CTC prefix scores inside
+        the beam"; `blank` the head's blank), and "score" / "positional_scores" are of that combined score.  0 is the plain search: no
+        scorer is made."""
         from .beam import hypotheses
+        if not 0.0 <= float(ctc_weight) <= 1.0:
+            raise ValueError(f"ctc_weight must be in [0, 1], got {ctc_weight}")
         enc = self.encoder.forward(src_tokens, src_lengths)
         lens = [int(t) for t in torch.as_tensor(src_lengths).tolist()]
         max_len = [self.target_cap(t, max_len_a, max_len_b) for t in lens]
         toks, lengths, scores, pos, _ = self.decoder.beam_offline(enc["encoder_out_btd"], enc["encoder_lengths"], max_len, beam=beam,
-                                                                  lenpen=lenpen, nbest=nbest)
+                                                                  lenpen=lenpen, nbest=nbest,
+                                                                  ctc=self.ctc_scorer(enc, beam=beam, ctc_weight=ctc_weight, blank=blank))
         return hypotheses(toks, lengths, scores, pos)
 
     def score_reference(self, src_tokens, src_lengths, targets, *, return_alignments=False):

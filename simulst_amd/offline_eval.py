@@ -123,20 +123,22 @@ def make_batch(idx: Sequence[int], lengths: Sequence[int], device, dtype, fbank_
     return fb.to(device=device, dtype=dtype), L.to(device), L, max_steps(Tmax), Tpad
 
 
-def decode_batch(model, batch, retire=True, stop_at_eos=False, beam=1, lenpen=1.0):
+def decode_batch(model, batch, retire=True, stop_at_eos=False, beam=1, lenpen=1.0, ctc_weight=0.0):
     """One ragged launch sequence (rows longest first).  retire: rows leave the step loop at their OWN cap int(0.1 T + 10)
     (decoder.greedy_offline_ragged; the reference's generator shrinks its batch the same way, eval/generate.py:187-209); False: every
     row rides to the cap of the longest member (rounds 2-5).  The hypotheses after trim_hypotheses are the same either way.
     stop_at_eos: rows also leave at their first EOS (decoder.generate_offline: finished rows are compacted out of the batch on the
     device); the tokens are then padding_idx behind each hypothesis' end, its first EOS included.
     beam > 1: beam search (decoder.beam_offline, fairseq's --beam / --lenpen): the best hypothesis of each row, at most
-    min(int(0.1 T + 10), max_target_positions - 1) tokens and EOS, padding_idx behind (one column wider than the greedy paths)."""
+    min(int(0.1 T + 10), max_target_positions - 1) tokens and EOS, padding_idx behind (one column wider than the greedy paths);
+    ctc_weight > 0 makes it joint CTC / attention decoding (SimulSTModel.generate's ctc_weight)."""
     fb, Ld, L, steps, Tpad = batch
     enc = model.encoder.forward(fb, Ld)
     if beam > 1:
         caps = [model.target_cap(int(t)) for t in L.tolist()]
         toks, _, _, _, _ = model.decoder.beam_offline(enc["encoder_out_btd"], enc["encoder_lengths"], caps, beam=beam, lenpen=lenpen,
-                                                      nbest=1, s_cap=Tpad // 4 + 1)
+                                                      nbest=1, s_cap=Tpad // 4 + 1,
+                                                      ctc=model.ctc_scorer(enc, beam=beam, ctc_weight=ctc_weight) if ctc_weight else None)
         return toks[:, 0]
     kw = dict(s_cap=Tpad // 4 + 1, cap=(steps + 2 + 31) // 32 * 32)
     if stop_at_eos:

@@ -72,6 +72,9 @@ def main(argv=None, collect=None):
                     help="offline: beam search of this width (offline_eval.decode_batch(beam=N), fairseq's --beam; the best hypothesis "
                          "is kept, EOS included); 1: the greedy paths")
     ap.add_argument("--lenpen", type=float, default=1.0, help="offline beam search: length penalty (fairseq's --lenpen)")
+    ap.add_argument("--ctc-weight", dest="ctc_weight", type=float, default=0.0,
+                    help="offline beam search (--beam N > 1): joint CTC / attention decoding with this weight on the CTC head's prefix "
+                         "scores (SimulSTModel.generate's ctc_weight; the model is built with a CTC head); 0: the plain search")
     ap.add_argument("--warmup-passes", type=int, default=0,
                     help="whole untimed passes over the shard before the timed ones (allocator pools of every launch-sequence shape, like "
                          "bench.py's warm-up steps); the default warm-up is one sequence per stream")
@@ -109,11 +112,13 @@ def main(argv=None, collect=None):
     if args.model == "s2t_emformer":
         if args.streaming:
             raise SystemExit("--model s2t_emformer: an offline model (full attention), no --streaming")
-        cfg = s2t_emformer_s()
+        cfg = s2t_emformer_s(ctc_layer=args.ctc_weight > 0)
     elif args.streaming and args.policy == "hard":
         cfg = mma_model_s(simul_attn_type="hard_aligned_fixed_pre_decision", fixed_pre_decision_ratio=8, mass_preservation=True)
     else:
-        cfg = mma_model_s(simul_attn_type="waitk_fixed_pre_decision", waitk_lagging=args.waitk)
+        cfg = mma_model_s(simul_attn_type="waitk_fixed_pre_decision", waitk_lagging=args.waitk, ctc_layer=args.ctc_weight > 0)
+    if args.ctc_weight and (args.beam <= 1 or args.streaming):
+        raise SystemExit("--ctc-weight: joint decoding is the offline beam search's (--beam N > 1, no --streaming)")
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     dev = f"cuda:{local}"
     weights = init_model(cfg, seed=999)
@@ -146,7 +151,7 @@ def main(argv=None, collect=None):
     outs = [None] * len(batches)
 
     def decode(m, b):
-        return decode_batch(m, b[1:], stop_at_eos=args.stop_at_eos, beam=args.beam, lenpen=args.lenpen)
+        return decode_batch(m, b[1:], stop_at_eos=args.stop_at_eos, beam=args.beam, lenpen=args.lenpen, ctc_weight=args.ctc_weight)
 
     import threading
     qlock = threading.Lock()
