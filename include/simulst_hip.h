@@ -560,6 +560,21 @@ int simulst_decoder_self_attention(simulst_handle* h, const void* qkv, void* k_c
                                    const int32_t* n_prev, void* ctx, int32_t B, int32_t H, int32_t d,
                                    int32_t cap, int32_t dtype);
 
+/* The same operation in the launch forms of the device-resident decode loops; simulst_decoder_self_attention is this call with
+ * np_uniform = -1 and row_map = NULL.
+ *   np_uniform >= 0: the host-known position of lockstep rows, used for every row in place of n_prev[] (which may then be NULL);
+ *                    np_uniform >= cap is refused (SIMULST_E_SHAPE).  np_uniform < 0: n_prev[] is read, and must not be NULL.
+ *   row_map (optional, [slots] int32, active-row compaction): slot i reads qkv row i and writes ctx row i, and uses the caches and
+ *                    n_prev[] of STREAM row row_map[i]; a negative entry leaves ctx row i and every cache untouched.  The caches hold
+ *                    at least max(row_map) + 1 stream rows.  A row map never names a stream row twice: two slots would append to and
+ *                    read the same cache row in one launch (a race) -- that is the caller's contract, nothing checks it.
+ * n_prev[b] < cap is the caller's contract as well (the kernels do not check the device array).
+ * Rounding points in both forms and every kernel behind them: scores (q scaled by head_dim^-0.5), softmax and P.V in fp32 -- the
+ * probabilities are NOT rounded -- and one rounding to the activation dtype at the store. */
+int simulst_decoder_self_attention_rows(simulst_handle* h, const void* qkv, void* k_cache, void* v_cache,
+                                        const int32_t* n_prev, int32_t np_uniform, const int32_t* row_map, void* ctx,
+                                        int32_t slots, int32_t H, int32_t d, int32_t cap, int32_t dtype);
+
 /* Monotonic cross-attention value aggregation for one decode step.
  * q [B][D] (soft-energy query = q_proj(x), the 1/sqrt(d) scaling is applied inside), Kc/Vc [B][H][S_cap][head_dim] (head-major) cached
  * projections of the encoder states, step [B*H] int64 = head_step after the search.
@@ -1077,8 +1092,10 @@ int simulst_policy_cross_attention(simulst_handle* h, const void* qm, const void
  * activations, fp32 MFMAs for fp32 activations; fp32 accumulation in both.  head_dim <= 64, B * H <= 65535.
  *
  * Causal self-attention: qkv [B][U][3D] -> ctx [B][U][D], query u attends keys 0 .. u (fairseq's buffered_future_mask; no
- * target padding mask, as in the reference).  Scores (q scaled by head_dim^-0.5) and softmax in fp32, P.V accumulated in fp32,
- * one rounding to the activation dtype: the rounding points of simulst_decoder_self_attention.  Keys are tiled with a running
+ * target padding mask, as in the reference).  Scores and softmax in fp32 (the fp32 scores are scaled by head_dim^-0.5 after the
+ * first product, so q enters it as given), P.V accumulated in fp32, one rounding to the activation dtype at the store.  With bf16
+ * activations the probabilities are ALSO rounded to bf16, as the A operand of the second product (the normaliser sums the unrounded
+ * exponentials): one rounding more than simulst_decoder_self_attention, which keeps P in fp32.  Keys are tiled with a running
  * maximum and sum, so U is not bounded by LDS. */
 int simulst_decoder_self_attention_causal(simulst_handle* h, const void* qkv, void* ctx, int32_t B, int32_t U, int32_t H,
                                           int32_t d, int32_t dtype);

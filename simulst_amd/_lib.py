@@ -173,6 +173,7 @@ SIGNATURES = {
     "simulst_cif_alpha_head": [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32],
     "simulst_embed_tokens": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32],
     "simulst_decoder_self_attention": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32],
+    "simulst_decoder_self_attention_rows": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32],
     "simulst_decoder_cross_attention": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
                                         _i32, _i32],
     "simulst_greedy_argmax": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32],

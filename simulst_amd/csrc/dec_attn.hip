@@ -214,9 +214,16 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const T* __restrict__ q
 extern "C" int simulst_decoder_self_attention(simulst_handle* h, const void* qkv, void* k_cache, void* v_cache,
                                               const int32_t* n_prev, void* ctx, int32_t B, int32_t H, int32_t d,
                                               int32_t cap, int32_t dtype) {
+  return simulst_decoder_self_attention_rows(h, qkv, k_cache, v_cache, n_prev, -1, nullptr, ctx, B, H, d, cap, dtype);
+}
+
+// the public face of sl_self_attention: the launch forms of the device loops (host-known lockstep position, active-row compaction)
+extern "C" int simulst_decoder_self_attention_rows(simulst_handle* h, const void* qkv, void* k_cache, void* v_cache,
+                                                   const int32_t* n_prev, int32_t np_uniform, const int32_t* row_map, void* ctx,
+                                                   int32_t slots, int32_t H, int32_t d, int32_t cap, int32_t dtype) {
   if (!h) return SIMULST_E_NULL;
-  SL_CHECK_NULL(h, n_prev);
-  return sl_self_attention(h, qkv, k_cache, v_cache, n_prev, -1, ctx, B, H, d, cap, dtype);
+  if (np_uniform < 0) SL_CHECK_NULL(h, n_prev);
+  return sl_self_attention(h, qkv, k_cache, v_cache, n_prev, np_uniform < 0 ? -1 : np_uniform, ctx, slots, H, d, cap, dtype, row_map);
 }
 
 int sl_self_attention(simulst_handle* h, const void* qkv, void* k_cache, void* v_cache, const int32_t* n_prev,

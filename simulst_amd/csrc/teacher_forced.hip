@@ -5,10 +5,10 @@
 // workgroup owns 64 query rows of one (utterance, head), each of its four waves a 16-row strip; operand tiles are staged in LDS as
 // [row][k] and a wave builds 16 x 16 output tiles with v_mfma_f32_16x16x32_bf16 (bf16 activations) or v_mfma_f32_16x16x4_f32 (fp32
 // activations: the matrix cores at full fp32 precision, so the fp32 pass agrees with the step kernels' fp32 dot products up to
-// summation order).  Accumulators are fp32 in both; the rounding points are those of the step kernels (dec_attn.hip): scores and
-// softmax in fp32, P . V accumulated in fp32, one rounding to the activation dtype at the store.  With bf16 activations the
-// probabilities are rounded to bf16 as the A operand of the second product, which is the reference's own `.type_as(q)` /
-// `beta.to(v.dtype)`.
+// summation order).  Accumulators are fp32 in both: scores and softmax in fp32 (q enters the first product as given; the fp32 scores
+// are scaled by head_dim^-0.5), P . V accumulated in fp32, one rounding to the activation dtype at the store.  With bf16 activations the
+// probabilities are ALSO rounded to bf16 as the A operand of the second product, which is the reference's own `.type_as(q)` /
+// `beta.to(v.dtype)` -- one rounding more than the step kernels (dec_attn.hip), which keep P in fp32.
 #include "policy_core.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -58,6 +58,7 @@ __device__ __forceinline__ float row16_sum(float v) {
 }
 
 // rows [r0, r0 + n_rows) x channels [0, d) of a [row][ld] global matrix -> LDS [n_rows][lds_ld], scaled, zero beyond row_end / d
+// (the scale is applied BEFORE the rounding to T: callers pass 1 unless that rounding is meant)
 template <typename T>
 __device__ __forceinline__ void stage_rows(T* dst, int lds_ld, const T* src, long ld, int r0, int n_rows, int row_end, int d,
                                            int dp, float scale) {
@@ -94,7 +95,9 @@ __global__ __launch_bounds__(256) void causal_self_attn_kernel(const T* __restri
   const int q0 = blockIdx.x * TF_ROWS, h = blockIdx.y, b = blockIdx.z;
   const int D = H * d, D3 = 3 * D, dp = (d + 31) & ~31, n_ct = (d + 15) >> 4;
   const T* base = qkv + (long)b * U * D3 + h * d;
-  stage_rows<T>(Qs, LDQ, base, D3, q0, TF_ROWS, U, d, dp, scale);
+  // q is staged as given and the fp32 scores are scaled below: head_dim^-0.5 is a power of two only at d = 16 and 64, and a scaled q
+  // rounded to bf16 here would be a second rounding of q (2^-9 of every score's terms) that the step kernels do not have
+  stage_rows<T>(Qs, LDQ, base, D3, q0, TF_ROWS, U, d, dp, 1.0f);
   f32x4 o[4];
   float m[4], l[4];
 #pragma unroll
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(256) void causal_self_attn_kernel(const T* __restri
       float mx = -INFINITY;
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
-        if (k0 + 16 * n + r > u) s[n][i] = -INFINITY;
+        s[n][i] = k0 + 16 * n + r > u ? -INFINITY : s[n][i] * scale;
         mx = fmaxf(mx, s[n][i]);
       }
       const float mt = fmaxf(m[i], row16_max(mx));       // key 0 is never in a query's future: finite from the first tile on
@@ -171,7 +174,7 @@ __global__ __launch_bounds__(256) void mma_energy_kernel(const T* __restrict__ q
   const int b = bh / H, h = bh - b * H, D = H * d, dp = (d + 31) & ~31;
   const int P = pooled_count(S, ratio, false, pool_last);
   const int len = key_len ? key_len[b] : S;
-  stage_rows<T>(Qs, LDQ, q + (long)b * U * D + h * d, D, u0, TF_ROWS, U, d, dp, scale);
+  stage_rows<T>(Qs, LDQ, q + (long)b * U * D + h * d, D, u0, TF_ROWS, U, d, dp, 1.0f);      // as given: the fp32 energies are scaled (see (a))
   const T* Kh = K + (long)bh * S_cap * d;
   for (int idx = threadIdx.x; idx < TF_KT * dp; idx += 256) {
     const int kj = idx / dp, c = idx - kj * dp;
@@ -199,7 +202,7 @@ __global__ __launch_bounds__(256) void mma_energy_kernel(const T* __restrict__ q
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      float v = e[i];
+      float v = e[i] * scale;
       if (monotonic) {
         v = masked ? -1e8f : v + bias;
         v = 1.0f / (1.0f + expf(-v));

@@ -444,6 +444,19 @@ class Ops:
                      "simulst_decoder_self_attention")
         return out
 
+    def decoder_self_attention_rows(self, qkv, k_cache, v_cache, n_prev=None, *, np_uniform=-1, row_map=None, out=None):
+        """simulst_decoder_self_attention_rows: qkv [slots, 3D] -> ctx [slots, D]; np_uniform >= 0 is the host-known position of
+        lockstep rows (n_prev may be None), row_map [slots] int32 names the stream row (caches, n_prev) of every slot, < 0 skips it"""
+        _chk_contig(qkv, k_cache, v_cache, n_prev, row_map, out)
+        _, H, cap, d = k_cache.shape
+        slots = qkv.shape[0]
+        if out is None:
+            out = torch.empty(slots, H * d, device=qkv.device, dtype=qkv.dtype)
+        self.h.check(self.lib.simulst_decoder_self_attention_rows(self.h.ptr, _p(qkv), _p(k_cache), _p(v_cache), _p(n_prev),
+                                                                  int(np_uniform), _p(row_map), _p(out), slots, H, d, cap, dt(qkv)),
+                     "simulst_decoder_self_attention_rows")
+        return out
+
     def decoder_cross_attention(self, q, Kc, Vc, step, *, H, attn_type, mass_preservation, key_len=None,
                                 want_beta=False, out=None):
         B, H_, S_cap, d = Vc.shape              # head-major [B, H, S_cap, head_dim]
