@@ -1014,17 +1014,28 @@ int simulst_cif_stream_append(simulst_handle* h, const void* out, const int32_t*
  *                = the self-attention output projection + residual of fairseq's TransformerDecoderLayer followed by
  *                encoder_attn_layer_norm and the (monotonic / soft) query projections of
  *                modules/monotonic_multihead_attention.py as run by models/mma_model.py:99-135
- *   ffn chain:   x' = bf16(x + Wco ctx + bco);  x <- bf16(x' + W2 gelu(W1 LN(x') + b1) + b2)
+ *   proj chain, kk form (simulst_decoder_proj_chain_kk):  x as above;  q <- bf16(gelu(Wq LN(x) + bq + kk)), exact (erf) GELU,
+ *                kk [B][256] bf16 required, bq may be NULL (taken as 0), no second projection
+ *                = the CIF decoder's FakeCrossAttn, activation(q_proj(query) + k_proj(key)) (models/cif_transformer.py:357-362):
+ *                the launch simulst_cif_decode makes, as an entry point of its own so that it can be checked alone
+ *   ffn chain:  x' = bf16(x + Wco ctx + bco);  x <- bf16(x' + W2 gelu(W1 LN(x') + b1) + b2)
  *                = encoder_attn out_proj + residual, final_layer_norm, fc1, activation, fc2, residual of the same layer.
  *                partial: fp32 [F / 256][B][D] slabs (one per 256 hidden units).  x_mid == NULL: the last-arriving
  *                workgroup of a row tile adds the slabs inside the launch (sem: (B + 15) / 16 int32, zero on entry, zero on
  *                return).  x_mid != NULL: x' is written to x_mid, x is left alone and the slabs are added by the following
  *                simulst_decoder_slab_sum_qkv (the form the decode loop uses: the launch boundary is the hand-off).
  *   slab sum:    x <- bf16(x_mid + b2 + slab 0 + slab 1 + ...) (split order: deterministic);  with wqkv_fm != NULL also
- *                qkv [B][3 D] <- Wqkv LN(x) + bqkv, the next layer's self_attn_layer_norm + q / k / v projections. */
+ *                qkv [B][3 D] <- Wqkv LN(x) + bqkv, the next layer's self_attn_layer_norm + q / k / v projections.
+ * LayerNorm here is eps 1e-5, biased variance, from one-pass moments in fp32 (E[x^2] - mean^2, clamped at 0).  Checked domain
+ * (tests/test_hip_dec_chain_fp64.py against float64): rows whose common offset is up to 32 standard deviations (worst |got - ref| /
+ * bound 0.46 there, 0.93 at 8), variance down to 1.5e-5 (the size of eps) and 0 (a constant row gives beta exactly), scale up to
+ * 2^6; the variance loses about (offset / deviation)^2 2^-19 of its relative accuracy, so far larger offsets are outside it. */
 int simulst_decoder_proj_chain(simulst_handle* h, const void* ctx, void* x, const void* wo_fm, const float* bo,
                                const float* ln_g, const float* ln_b, const void* wq_fm, const float* bq, void* q,
                                const void* wq2_fm, const float* bq2, void* q2, int32_t B, int32_t D, int32_t dtype);
+int simulst_decoder_proj_chain_kk(simulst_handle* h, const void* ctx, void* x, const void* wo_fm, const float* bo,
+                                  const float* ln_g, const float* ln_b, const void* wq_fm, const float* bq /* may be NULL */,
+                                  void* q, const void* kk /* [B][256], required */, int32_t B, int32_t D, int32_t dtype);
 int simulst_decoder_ffn_chain(simulst_handle* h, const void* ctx, void* x, const void* wco_fm, const float* bco,
                               const float* ln_g, const float* ln_b, const void* w1_fm, const float* b1, const void* w2_fm,
                               const float* b2, float* partial, int32_t* sem, void* x_mid, int32_t B, int32_t D, int32_t F,

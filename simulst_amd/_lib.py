@@ -193,6 +193,7 @@ SIGNATURES = {
     "simulst_cif_stream_steps": [_vp, C.POINTER(CifDecoderDesc), C.POINTER(CifDecLayer), _vp, C.POINTER(CifStreamCtl), _i32],
     "simulst_cif_stream_append": [_vp] * 8 + [_i32, _i32, _i32, _i32, C.c_float, _i32, _i32],
     "simulst_decoder_proj_chain": [_vp] * 13 + [_i32, _i32, _i32],
+    "simulst_decoder_proj_chain_kk": [_vp] * 11 + [_i32, _i32, _i32],
     "simulst_decoder_ffn_chain": [_vp] * 14 + [_i32, _i32, _i32, _i32],
     "simulst_decoder_slab_sum_qkv": [_vp] * 10 + [_i32, _i32, _i32, _i32],
     "simulst_decoder_vocab_chain": [_vp] * 9 + [_i32] * 7 + [_vp, _i32, _i32],

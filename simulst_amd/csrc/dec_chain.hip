@@ -1106,6 +1106,19 @@ extern "C" int simulst_decoder_proj_chain(simulst_handle* h, const void* ctx, vo
   return sl_dec_proj_chain(h, ctx, x, wo_fm, bo, ln_g, ln_b, wq_fm, bq, q, wq2_fm, bq2, q2, B, nullptr);
 }
 
+// the CIF form of the projection chain, q = gelu(Wq LN(x) + bq + kk): the form simulst_cif_decode launches (csrc/cif_decode.hip)
+extern "C" int simulst_decoder_proj_chain_kk(simulst_handle* h, const void* ctx, void* x, const void* wo_fm, const float* bo,
+                                             const float* ln_g, const float* ln_b, const void* wq_fm, const float* bq, void* q,
+                                             const void* kk, int32_t B, int32_t D, int32_t dtype) {
+  if (!h) return SIMULST_E_NULL;
+  SL_CHECK_NULL(h, ctx); SL_CHECK_NULL(h, x); SL_CHECK_NULL(h, wo_fm); SL_CHECK_NULL(h, bo); SL_CHECK_NULL(h, ln_g);
+  SL_CHECK_NULL(h, ln_b); SL_CHECK_NULL(h, wq_fm); SL_CHECK_NULL(h, q); SL_CHECK_NULL(h, kk);
+  SL_REQUIRE(h, dtype == SIMULST_BF16, SIMULST_E_DTYPE, "simulst_decoder_proj_chain_kk: bf16 only (fp32 keeps one launch per GEMM)");
+  SL_REQUIRE(h, D == CD && B >= 0, SIMULST_E_SHAPE, "simulst_decoder_proj_chain_kk: D == 256");
+  if (B == 0) return SIMULST_OK;
+  return sl_dec_proj_chain(h, ctx, x, wo_fm, bo, ln_g, ln_b, wq_fm, bq, q, nullptr, nullptr, nullptr, B, kk);
+}
+
 extern "C" int simulst_decoder_ffn_chain(simulst_handle* h, const void* ctx, void* x, const void* wco_fm, const float* bco,
                                          const float* ln_g, const float* ln_b, const void* w1_fm, const float* b1,
                                          const void* w2_fm, const float* b2, float* partial, int32_t* sem, void* x_mid,

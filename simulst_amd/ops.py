@@ -530,6 +530,17 @@ class Ops:
                      "simulst_decoder_proj_chain")
         return q, q2
 
+    def decoder_proj_chain_kk(self, ctx, x, wo_fm, bo, ln, wq_fm, bq, kk, q=None):
+        """x <- x + Wo ctx + bo (in place);  q = gelu(Wq LN(x) + bq + kk), bq may be None: the CIF decoder's form of the
+        projection chain in ONE launch (simulst_decoder_proj_chain_kk; bf16, D == 256, fragment-major weights)."""
+        B, D = x.shape
+        if q is None:
+            q = torch.empty_like(x)
+        self.h.check(self.lib.simulst_decoder_proj_chain_kk(self.h.ptr, _p(ctx), _p(x), _p(wo_fm), _p(bo), _p(ln[0]), _p(ln[1]),
+                                                            _p(wq_fm), _p(bq), _p(q), _p(kk), B, D, dt(x)),
+                     "simulst_decoder_proj_chain_kk")
+        return q
+
     def decoder_attn_proj_chain(self, qkv, k_cache, v_cache, n_prev, x, wo_fm, bo, ln, wq_fm, bq, q=None, wq2_fm=None, bq2=None,
                                 q2=None, kk_gelu=None, rows_per_workgroup=0, n_prev_uniform=-1):
         """self-attention over the caches [B][4][cap][64] (appending this step's k / v rows at n_prev) + x <- x + Wo ctx + bo +
@@ -577,12 +588,15 @@ class Ops:
                      "simulst_decoder_slab_sum_qkv")
         return qkv
 
-    def decoder_vocab_chain(self, x_mid, x, partial, b2, ln, wout_fm, V, split, skip_a=-1, skip_b=-1, row_bias=None, row_bias_col=-1):
+    def decoder_vocab_chain(self, x_mid, x, partial, b2, ln, wout_fm, V, split, skip_a=-1, skip_b=-1, row_bias=None, row_bias_col=-1,
+                            pairs=None):
         """x <- x_mid + b2 + sum of the slabs; pairs[row][s] = (largest logit, its lowest column) of Wout LN(x) over the s-th of
-        `split` column ranges (simulst_decoder_vocab_chain).  Returns (values [B, split] fp32, columns [B, split] int32)."""
+        `split` column ranges (simulst_decoder_vocab_chain).  Returns (values [B, split] fp32, columns [B, split] int32).
+        pairs: the [B, split, 2] fp32 buffer to write (default: a new one)."""
         B, D = x.shape
         F = partial.shape[0] * 256
-        pairs = torch.empty(B, split, 2, device=x.device, dtype=torch.float32)
+        if pairs is None:
+            pairs = torch.empty(B, split, 2, device=x.device, dtype=torch.float32)
         self.h.check(self.lib.simulst_decoder_vocab_chain(self.h.ptr, _p(x_mid), _p(x), _p(partial), _p(b2), _p(ln[0]), _p(ln[1]),
                                                           _p(wout_fm), _p(pairs), B, D, F, V, split, skip_a, skip_b, _p(row_bias),
                                                           row_bias_col, dt(x)),

@@ -70,6 +70,6 @@ def test_epilogue_7_is_still_unknown(handle):
 
 def test_no_new_entry_point_and_no_descriptor_change():
     from simulst_amd import _lib
-    assert len(_lib.SIGNATURES) == 80
+    assert len(_lib.SIGNATURES) == 81
     assert _lib.load().simulst_version() == 108 == _lib.ABI_VERSION
     assert ctypes.sizeof(_lib.LinearDesc) == 152

@@ -86,7 +86,7 @@ def test_descriptor_layout_and_pinned_counts():
     assert ctypes.sizeof(d) == 64
     assert [getattr(d, n).offset for n in ("cand_ids", "id_stride_b", "id_stride_t", "k", "pad", "cap", "lengths", "p_b", "p_nb")] == \
         [0, 8, 16, 24, 28, 32, 40, 48, 56]
-    assert len(_lib.SIGNATURES) == 80
+    assert len(_lib.SIGNATURES) == 81
     assert _lib.load().simulst_version() == 108 == _lib.ABI_VERSION
     assert ctypes.sizeof(_lib.LinearDesc) == 152
 

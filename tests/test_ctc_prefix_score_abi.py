@@ -95,6 +95,6 @@ def test_descriptor_layout_and_pinned_counts():
              "cand_lp", "cand_tok", "cand_slot", "finished", "next_tok", "reorder", "state_out", "psi_out", "last_out", "len_out", "result")
     assert [n for n, _ in d._fields_] == list(names)
     assert [getattr(d, n).offset for n in names] == [0, 4, 8, 12, 16, 20] + list(range(24, 160, 8))
-    assert len(_lib.SIGNATURES) == 80
+    assert len(_lib.SIGNATURES) == 81
     assert _lib.load().simulst_version() == 108 == _lib.ABI_VERSION
     assert ctypes.sizeof(_lib.LinearDesc) == 152 and ctypes.sizeof(_lib.CtcPrefixDesc) == 64

@@ -94,6 +94,6 @@ def test_sum_mode_of_ctc_best_alignment_on_host_buffers(handle):
 
 def test_no_new_entry_point_and_no_descriptor_change():
     from simulst_amd import _lib
-    assert len(_lib.SIGNATURES) == 80
+    assert len(_lib.SIGNATURES) == 81
     assert _lib.load().simulst_version() == 108 == _lib.ABI_VERSION
     assert ctypes.sizeof(_lib.LinearDesc) == 152

@@ -25,7 +25,7 @@ def test_declared_exported_and_bound():
         assert n in _lib.SIGNATURES and len(_lib.SIGNATURES[n]) == n_args and hasattr(lib, n)
     assert lib.simulst_version() == 108 == _lib.ABI_VERSION           # no descriptor structure changed
     # the library's entry points: 76 before these three
-    assert len(_lib.SIGNATURES) == 80 == len(re.findall(r"^\S+ T simulst_\w+$", exported, flags=re.M))
+    assert len(_lib.SIGNATURES) == 81 == len(re.findall(r"^\S+ T simulst_\w+$", exported, flags=re.M))
 
 
 @pytest.fixture
