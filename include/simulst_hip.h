@@ -716,6 +716,51 @@ typedef struct simulst_ctc_score_desc {
   int64_t* len_out;               /* commit: device int64 [N] */
   int32_t* result;                /* commit: device int32, + 1 per row whose token was not found */
 } simulst_ctc_score_desc;
+/* log_probs == NULL with max_target_length >= 0 (E_NULL "log_probs" before; simulst_version() stays 108): no probabilities are given,
+ * the call COMPARES label strings -- the batched Levenshtein alignment of N (reference, hypothesis) pairs in one launch
+ * (csrc/edit_distance.hip; DESIGN.md "CTC head", subsection "Error rates"), what the word error rate of the reference's ASR stage is
+ * summed from (tasks/speech_to_text_infer.py:206-215, :263-289).  The mode is recognised behind the two max_target_length < 0 modes,
+ * which answer as before, and before every other check; the arguments then mean
+ *   targets    int64: the REFERENCE strings, row r at r*tg_stride_b;  target_lengths int64 [n_ref]: their lengths
+ *   input_lengths  int64 [n_hyp]: the HYPOTHESIS lengths (the strings themselves are simulst_edit_desc.hyp)
+ *   max_target_length, S   the two capacities: no reference is longer than max_target_length, no hypothesis longer than S; both
+ *              0..1023 (E_SHAPE "1023" above it), the label limit of the other modes
+ *   N          the PAIRS (N <= 0: nothing is launched, OK).  Pair p compares reference row ref_idx[p] with hypothesis row hyp_idx[p];
+ *              a NULL index array means p.  Strings and lengths are read through the indices, in place: one reference can face 16
+ *              hypotheses, and a list can face itself (the same buffer on both sides)
+ *   out        the alignment `ops` [N][ops_cap], int8 or int32 (ops_width), or NULL (pointer presence): counts only
+ *   scratch    a HOST simulst_edit_desc (below), read during the call
+ *   lp_stride_*, blank, as_labels, neg_log_likelihood   ignored
+ * With D[i][j] the distance of the first i reference labels and the first j hypothesis labels, the predecessor of a cell is, among
+ * those that attain the minimum, the first of: the DIAGONAL (D[i-1][j-1]; a match if the labels are equal, else a substitution), a
+ * DELETION (D[i-1][j] + 1: reference label i has no counterpart), an INSERTION (D[i][j-1] + 1).  counts[p] = (distance, sub, del,
+ * ins), int32, the last three counted along the path from (Lr, Lh) back to (0, 0) under this rule; they are carried forward with the
+ * minimum, so the counts-only form writes 16 bytes a pair and reads nothing but the strings.  Empty strings are ordinary: distance Lh,
+ * Lr or 0.  Nothing at or past a length is read; rows no pair names are not touched.
+ * With `out`: ops[p][0 .. n_ops[p]) is that alignment front to back, 0 match, 1 substitution, 2 deletion, 3 insertion, `pad` behind
+ * it; n_ops[p] = Lr + ins <= ops_cap.  One-byte back-pointers go to `bp` (SIMULST_EDIT_BP_BYTES, 16-byte aligned), the back-track runs
+ * on the device.  A pair's counts do not depend on its position, on the other pairs, or on whether the path was asked for.
+ * A pair whose index is outside [0, n_ref) / [0, n_hyp), or whose string is longer than its capacity, reads no string: its counts are
+ * (-1, -1, -1, -1), n_ops 0, ops all `pad`.  With a NULL index array the host knows the indices: N above n_ref / n_hyp is E_SHAPE.
+ * Refusals, before any launch: E_NULL for a NULL scratch, targets, target_lengths, input_lengths, hyp, counts, and with `out` n_ops
+ * and bp (N > 0); E_SHAPE for a capacity above 1023 ("1023"), S < 0, ops_width other than 1 / 4, ops_cap < max_target_length + S,
+ * bp_bytes below SIMULST_EDIT_BP_BYTES; E_ARG for a misaligned bp. */
+#define SIMULST_EDIT_BP_BYTES(N, ref_cap, hyp_cap) ((int64_t)(N) * (((hyp_cap) + 63) / 64) * ((ref_cap) + 63) * 64)
+typedef struct simulst_edit_desc {
+  const int64_t* hyp;             /* device int64: the hypothesis strings, row r at r*hyp_stride_b */
+  int64_t hyp_stride_b;
+  const int32_t* ref_idx;         /* device int32 [N] or NULL (= p) */
+  const int32_t* hyp_idx;         /* device int32 [N] or NULL (= p) */
+  int32_t n_ref, n_hyp;           /* rows of the two sides: what an index is compared with */
+  int32_t* counts;                /* device int32 [N][4]: distance, sub, del, ins */
+  int32_t* n_ops;                 /* device int32 [N]; read only with `out` */
+  void* bp;                       /* device scratch for the back-pointers; read only with `out` */
+  int64_t bp_bytes;
+  int32_t ops_cap;                /* elements per row of `out`, >= max_target_length + S */
+  int32_t ops_width;              /* bytes per element of `out`: 1 (int8) or 4 (int32) */
+  int32_t pad;                    /* written behind each alignment */
+  int32_t reserved;               /* 0 */
+} simulst_edit_desc;
 int64_t simulst_ctc_best_alignment_scratch_bytes(int32_t N, int32_t S, int32_t max_target_length);
 int simulst_ctc_best_alignment(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
                                int64_t lp_stride_v, const int64_t* targets, int64_t tg_stride_b,

@@ -68,6 +68,22 @@ class CtcScoreDesc(C.Structure):
                                           "next_tok", "reorder", "state_out", "psi_out", "last_out", "len_out", "result")]
 
 
+class EditDesc(C.Structure):
+    """simulst_edit_desc: what the edit-distance mode of simulst_ctc_best_alignment (log_probs NULL, max_target_length >= 0) reads
+    through `scratch`"""
+    _fields_ = [("hyp", C.c_void_p), ("hyp_stride_b", C.c_int64), ("ref_idx", C.c_void_p), ("hyp_idx", C.c_void_p),
+                ("n_ref", C.c_int32), ("n_hyp", C.c_int32), ("counts", C.c_void_p), ("n_ops", C.c_void_p), ("bp", C.c_void_p),
+                ("bp_bytes", C.c_int64), ("ops_cap", C.c_int32), ("ops_width", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int32)]
+
+
+EDIT_MAX_LABELS = 1023
+
+
+def edit_bp_bytes(n_pairs: int, ref_cap: int, hyp_cap: int) -> int:
+    """SIMULST_EDIT_BP_BYTES: the back-pointer scratch of a path call"""
+    return n_pairs * ((hyp_cap + 63) // 64) * (ref_cap + 63) * 64
+
+
 CTC_PREFIX_STRING_BYTES = 141312          # SIMULST_CTC_PREFIX_STRING_BYTES
 
 

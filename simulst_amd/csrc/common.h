@@ -407,6 +407,11 @@ int sl_ctc_prefix_score(simulst_handle* h, const float* log_probs, int64_t lp_st
                         const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths, int32_t S, int32_t N,
                         int32_t K, int32_t blank, const void* desc);
 
+// the edit-distance mode of simulst_ctc_best_alignment (edit_distance.hip: log_probs == NULL with max_target_length >= 0), desc the
+// caller's simulst_edit_desc; makes every refusal of the mode itself
+int sl_edit_distance(simulst_handle* h, const int64_t* refs, int64_t ref_stride_b, const int64_t* hyp_lengths,
+                     const int64_t* ref_lengths, int32_t hyp_cap, int32_t N, int32_t ref_cap, const void* desc, void* ops);
+
 // beam-state reorder (beam.hip): the launch shared by simulst_beam_reorder (head_step: the layers' head_step / head_read move per
 // head) and simulst_transducer_beam_reorder (pe_src / pe_dst: one int32 per row moves); each front end makes its own refusals
 constexpr int SL_REORDER_MAX_LAYERS = 16;

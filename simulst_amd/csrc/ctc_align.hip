@@ -216,6 +216,8 @@ extern "C" int simulst_ctc_best_alignment(simulst_handle* h, const float* log_pr
   if (max_target_length < 0)
     return sl_ctc_prefix_beam(h, log_probs, lp_stride_t, lp_stride_b, lp_stride_v, input_lengths, S, N,
                               max_target_length < -17 ? 17 : -max_target_length, blank, scratch, out);   // (17: refused like any beam > 16)
+  // no probabilities: the call compares label strings (edit_distance.hip); targets are the references, `out` the optional alignment
+  if (!log_probs) return sl_edit_distance(h, targets, tg_stride_b, input_lengths, target_lengths, S, N, max_target_length, scratch, out);
   SL_CHECK_NULL(h, log_probs); SL_CHECK_NULL(h, targets); SL_CHECK_NULL(h, input_lengths); SL_CHECK_NULL(h, target_lengths);
   // out == NULL (the pointer-presence convention of simulst_rnnt_forward): the sum over alignments, which has no path to write
   if (!out) SL_CHECK_NULL(h, neg_log_likelihood);

@@ -24,6 +24,10 @@ every candidate of every step is scored by the CTC prefix probability of the ext
 and ``ctc_prefix_commit`` moves the chosen candidates' states behind the selection; both have a torch form (composed=True).
 
 The blank index is a keyword everywhere (default 0, the criterion's fallback, joint_ctc_criterion.py:76).
+
+``token_error_report`` counts the ERRORS of hypotheses against references (edit distance and its substitutions / deletions / insertions,
+summed over the batch on the device: simulst_amd/edit_distance.py, csrc/edit_distance.hip) where ``ctc_report`` counts bag-of-labels
+matches; ``CTCTranscriber.ctc_error_report`` runs it over the head's greedy transcript.
 """
 from typing import Dict, List, Optional
 
@@ -82,6 +86,21 @@ def ctc_report(path: torch.Tensor, lengths: Optional[torch.Tensor], target: torc
     recall = match / (target.ne(pad).sum(-1) + eps)
     precision = match / (path.ne(blank).sum(-1) + eps)
     return {"recall": recall.sum(), "precision": precision.sum(), "blank_rate": path.eq(blank).float().mean(-1).sum()}
+
+
+def token_error_report(tokens: torch.Tensor, n: torch.Tensor, target: torch.Tensor, target_lengths: torch.Tensor, *, ops=None,
+                       composed: bool = False) -> Dict[str, torch.Tensor]:
+    """The companion of ctc_report that counts ERRORS: tokens [B, L] with n [B] labels each (ctc_collapse's output, or any hypotheses)
+    against target [B, T] with target_lengths [B] -> the batch's SUMS {"errors", "sub", "del", "ins", "ref_labels"} as int64 scalars on
+    the tokens' device, with no host read-back.  errors / ref_labels is the token error rate (edit_distance.py: one launch over the
+    batch, the alignment's tie rule there); sums of several batches or ranks add (sharding.reduce_error_counts)."""
+    from .edit_distance import edit_distance, error_sums
+    target = target.to(device=tokens.device, dtype=torch.int64)
+    target_lengths = torch.as_tensor(target_lengths, device=tokens.device).to(torch.int64)
+    counts = edit_distance(ops, target, target_lengths, tokens.to(torch.int64), torch.as_tensor(n, device=tokens.device).to(torch.int64),
+                           composed=composed)
+    s = error_sums(counts, target_lengths)
+    return {"errors": s[0], "sub": s[1], "del": s[2], "ins": s[3], "ref_labels": s[4]}
 
 
 def ctc_greedy(ops, head_w: torch.Tensor, enc_btd: torch.Tensor, enc_len: torch.Tensor, *, blank: int = 0, pad: int = 1,
@@ -616,6 +635,12 @@ class CTCTranscriber:
         s = self.encoder.ctc_score(enc["encoder_out_btd"], enc["encoder_lengths"], tgt, n, blank=blank)
         nll, n = s["nll"].cpu(), n.cpu()
         return [{"nll": float(nll[b]), "score": -float(nll[b]) / max(int(n[b]), 1)} for b in range(nll.numel())]
+
+    def ctc_error_report(self, enc, targets, target_lengths, *, blank: int = 0) -> Dict[str, torch.Tensor]:
+        """Token errors of the head's greedy transcript over an encoder output (the dict encoder.forward returns) against targets
+        [B, T] / target_lengths [B]: ctc_greedy + ctc_collapse + token_error_report, sums on the device."""
+        g = self.encoder.ctc_greedy(enc["encoder_out_btd"], enc["encoder_lengths"], blank=blank)
+        return token_error_report(g["tokens"], g["n"], targets, target_lengths, ops=self.encoder.ops)
 
     def transcribe_ctc_nbest(self, src_tokens, src_lengths, *, beam: int = 8, nbest: int = 1, candidates: int = 8, blank: int = 0,
                              rescore: bool = True) -> List[List[dict]]:

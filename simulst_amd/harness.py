@@ -137,6 +137,97 @@ def corpus_bleu(hyps: Sequence[str], refs: Sequence[str], max_n: int = 4) -> flo
     return 100.0 * bp * math.exp(logp)
 
 
+class WerScorer:
+    """Word error rate as the reference's ASR stage reports it (tasks/speech_to_text_infer.py:206-215: fairseq's scoring.wer.WerScorer):
+    add_string(ref, pred) per sentence, then `distance` (summed edit distance over words), `ref_length` (summed reference words) and
+    score() = 100 * distance / ref_length (0 with no reference word).  Restated from the published class and UNPINNED like this
+    module's other scorers: fairseq, its editdistance dependency and sacrebleu are absent, so nothing here is checked against them.
+
+    Text processing is fairseq's EvaluationTokenizer, in its order: the tokenizer (only "none" is built; "13a" is sacrebleu's and
+    raises), wer_remove_punct (drop the whitespace-separated tokens made only of Unicode category-P characters), wer_char_level (one
+    token per character, a space becoming U+2581), wer_lowercase.
+
+    The distance is simulst_amd.edit_distance: the sentences added since the last read of a result are mapped to word ids with ONE
+    dictionary and go through ONE edit_distance call -- on `device` when it names a HIP device that is present, else (device=None, no
+    GPU) the composed host form, which gives the same integers.  `counts` holds the sums (errors, sub, del, ins, ref_words)."""
+
+    def __init__(self, wer_tokenizer: str = "none", wer_lowercase: bool = False, wer_remove_punct: bool = False,
+                 wer_char_level: bool = False, device=None, ops=None):
+        if wer_tokenizer != "none":
+            raise NotImplementedError(f"WerScorer: wer_tokenizer={wer_tokenizer!r} is sacrebleu's tokenizer, which is not available here; "
+                                      "only \"none\" is built")
+        self.lowercase, self.remove_punct, self.char_level = wer_lowercase, wer_remove_punct, wer_char_level
+        self.device, self.ops = device, ops
+        self.reset()
+
+    def reset(self):
+        self._sums = [0, 0, 0, 0, 0]
+        self._pending = []
+
+    def tokenize(self, sent: str) -> List[str]:
+        import unicodedata
+        if self.remove_punct:
+            sent = " ".join(t for t in sent.split(" ") if not all(unicodedata.category(c)[0] == "P" for c in t))
+        if self.char_level:
+            sent = " ".join(list(sent.replace(" ", BOW_PREFIX)))
+        if self.lowercase:
+            sent = sent.lower()
+        return sent.split()
+
+    def add_string(self, ref: str, pred: str):
+        self._pending.append((self.tokenize(ref), self.tokenize(pred)))
+
+    def _flush(self):
+        if not self._pending:
+            return
+        import torch
+        from .edit_distance import edit_distance, error_sums
+        pairs, self._pending = self._pending, []
+        ids = {}
+        n = len(pairs)
+        wr, wh = max(max(len(r) for r, _ in pairs), 1), max(max(len(h) for _, h in pairs), 1)
+        ref, hyp = torch.zeros(n, wr, dtype=torch.int64), torch.zeros(n, wh, dtype=torch.int64)
+        for p, (r, h) in enumerate(pairs):
+            ref[p, :len(r)] = torch.tensor([ids.setdefault(w, len(ids)) for w in r], dtype=torch.int64)
+            hyp[p, :len(h)] = torch.tensor([ids.setdefault(w, len(ids)) for w in h], dtype=torch.int64)
+        rl, hl = torch.tensor([len(r) for r, _ in pairs]), torch.tensor([len(h) for _, h in pairs])
+        on_gpu = self.device is not None and torch.device(self.device).type == "cuda" and torch.cuda.is_available()
+        if on_gpu:
+            ref, hyp, rl, hl = (t.to(self.device) for t in (ref, hyp, rl, hl))
+        counts = edit_distance(self.ops, ref, rl, hyp, hl, composed=not on_gpu)
+        for k, v in enumerate(error_sums(counts, rl).tolist()):
+            self._sums[k] += int(v)
+
+    @property
+    def counts(self):
+        self._flush()
+        return dict(zip(("errors", "sub", "del", "ins", "ref_words"), self._sums))
+
+    @property
+    def distance(self) -> int:
+        self._flush()
+        return self._sums[0]
+
+    @property
+    def ref_length(self) -> int:
+        self._flush()
+        return self._sums[4]
+
+    def score(self) -> float:
+        return 100.0 * self.distance / self.ref_length if self.ref_length > 0 else 0
+
+    def result_string(self) -> str:
+        return f"WER: {self.score():.2f}"
+
+
+def corpus_wer(hyps: Sequence[str], refs: Sequence[str], **opts) -> float:
+    """WerScorer over a corpus: 100 * summed word edit distance / summed reference words (opts: WerScorer's)"""
+    scorer = WerScorer(**opts)
+    for h, r in zip(hyps, refs):
+        scorer.add_string(r, h)
+    return scorer.score()
+
+
 def run_instance(agent, fbank, tgt_dict: Dictionary, index: int = 0, reference: Optional[str] = None):
     """One utterance through `agent` (agent.FairseqSimulSTAgent) with word merging and SimulEval-style logging:
     delays / elapsed are per emitted WORD (the server's unit), stamped when units_to_segment releases it."""
@@ -185,10 +276,16 @@ def run_instance(agent, fbank, tgt_dict: Dictionary, index: int = 0, reference: 
             "metric": {"latency": latency_scores(delays, elapsed, src.total_ms())}}
 
 
-def corpus_scores(instances, references: Optional[Sequence[str]] = None):
-    """docs/mma.md:44-56 schema: averages of the per-instance latency metrics (+ BLEU when references are given)."""
+def corpus_scores(instances, references: Optional[Sequence[str]] = None, wer: bool = False, **wer_opts):
+    """docs/mma.md:44-56 schema: averages of the per-instance latency metrics (+ BLEU when references are given; with wer=True also
+    "WER" under "Quality", corpus_wer with wer_opts -- the key is absent unless asked for)."""
     keys = ("AL", "AL_CA", "AP", "AP_CA", "DAL", "DAL_CA")
     n = max(len(instances), 1)
     lat = {k: sum(i["metric"]["latency"][k] for i in instances) / n for k in keys}
     bleu = corpus_bleu([i["prediction"] for i in instances], references) if references is not None else None
-    return {"Quality": {"BLEU": bleu}, "Latency": lat}
+    quality = {"BLEU": bleu}
+    if wer:
+        if references is None:
+            raise ValueError("corpus_scores: wer=True needs references")
+        quality["WER"] = corpus_wer([i["prediction"] for i in instances], references, **wer_opts)
+    return {"Quality": quality, "Latency": lat}

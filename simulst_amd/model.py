@@ -175,6 +175,48 @@ class SimulSTModel(FairseqModelSurface, CTCTranscriber):
                                                                   ctc=self.ctc_scorer(enc, beam=beam, ctc_weight=ctc_weight, blank=blank))
         return hypotheses(toks, lengths, scores, pos)
 
+    def evaluate_wer(self, src_tokens, src_lengths, references, tgt_dict, *, beam=5, ctc_weight=0.0, post_process="sentencepiece",
+                     **wer_opts):
+        """The validation step of the reference's ASR task with eval_wer (tasks/speech_to_text_infer.py:176-215): beam search (generate's,
+        with its ctc_weight), the best hypothesis and the reference of every sentence turned into text by tgt_dict.string(tokens,
+        post_process), and harness.WerScorer(**wer_opts) over them.  references: one token list per sentence (EOS and padding are
+        dropped), or a [B, L] tensor padded with the model's padding index.  Returns the reference's logging keys {"w_errors",
+        "wv_errors", "w_total"} (ints; sum them over batches and ranks -- sharding.reduce_error_counts -- and divide once), the
+        TOKEN-level sums of ctc.token_error_report over the same hypotheses as 0-d device tensors {"t_errors", "t_sub", "t_del",
+        "t_ins", "t_total"} (no read-back: the hypotheses never leave the device for them), and the texts {"hyps", "refs"}.
+        (The reference escapes <unk> in the reference text so that it matches nothing; the dictionaries here carry no unknown word.)"""
+        from .ctc import token_error_report
+        from .harness import WerScorer
+        cfg = self.cfg
+        if not 0.0 <= float(ctc_weight) <= 1.0:
+            raise ValueError(f"ctc_weight must be in [0, 1], got {ctc_weight}")
+        if torch.is_tensor(references):
+            references = [[int(t) for t in row if int(t) != cfg.padding_idx] for row in references.tolist()]
+        refs = [[int(t) for t in r if int(t) not in (cfg.eos, cfg.padding_idx)] for r in references]
+        B = len(refs)
+        assert B == src_tokens.size(0), "one reference per sentence"
+        enc = self.encoder.forward(src_tokens, src_lengths)
+        max_len = [self.target_cap(int(t)) for t in torch.as_tensor(src_lengths).tolist()]
+        toks, lengths, _, _, _ = self.decoder.beam_offline(enc["encoder_out_btd"], enc["encoder_lengths"], max_len, beam=beam, nbest=1,
+                                                           ctc=self.ctc_scorer(enc, beam=beam, ctc_weight=ctc_weight))
+        hyp, n = toks[:, 0], lengths[:, 0].to(torch.int64)
+        last = hyp.gather(1, (n - 1).clamp(min=0).unsqueeze(1))[:, 0]
+        n = n - ((n > 0) & (last == cfg.eos)).to(torch.int64)                 # the closing EOS is no label of the transcript
+        tgt = torch.full((B, max(max((len(r) for r in refs), default=0), 1)), cfg.padding_idx, dtype=torch.int64)
+        for b, r in enumerate(refs):
+            tgt[b, :len(r)] = torch.tensor(r, dtype=torch.int64)
+        tl = torch.tensor([len(r) for r in refs], dtype=torch.int64)
+        t = token_error_report(hyp, n, tgt.to(hyp.device), tl.to(hyp.device), ops=self.ops)
+        hyp_c, n_c = hyp.cpu(), n.cpu()
+        hyps = [tgt_dict.string(hyp_c[b, :int(n_c[b])].tolist(), post_process) for b in range(B)]
+        ref_text = [tgt_dict.string(r, post_process) for r in refs]
+        scorer = WerScorer(device=hyp.device, ops=self.ops, **wer_opts)
+        for h, r in zip(hyps, ref_text):
+            scorer.add_string(r, h)
+        return {"w_errors": scorer.distance, "wv_errors": scorer.distance, "w_total": scorer.ref_length,
+                "t_errors": t["errors"], "t_sub": t["sub"], "t_del": t["del"], "t_ins": t["ins"], "t_total": t["ref_labels"],
+                "hyps": hyps, "refs": ref_text}
+
     def score_reference(self, src_tokens, src_lengths, targets, *, return_alignments=False):
         """eval/generate.py --score-reference (fairseq's SequenceScorer): the encoder once, then ONE decoder pass over
         [eos] + target[:-1] of every sentence (MMADecoder.forward_teacher_forced).  targets: one EOS-terminated token list per

@@ -771,6 +771,65 @@ class Ops:
                                                    _p(best_ll), _p(emit), _p(backptr), B, S, U1), "simulst_rnnt_forward")
         return (ll, best_ll, emit) if want_best else ll
 
+    # ------------------------------------------------------------------ error rates (csrc/edit_distance.hip)
+    def edit_distance(self, ref, ref_len, hyp, hyp_len, *, ref_idx=None, hyp_idx=None, n_pairs=None, path=False, pad=-1,
+                      ops_dtype=torch.int8, ref_cap=None, hyp_cap=None):
+        """The edit-distance mode of simulst_ctc_best_alignment: ref [Rr, >= ref_cap] / hyp [Rh, >= hyp_cap] int64 label strings (rows
+        contiguous, any row stride; the same tensor may be both), ref_len [Rr] / hyp_len [Rh] int64, ref_idx / hyp_idx int32 [N] or
+        None (pair p is rows p, p) -> counts int32 [N, 4] = (distance, sub, del, ins); with path also (ops [N, ref_cap + hyp_cap] in
+        ops_dtype -- 0 match, 1 substitution, 2 deletion, 3 insertion, `pad` behind --, n_ops int32 [N]).  The capacities default to the
+        tensors' widths, at most 1023.  No read-back."""
+        import ctypes
+        for t in (ref, hyp, ref_len, hyp_len):
+            if t.dtype != torch.int64:
+                raise TypeError("edit_distance: strings and lengths are int64")
+        for t in (ref, hyp):
+            if t.dim() != 2 or (t.size(1) > 1 and t.stride(1) != 1):
+                raise ValueError("edit_distance: strings are [rows, labels] with contiguous rows")
+        _chk_contig(ref_len, hyp_len, ref_idx, hyp_idx)
+        if ref_len.numel() != ref.size(0) or hyp_len.numel() != hyp.size(0):
+            raise ValueError("edit_distance: one length per row")
+        for t in (ref_idx, hyp_idx):
+            if t is not None and t.dtype != torch.int32:
+                raise TypeError("edit_distance: indices are int32")
+        if n_pairs is None:
+            n_pairs = ref_idx.numel() if ref_idx is not None else hyp_idx.numel() if hyp_idx is not None else ref.size(0)
+        N = int(n_pairs)
+        for t in (ref_idx, hyp_idx):
+            if t is not None and t.numel() != N:
+                raise ValueError("edit_distance: one index per pair")
+        ref_cap = ref.size(1) if ref_cap is None else int(ref_cap)
+        hyp_cap = hyp.size(1) if hyp_cap is None else int(hyp_cap)
+        if ref_cap > ref.size(1) or hyp_cap > hyp.size(1):
+            raise ValueError("edit_distance: a capacity above the strings' width")
+        dev = ref.device
+        if ref.size(1) == 0:                                       # (an empty tensor has no address to pass)
+            ref = torch.zeros(max(ref.size(0), 1), 1, device=dev, dtype=torch.int64)[:ref.size(0)]
+        if hyp.size(1) == 0:
+            hyp = torch.zeros(max(hyp.size(0), 1), 1, device=dev, dtype=torch.int64)[:hyp.size(0)]
+        counts = torch.empty(N, 4, device=dev, dtype=torch.int32)
+        if N == 0:
+            return (counts, torch.empty(0, max(ref_cap + hyp_cap, 1), device=dev, dtype=ops_dtype),
+                    torch.empty(0, device=dev, dtype=torch.int32)) if path else counts
+        d = _lib.EditDesc()
+        d.hyp, d.hyp_stride_b = hyp.data_ptr(), hyp.stride(0)
+        d.ref_idx = ref_idx.data_ptr() if ref_idx is not None else None
+        d.hyp_idx = hyp_idx.data_ptr() if hyp_idx is not None else None
+        d.n_ref, d.n_hyp, d.counts, d.pad = ref.size(0), hyp.size(0), counts.data_ptr(), int(pad)
+        out = n_ops = bp = None
+        if path:
+            if ops_dtype not in (torch.int8, torch.int32):
+                raise TypeError("edit_distance: ops are int8 or int32")
+            cap = max(ref_cap + hyp_cap, 1)
+            out = torch.empty(N, cap, device=dev, dtype=ops_dtype)
+            n_ops = torch.empty(N, device=dev, dtype=torch.int32)
+            bp = torch.empty(max(_lib.edit_bp_bytes(N, ref_cap, hyp_cap), 16), device=dev, dtype=torch.uint8)
+            d.n_ops, d.bp, d.bp_bytes, d.ops_cap, d.ops_width = n_ops.data_ptr(), bp.data_ptr(), bp.numel(), cap, out.element_size()
+        self.h.check(self.lib.simulst_ctc_best_alignment(self.h.ptr, _p(None), 0, 0, 0, _p(ref), ref.stride(0), _p(hyp_len), _p(ref_len),
+                                                         hyp_cap, N, ref_cap, 0, 0, ctypes.addressof(d), _p(out), _p(None)),
+                     "simulst_ctc_best_alignment (edit distance)")
+        return (counts, out, n_ops) if path else counts
+
     # ------------------------------------------------------------------ beam search (csrc/beam.hip)
     def beam_topk(self, logits, max_len, finished, cand_lp, cand_tok, *, beam, step, pad_idx, eos_idx):
         _chk_contig(logits, max_len, finished, cand_lp, cand_tok)

@@ -5,7 +5,9 @@ The reference shards evaluation data as independent dataset shards with no colle
 utterances are sorted by length and dealt round-robin to ranks (balances the summed frames per
 rank), every rank holds a full weight replica and decodes its shard, and ONE all_gather of
 fixed-width hypothesis records brings the results together (RCCL over xGMI when the backend is
-"nccl"; gloo in the CPU tests).  There is no data-path collective.
+"nccl"; gloo in the CPU tests).  There is no data-path collective.  Error rates are the one other thing that
+crosses ranks: `reduce_error_counts` sums the integer error counters in one all_reduce, as the reference's
+reduce_metrics does (tasks/speech_to_text_infer.py:263-289).
 """
 from typing import List, Sequence
 
@@ -32,6 +34,23 @@ def gather_hypotheses(tokens: torch.Tensor, dist, group=None) -> torch.Tensor:
     out = torch.empty((world,) + tuple(tokens.shape), device=tokens.device, dtype=tokens.dtype)
     dist.all_gather_into_tensor(out.view(world * tokens.shape[0], *tokens.shape[1:]), tokens, group=group)
     return out.view(world * tokens.shape[0], *tokens.shape[1:])
+
+
+def reduce_error_counts(counts, dist, group=None):
+    """ONE all_reduce (sum) of integer error counters over the ranks: counts is a dict of integers / integer scalars tensors (the
+    reference's logging keys w_errors / wv_errors / w_total, or ctc.token_error_report's sums) or an integer tensor; the same kind comes
+    back with every value summed (dict values as 0-d int64 tensors on the counters' device).  An error rate is computed from the
+    REDUCED sums -- errors / total -- and never as an average of per-rank rates, which would weigh a short shard like a long one."""
+    if isinstance(counts, dict):
+        keys = list(counts)
+        dev = next((v.device for v in counts.values() if torch.is_tensor(v)), torch.device("cpu"))
+        buf = torch.stack([torch.as_tensor(counts[k], device=dev).to(torch.int64).reshape(()) for k in keys])
+    else:
+        if counts.is_floating_point():
+            raise TypeError("reduce_error_counts: integer counters (a rate is made after the sum)")
+        keys, buf = None, counts.to(torch.int64).clone()
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return buf if keys is None else {k: buf[i] for i, k in enumerate(keys)}
 
 
 def gather_records(utt_ids: torch.Tensor, n_tok: torch.Tensor, tokens: torch.Tensor, delays_ms: torch.Tensor,
