@@ -606,7 +606,8 @@ int simulst_pack_fragment_major(simulst_handle* h, const void* W, void* out, int
  * reference's CUDA kernel (criterion/best_alignment/best_alignment.cu:58-187) together with the final-state choice,
  * back-tracking and optional label translation its Python wrapper does (criterion/best_alignment/__init__.py:56-111).
  *   log_probs  fp32, element (t, b, v) at t*lp_stride_t + b*lp_stride_b + v*lp_stride_v (after log_softmax)
- *   targets    int64 [N][>= max_target_length], row stride tg_stride_b;  input_lengths / target_lengths int64 [N]
+ *   targets    int64 [N][>= max_target_length], row stride tg_stride_b;  input_lengths / target_lengths int64 [N];
+ *              max_target_length 0..1023 (E_SHAPE "shape" below 0, "1023" above)
  *   out        int64 [N][S]: CTC state in [0, 2T+1) per frame (as_labels: the label, blank for even states);
  *              frames >= input_lengths[b] get state 0 / blank, as the reference returns
  *   scratch    simulst_ctc_best_alignment_scratch_bytes(N, S, max_target_length) bytes (1-byte back-pointers)
@@ -616,25 +617,25 @@ int simulst_pack_fragment_major(simulst_handle* h, const void* W, void* out, int
  * (E_NULL) and receives the true CTC negative log-likelihood of each utterance -- F.ctc_loss(reduction="none"),
  * criterion/joint_ctc_criterion.py:78-90: the same state recursion with log-add over the legal predecessors in place of max (s-2 only
  * between different labels), -log of the two final states' sum, +inf when no alignment exists (never NaN), T = 0 the sum of the
- * blanks.  No back-pointers: scratch is not read and may be NULL; as_labels is ignored; the 1023-label limit is the same.  The
- * arguments existed before with a refused value, so simulst_version() stays 108.
- *
- * max_target_length < 0 (refused as "shape" before; simulst_version() stays 108): no transcript is given, the call SEARCHES for it --
- * every frame of the time-synchronous CTC prefix beam search over per-frame candidate lists in one launch (csrc/ctc_prefix.hip), the
- * recursion simulst_amd/ctc.py ctc_prefix_beam_advance spells out, with its pool order and tie rule.  The mode is recognised before any
- * other check; the arguments then mean
- *   beam       = -max_target_length, 1..16 (E_SHAPE "beam" otherwise)
- *   log_probs  the CANDIDATES' log-probabilities, fp32, element (t, b, j) at t*lp_stride_t + b*lp_stride_b + j*lp_stride_v, j = 0..k;
- *              slot 0 is the blank
+ * blanks.  No back-pointers: scratch is not read and may be NULL; as_labels is ignored; the 1023-label limit is the same. */
+int64_t simulst_ctc_best_alignment_scratch_bytes(int32_t N, int32_t S, int32_t max_target_length);
+int simulst_ctc_best_alignment(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
+                               int64_t lp_stride_v, const int64_t* targets, int64_t tg_stride_b,
+                               const int64_t* input_lengths, const int64_t* target_lengths, int32_t S, int32_t N,
+                               int32_t max_target_length, int32_t blank, int32_t as_labels, void* scratch,
+                               int64_t* out, float* neg_log_likelihood);
+
+/* CTC prefix beam search: every frame of the time-synchronous search over per-frame candidate lists in one launch
+ * (csrc/ctc_prefix.hip), the recursion simulst_amd/ctc.py ctc_prefix_beam_advance spells out, with its pool order and tie rule.
+ *   cand_log_probs  the CANDIDATES' log-probabilities, fp32, element (t, b, j) at t*lp_stride_t + b*lp_stride_b + j*lp_stride_v,
+ *              j = 0..k; slot 0 is the blank
  *   input_lengths  int64 [N]: the frames of this call to take of utterance b, t = 0 .. min(S, input_lengths[b]) - 1; with none
  *              (<= 0) the utterance's state is not touched, bit for bit.  Candidates of frames at and past it are not read
- *   S          the frames in the call (S > 0 as in the other modes);  N utterances (N <= 0: nothing is launched, OK)
- *   out        int64 [N][beam][cap]: the beam's strings, read at entry and written at exit, `pad` behind each length and in dead slots
- *   scratch    a HOST simulst_ctc_prefix_desc (below), read during the call like simulst_linear_desc
- *   blank      >= 0 as before; informational (the blank is candidate slot 0 by construction)
- *   targets, target_lengths, as_labels, neg_log_likelihood   ignored; may be NULL
+ *   S          the frames in the call (S > 0);  N utterances (N <= 0: nothing is launched, OK);  beam 1..16 (E_SHAPE otherwise)
+ *   strings    int64 [N][beam][cap]: the beam's strings, read at entry and written at exit, `pad` behind each length and in dead slots
+ *   desc       a HOST simulst_ctc_prefix_desc (below), read during the call;  blank >= 0, informational (the blank is candidate slot 0)
  * State of utterance b and beam slot i (in / out): lengths[b][i], p_b[b][i], p_nb[b][i] (log-probability of the prefix ending in a
- * blank / in its last label) and the string out[b][i][:lengths].  Slots are in descending order of p_b (+) p_nb; a dead slot is
+ * blank / in its last label) and the string strings[b][i][:lengths].  Slots are in descending order of p_b (+) p_nb; a dead slot is
  * (-inf, -inf), length 0, all `pad`.  Per frame and live prefix l with last label e, lp the frame's candidate log-probabilities:
  *   p_b'(l) = (p_b (+) p_nb) + lp[blank];   p_nb'(l) = p_nb + lp[e] if e is a candidate;
  *   p_nb'(l + c) = p_b + lp[c] if c == e else (p_b (+) p_nb) + lp[c]        for every candidate c >= 0 (candidates of a frame are distinct)
@@ -646,8 +647,8 @@ int simulst_pack_fragment_major(simulst_handle* h, const void* W, void* out, int
  * The strings stay in LDS for the call (int32, two buffers), which bounds the capacity: cap <= SIMULST_CTC_PREFIX_CAP(beam) -- 1104
  * labels at beam 16, 2208 at beam 8.  The caller provides cap >= the longest length at entry + the frames taken (a string grows by at
  * most one label a frame; a label that would not fit is dropped).
- * Refusals, before any launch: E_NULL for a NULL scratch, out, log_probs, input_lengths, cand_ids, lengths, p_b or p_nb; E_SHAPE for
- * S <= 0 or blank < 0 ("shape"), beam > 16 ("beam"), k outside 0..8 ("k"), cap < 1 or above the limit ("cap"). */
+ * Refusals, before any launch: E_NULL for a NULL desc, strings, cand_log_probs, input_lengths, cand_ids, lengths, p_b or p_nb; E_SHAPE
+ * for S <= 0 or blank < 0 ("shape"), beam outside 1..16 ("beam is"), k outside 0..8 ("k is"), cap < 1 or above the limit ("cap is") */
 #define SIMULST_CTC_PREFIX_STRING_BYTES 141312                                        /* LDS for the two string buffers: 138 KB */
 #define SIMULST_CTC_PREFIX_CAP(beam) ((SIMULST_CTC_PREFIX_STRING_BYTES / (8 * (beam))) & ~3)
 typedef struct simulst_ctc_prefix_desc {
@@ -656,42 +657,43 @@ typedef struct simulst_ctc_prefix_desc {
   int64_t id_stride_b, id_stride_t;
   int32_t k;                      /* non-blank candidates per frame, 0..8 */
   int32_t pad;                    /* label written behind each string and into dead slots */
-  int32_t cap;                    /* labels per string of `out` */
+  int32_t cap;                    /* labels per string of `strings` */
   int64_t* lengths;               /* device int64 [N][beam], in / out */
   float* p_b;                     /* device fp32 [N][beam], in / out */
   float* p_nb;                    /* device fp32 [N][beam], in / out */
 } simulst_ctc_prefix_desc;
-/* max_target_length < 0 AND targets != NULL (the search mode ignores targets and its callers pass NULL; simulst_version() stays 108):
- * the call SCORES the candidates of one step of the attention beam search by their CTC prefix probability, or commits the step's
- * selection (csrc/ctc_prefix_score.hip; DESIGN.md "Beam search", subsection "CTC prefix scores inside the beam").  The mode is
- * recognised before the search mode's own checks; the arguments then mean
- *   K          = -max_target_length, 1..32: the candidates of a row (2 * beam)
+int simulst_ctc_prefix_beam(simulst_handle* h, const float* cand_log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
+                            int64_t lp_stride_v, const int64_t* input_lengths, int32_t S, int32_t N, int32_t beam, int32_t blank,
+                            const simulst_ctc_prefix_desc* desc, int64_t* strings);
+
+/* CTC prefix scores inside the attention beam search: the call scores the candidates of one step by their CTC prefix probability, or
+ * commits the step's selection (csrc/ctc_prefix_score.hip; DESIGN.md "Beam search", subsection "CTC prefix scores inside the beam").
+ *   K          1..32: the candidates of a row (2 * beam)
  *   N          beam rows r = s * G + j of N / G sentences (N <= 0: nothing is launched, OK);  S the frames of the buffers
- *   log_probs  the CANDIDATES' log-probabilities under the CTC head, fp32: element (t, s, j * K + k) at t*lp_stride_t + s*lp_stride_b
- *              + (j * K + k)*lp_stride_v -- simulst_linear's SIMULST_EPI_ROW_GATHER over cand_tok viewed as [N / G][G * K]
- *   targets    int64 [N]: the last label of each row's hypothesis (not read where the prefix is empty)
- *   target_lengths  int64 [N]: the labels of each row's hypothesis, 0 = the empty prefix
+ *   cand_log_probs  the CANDIDATES' log-probabilities under the CTC head, fp32: element (t, s, j * K + k) at t*lp_stride_t +
+ *              s*lp_stride_b + (j * K + k)*lp_stride_v -- simulst_linear's SIMULST_EPI_ROW_GATHER over cand_tok viewed as [N / G][G * K]
+ *   last_labels     int64 [N]: the last label of each row's hypothesis (not read where the prefix is empty).  Both are read by op 0 alone
+ *   prefix_lengths  int64 [N]: the labels of each row's hypothesis, 0 = the empty prefix
  *   input_lengths   int64 [N]: the frames T of each row, cut to S; frames at and past T are not read
- *   scratch    a HOST simulst_ctc_score_desc (below), read during the call
- *   blank      >= 0: a candidate equal to it, to pad, or negative has psi = -inf
- *   tg_stride_b, as_labels, out, neg_log_likelihood   ignored; may be 0 / NULL
+ *   desc       a HOST simulst_ctc_score_desc (below), read during the call;  blank >= 0: a candidate equal to it, to pad, or negative
+ *              has psi = -inf
  * op 0, score (one launch, a wave per row, a lane per candidate; rows of finished sentences, and with first_only the rows j > 0, are
  * not touched).  The row's state is gn[t], gb[t] (state [N][S][2]: log-probability of the alignments of frames 0..t that spell the
  * hypothesis g and end in its last label / in a blank) and psi [N].  For a candidate c that is a label, e the last label of g:
  *   phi[t] = gb[t] if c == e else gn[t] (+) gb[t];  phi[-1] = 0 for the empty g, else -inf;  gn'[-1] = gb'[-1] = -inf
  *   gn'[t] = (gn'[t-1] (+) phi[t-1]) + x[t][c];  gb'[t] = (gn'[t-1] (+) gb'[t-1]) + x[t][blank];  psi(g c) = (+)_t (phi[t-1] + x[t][c])
- * (psi(g c) = -inf with T = 0); for c == eos psi = gn[T-1] (+) gb[T-1] (T = 0: 0 for the empty g, else -inf).  (+) as in the search
- * mode.  delta = -1e4 if psi(h) is -inf, else max(psi(h) - psi(g), -1e4); the candidate's score becomes cand_lp unchanged where it is
- * -inf or weight == 0, else (1 - weight) cand_lp + weight delta.  Outputs: cand_state [N][S][K][2] (gn', gb' of lane k; -inf for a
- * candidate that is no label), cand_psi [N][K], and cand_lp / cand_tok REWRITTEN IN PLACE in candidate order (descending score, equal
- * scores to the lower token) with cand_slot [N][K] = the slot each entry came from (the k of cand_state / cand_psi).  A candidate's
- * result does not depend on its slot, its row or the other candidates.
+ * (psi(g c) = -inf with T = 0); for c == eos psi = gn[T-1] (+) gb[T-1] (T = 0: 0 for the empty g, else -inf).  (+) as in
+ * simulst_ctc_prefix_beam.  delta = -1e4 if psi(h) is -inf, else max(psi(h) - psi(g), -1e4); the candidate's score becomes cand_lp
+ * unchanged where it is -inf or weight == 0, else (1 - weight) cand_lp + weight delta.  Outputs: cand_state [N][S][K][2] (gn', gb' of
+ * lane k; -inf for a candidate that is no label), cand_psi [N][K], and cand_lp / cand_tok REWRITTEN IN PLACE in candidate order
+ * (descending score, equal scores to the lower token) with cand_slot [N][K] = the slot each entry came from (the k of cand_state /
+ * cand_psi).  A candidate's result does not depend on its slot, its row or the other candidates.
  * op 1, commit (behind simulst_beam_select): row r of an unfinished sentence takes cand_state / cand_psi of candidate next_tok[r] of
- * row reorder[r] into state_out [N][S][2] / psi_out [N], with last_out[r] = next_tok[r] and len_out[r] = target_lengths[reorder[r]] + 1.
+ * row reorder[r] into state_out [N][S][2] / psi_out [N], with last_out[r] = next_tok[r] and len_out[r] = prefix_lengths[reorder[r]] + 1.
  * A parent outside the row's sentence or a token that is not among the parent's candidates adds 1 to *result and leaves the row.
- * Refusals, before any launch: E_NULL for a NULL scratch, targets, target_lengths, input_lengths, cand_state, cand_psi, cand_tok,
- * cand_slot, and for op 0 log_probs, blank_lp, state, psi, cand_lp, for op 1 next_tok, reorder, state_out, psi_out, last_out, len_out,
- * result; E_SHAPE for K outside 1..32, G < 1, S <= 0, blank < 0, an op other than 0 / 1, N not a multiple of G. */
+ * Refusals, before any launch: E_NULL for a NULL desc, prefix_lengths, input_lengths, cand_state, cand_psi, cand_tok, cand_slot, and
+ * for op 0 last_labels, cand_log_probs, blank_lp, state, psi, cand_lp, for op 1 next_tok, reorder, state_out, psi_out, last_out,
+ * len_out, result; E_SHAPE for K outside 1..32, G < 1, S <= 0, blank < 0, an op other than 0 / 1, N not a multiple of G. */
 typedef struct simulst_ctc_score_desc {
   int32_t op;                     /* 0 = score, 1 = commit */
   int32_t G;                      /* rows per sentence (the beam) */
@@ -716,35 +718,35 @@ typedef struct simulst_ctc_score_desc {
   int64_t* len_out;               /* commit: device int64 [N] */
   int32_t* result;                /* commit: device int32, + 1 per row whose token was not found */
 } simulst_ctc_score_desc;
-/* log_probs == NULL with max_target_length >= 0 (E_NULL "log_probs" before; simulst_version() stays 108): no probabilities are given,
- * the call COMPARES label strings -- the batched Levenshtein alignment of N (reference, hypothesis) pairs in one launch
- * (csrc/edit_distance.hip; DESIGN.md "CTC head", subsection "Error rates"), what the word error rate of the reference's ASR stage is
- * summed from (tasks/speech_to_text_infer.py:206-215, :263-289).  The mode is recognised behind the two max_target_length < 0 modes,
- * which answer as before, and before every other check; the arguments then mean
- *   targets    int64: the REFERENCE strings, row r at r*tg_stride_b;  target_lengths int64 [n_ref]: their lengths
- *   input_lengths  int64 [n_hyp]: the HYPOTHESIS lengths (the strings themselves are simulst_edit_desc.hyp)
- *   max_target_length, S   the two capacities: no reference is longer than max_target_length, no hypothesis longer than S; both
- *              0..1023 (E_SHAPE "1023" above it), the label limit of the other modes
+int simulst_ctc_prefix_score(simulst_handle* h, const float* cand_log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
+                             int64_t lp_stride_v, const int64_t* last_labels, const int64_t* input_lengths, const int64_t* prefix_lengths,
+                             int32_t S, int32_t N, int32_t K, int32_t blank, const simulst_ctc_score_desc* desc);
+
+/* Batched edit distance: the call compares label strings -- the batched Levenshtein alignment of N (reference, hypothesis) pairs in
+ * one launch (csrc/edit_distance.hip; DESIGN.md "CTC head", subsection "Error rates"), what the word error rate of the reference's
+ * ASR stage is summed from (tasks/speech_to_text_infer.py:206-215, :263-289).  desc: a HOST simulst_edit_desc (below), read during the call
+ *   refs       int64: the REFERENCE strings, row r at r*ref_stride_b;  ref_lengths int64 [n_ref]: their lengths
+ *   hyp_lengths  int64 [n_hyp]: the HYPOTHESIS lengths (the strings themselves are simulst_edit_desc.hyp)
+ *   ref_cap, hyp_cap   the two capacities: no reference is longer than ref_cap, no hypothesis longer than hyp_cap; both 0..1023
+ *              (E_SHAPE "1023" above it), the label limit of simulst_ctc_best_alignment
  *   N          the PAIRS (N <= 0: nothing is launched, OK).  Pair p compares reference row ref_idx[p] with hypothesis row hyp_idx[p];
  *              a NULL index array means p.  Strings and lengths are read through the indices, in place: one reference can face 16
  *              hypotheses, and a list can face itself (the same buffer on both sides)
- *   out        the alignment `ops` [N][ops_cap], int8 or int32 (ops_width), or NULL (pointer presence): counts only
- *   scratch    a HOST simulst_edit_desc (below), read during the call
- *   lp_stride_*, blank, as_labels, neg_log_likelihood   ignored
+ *   ops        the alignment [N][ops_cap], int8 or int32 (ops_width), or NULL (pointer presence): counts only
  * With D[i][j] the distance of the first i reference labels and the first j hypothesis labels, the predecessor of a cell is, among
  * those that attain the minimum, the first of: the DIAGONAL (D[i-1][j-1]; a match if the labels are equal, else a substitution), a
  * DELETION (D[i-1][j] + 1: reference label i has no counterpart), an INSERTION (D[i][j-1] + 1).  counts[p] = (distance, sub, del,
  * ins), int32, the last three counted along the path from (Lr, Lh) back to (0, 0) under this rule; they are carried forward with the
  * minimum, so the counts-only form writes 16 bytes a pair and reads nothing but the strings.  Empty strings are ordinary: distance Lh,
  * Lr or 0.  Nothing at or past a length is read; rows no pair names are not touched.
- * With `out`: ops[p][0 .. n_ops[p]) is that alignment front to back, 0 match, 1 substitution, 2 deletion, 3 insertion, `pad` behind
+ * With `ops`: ops[p][0 .. n_ops[p]) is that alignment front to back, 0 match, 1 substitution, 2 deletion, 3 insertion, `pad` behind
  * it; n_ops[p] = Lr + ins <= ops_cap.  One-byte back-pointers go to `bp` (SIMULST_EDIT_BP_BYTES, 16-byte aligned), the back-track runs
  * on the device.  A pair's counts do not depend on its position, on the other pairs, or on whether the path was asked for.
  * A pair whose index is outside [0, n_ref) / [0, n_hyp), or whose string is longer than its capacity, reads no string: its counts are
  * (-1, -1, -1, -1), n_ops 0, ops all `pad`.  With a NULL index array the host knows the indices: N above n_ref / n_hyp is E_SHAPE.
- * Refusals, before any launch: E_NULL for a NULL scratch, targets, target_lengths, input_lengths, hyp, counts, and with `out` n_ops
- * and bp (N > 0); E_SHAPE for a capacity above 1023 ("1023"), S < 0, ops_width other than 1 / 4, ops_cap < max_target_length + S,
- * bp_bytes below SIMULST_EDIT_BP_BYTES; E_ARG for a misaligned bp. */
+ * Refusals, before any launch: E_NULL for a NULL desc, refs, ref_lengths, hyp_lengths, hyp, counts, and with `ops` n_ops and bp
+ * (N > 0); E_SHAPE for a capacity above 1023 ("1023") or below 0, ops_width other than 1 / 4, ops_cap < ref_cap + hyp_cap, bp_bytes
+ * below SIMULST_EDIT_BP_BYTES; E_ARG for a misaligned bp. */
 #define SIMULST_EDIT_BP_BYTES(N, ref_cap, hyp_cap) ((int64_t)(N) * (((hyp_cap) + 63) / 64) * ((ref_cap) + 63) * 64)
 typedef struct simulst_edit_desc {
   const int64_t* hyp;             /* device int64: the hypothesis strings, row r at r*hyp_stride_b */
@@ -753,20 +755,16 @@ typedef struct simulst_edit_desc {
   const int32_t* hyp_idx;         /* device int32 [N] or NULL (= p) */
   int32_t n_ref, n_hyp;           /* rows of the two sides: what an index is compared with */
   int32_t* counts;                /* device int32 [N][4]: distance, sub, del, ins */
-  int32_t* n_ops;                 /* device int32 [N]; read only with `out` */
-  void* bp;                       /* device scratch for the back-pointers; read only with `out` */
+  int32_t* n_ops;                 /* device int32 [N]; read only with `ops` */
+  void* bp;                       /* device scratch for the back-pointers; read only with `ops` */
   int64_t bp_bytes;
-  int32_t ops_cap;                /* elements per row of `out`, >= max_target_length + S */
-  int32_t ops_width;              /* bytes per element of `out`: 1 (int8) or 4 (int32) */
+  int32_t ops_cap;                /* elements per row of `ops`, >= ref_cap + hyp_cap */
+  int32_t ops_width;              /* bytes per element of `ops`: 1 (int8) or 4 (int32) */
   int32_t pad;                    /* written behind each alignment */
   int32_t reserved;               /* 0 */
 } simulst_edit_desc;
-int64_t simulst_ctc_best_alignment_scratch_bytes(int32_t N, int32_t S, int32_t max_target_length);
-int simulst_ctc_best_alignment(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
-                               int64_t lp_stride_v, const int64_t* targets, int64_t tg_stride_b,
-                               const int64_t* input_lengths, const int64_t* target_lengths, int32_t S, int32_t N,
-                               int32_t max_target_length, int32_t blank, int32_t as_labels, void* scratch,
-                               int64_t* out, float* neg_log_likelihood);
+int simulst_edit_distance(simulst_handle* h, const int64_t* refs, int64_t ref_stride_b, const int64_t* ref_lengths,
+                          const int64_t* hyp_lengths, int32_t ref_cap, int32_t hyp_cap, int32_t N, const simulst_edit_desc* desc, void* ops);
 
 /* ---- whole decode steps on the device ----------------------------------------------
  * Runs n_steps consecutive WRITE steps of the MMA / wait-k decoder for a batch in lockstep with no

@@ -53,15 +53,14 @@ _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 
 class CtcPrefixDesc(C.Structure):
-    """simulst_ctc_prefix_desc: what the search mode of simulst_ctc_best_alignment (max_target_length < 0) reads through `scratch`"""
+    """simulst_ctc_prefix_desc: what simulst_ctc_prefix_beam reads through `desc`"""
     _fields_ = [("cand_ids", C.c_void_p), ("id_stride_b", C.c_int64), ("id_stride_t", C.c_int64),
                 ("k", C.c_int32), ("pad", C.c_int32), ("cap", C.c_int32),
                 ("lengths", C.c_void_p), ("p_b", C.c_void_p), ("p_nb", C.c_void_p)]
 
 
 class CtcScoreDesc(C.Structure):
-    """simulst_ctc_score_desc: what the scoring mode of simulst_ctc_best_alignment (max_target_length < 0 with targets) reads through
-    `scratch`"""
+    """simulst_ctc_score_desc: what simulst_ctc_prefix_score reads through `desc`"""
     _fields_ = [("op", C.c_int32), ("G", C.c_int32), ("eos", C.c_int32), ("pad", C.c_int32), ("weight", C.c_float),
                 ("first_only", C.c_int32), ("blank_lp", C.c_void_p), ("blank_stride_b", C.c_int64)] + \
                [(n, C.c_void_p) for n in ("state", "psi", "cand_state", "cand_psi", "cand_lp", "cand_tok", "cand_slot", "finished",
@@ -69,8 +68,7 @@ class CtcScoreDesc(C.Structure):
 
 
 class EditDesc(C.Structure):
-    """simulst_edit_desc: what the edit-distance mode of simulst_ctc_best_alignment (log_probs NULL, max_target_length >= 0) reads
-    through `scratch`"""
+    """simulst_edit_desc: what simulst_edit_distance reads through `desc`"""
     _fields_ = [("hyp", C.c_void_p), ("hyp_stride_b", C.c_int64), ("ref_idx", C.c_void_p), ("hyp_idx", C.c_void_p),
                 ("n_ref", C.c_int32), ("n_hyp", C.c_int32), ("counts", C.c_void_p), ("n_ops", C.c_void_p), ("bp", C.c_void_p),
                 ("bp_bytes", C.c_int64), ("ops_cap", C.c_int32), ("ops_width", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int32)]
@@ -88,7 +86,7 @@ CTC_PREFIX_STRING_BYTES = 141312          # SIMULST_CTC_PREFIX_STRING_BYTES
 
 
 def ctc_prefix_cap(beam: int) -> int:
-    """SIMULST_CTC_PREFIX_CAP(beam): the longest strings the search mode keeps on chip"""
+    """SIMULST_CTC_PREFIX_CAP(beam): the longest strings simulst_ctc_prefix_beam keeps on chip"""
     return (CTC_PREFIX_STRING_BYTES // (8 * beam)) & ~3
 
 
@@ -160,6 +158,9 @@ SIGNATURES = {
     "simulst_ctc_best_alignment_scratch_bytes": [_i32, _i32, _i32],
     "simulst_ctc_best_alignment": [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
                                    _vp, _vp],
+    "simulst_ctc_prefix_beam": [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, C.POINTER(CtcPrefixDesc), _vp],
+    "simulst_ctc_prefix_score": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(CtcScoreDesc)],
+    "simulst_edit_distance": [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, C.POINTER(EditDesc), _vp],
     "simulst_fbank": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32],
     "simulst_conv_pos_mfma": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32],
     "simulst_emformer_pack_rows": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32],

@@ -284,6 +284,13 @@ __device__ __forceinline__ float wave_last(float v) {        // lane 63's value 
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// log(e^a + e^b) of the CTC prefix kernels: max + log1p(exp(-|a - b|)) with the accurate expf / log1pf, -inf when both are
+__device__ __forceinline__ float lae(float a, float b) {
+  const float m = fmaxf(a, b);
+  if (m == -INFINITY) return -INFINITY;
+  return m + log1pf(expf(-fabsf(a - b)));
+}
+
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 // GELU for bf16 outputs: x*Phi(x) = h + |h| - |h| * erfc(|x|/sqrt2), h = x/2 (no cancellation on the negative side), with
 //   erfc(|h| sqrt2) = exp2(Q(|h|)),  Q(a) = a (c1 + a (c2 + a (c3 + a (c4 + a c5))))
@@ -394,23 +401,6 @@ int sl_self_attention_fused(simulst_handle* h, const void* x, const float* ln_g,
                             const float* bqkv, const void* Wo, void* k_cache, void* v_cache, const int32_t* n_prev,
                             int np_uniform, float* partial, int32_t B, int32_t H, int32_t d, int32_t cap,
                             int32_t dtype);
-
-// the search mode of simulst_ctc_best_alignment (ctc_prefix.hip): beam = -max_target_length, desc the caller's simulst_ctc_prefix_desc;
-// makes every refusal of the mode itself
-int sl_ctc_prefix_beam(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b, int64_t lp_stride_v,
-                       const int64_t* input_lengths, int32_t S, int32_t N, int32_t beam, int32_t blank, const void* desc,
-                       int64_t* out);
-
-// the scoring mode of simulst_ctc_best_alignment (ctc_prefix_score.hip: max_target_length < 0 with targets): K = -max_target_length, desc
-// the caller's simulst_ctc_score_desc; makes every refusal of the mode itself
-int sl_ctc_prefix_score(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b, int64_t lp_stride_v,
-                        const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths, int32_t S, int32_t N,
-                        int32_t K, int32_t blank, const void* desc);
-
-// the edit-distance mode of simulst_ctc_best_alignment (edit_distance.hip: log_probs == NULL with max_target_length >= 0), desc the
-// caller's simulst_edit_desc; makes every refusal of the mode itself
-int sl_edit_distance(simulst_handle* h, const int64_t* refs, int64_t ref_stride_b, const int64_t* hyp_lengths,
-                     const int64_t* ref_lengths, int32_t hyp_cap, int32_t N, int32_t ref_cap, const void* desc, void* ops);
 
 // beam-state reorder (beam.hip): the launch shared by simulst_beam_reorder (head_step: the layers' head_step / head_read move per
 // head) and simulst_transducer_beam_reorder (pe_src / pe_dst: one int32 per row moves); each front end makes its own refusals

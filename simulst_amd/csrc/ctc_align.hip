@@ -208,16 +208,6 @@ extern "C" int simulst_ctc_best_alignment(simulst_handle* h, const float* log_pr
                                           int32_t max_target_length, int32_t blank, int32_t as_labels, void* scratch,
                                           int64_t* out, float* neg_log_likelihood) {
   if (!h) return SIMULST_E_NULL;
-  // max_target_length < 0: no transcript is given, the call searches for it (ctc_prefix.hip); targets / target_lengths may be NULL
-  // ... and with targets (which the search ignores: its callers pass NULL) it scores the candidates of a beam step (ctc_prefix_score.hip)
-  if (max_target_length < 0 && targets)
-    return sl_ctc_prefix_score(h, log_probs, lp_stride_t, lp_stride_b, lp_stride_v, targets, input_lengths, target_lengths, S, N,
-                               max_target_length < -33 ? 33 : -max_target_length, blank, scratch);   // (33: refused like any K > 32)
-  if (max_target_length < 0)
-    return sl_ctc_prefix_beam(h, log_probs, lp_stride_t, lp_stride_b, lp_stride_v, input_lengths, S, N,
-                              max_target_length < -17 ? 17 : -max_target_length, blank, scratch, out);   // (17: refused like any beam > 16)
-  // no probabilities: the call compares label strings (edit_distance.hip); targets are the references, `out` the optional alignment
-  if (!log_probs) return sl_edit_distance(h, targets, tg_stride_b, input_lengths, target_lengths, S, N, max_target_length, scratch, out);
   SL_CHECK_NULL(h, log_probs); SL_CHECK_NULL(h, targets); SL_CHECK_NULL(h, input_lengths); SL_CHECK_NULL(h, target_lengths);
   // out == NULL (the pointer-presence convention of simulst_rnnt_forward): the sum over alignments, which has no path to write
   if (!out) SL_CHECK_NULL(h, neg_log_likelihood);

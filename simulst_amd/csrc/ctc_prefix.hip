@@ -1,5 +1,5 @@
 // CTC prefix beam search for gfx950: every frame of the time-synchronous recursion of simulst_amd/ctc.py ctc_prefix_beam_advance for a
-// batch in ONE launch -- the search mode of simulst_ctc_best_alignment (max_target_length < 0, include/simulst_hip.h).
+// batch in ONE launch -- simulst_ctc_prefix_beam (include/simulst_hip.h).
 //
 // One workgroup of ONE wave per utterance: a frame is a chain of small dependent steps over at most 16 prefixes and 16 + 16 * 8 = 144
 // pool entries, so a second wave would only add barriers.  The wave keeps
@@ -31,12 +31,6 @@ constexpr int PB_FB = 32;                                                      /
 constexpr int PB_STAGE = PB_FB * (PB_K + 1);
 constexpr int PB_PER_LANE = (PB_STAGE + 63) / 64;
 constexpr int PB_STATIC_LDS = 6144;                                            // bound on the static arrays below (checked)
-
-__device__ __forceinline__ float lae(float a, float b) {     // log(e^a + e^b): max + log1p(exp(-|a - b|)), -inf when both are
-  const float m = fmaxf(a, b);
-  if (m == -INFINITY) return -INFINITY;
-  return m + log1pf(expf(-fabsf(a - b)));
-}
 
 __device__ __forceinline__ unsigned mix(int pos, int label) {
   unsigned x = ((unsigned)(pos + 1) * 0x9E3779B1u) ^ (((unsigned)label + 0x7F4A7C15u) * 0x85EBCA6Bu);
@@ -320,27 +314,28 @@ __global__ __launch_bounds__(64) void ctc_prefix_kernel(const float* __restrict_
 
 }  // namespace
 
-int sl_ctc_prefix_beam(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b, int64_t lp_stride_v,
-                       const int64_t* input_lengths, int32_t S, int32_t N, int32_t beam, int32_t blank, const void* desc,
-                       int64_t* out) {
+extern "C" int simulst_ctc_prefix_beam(simulst_handle* h, const float* cand_log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
+                                       int64_t lp_stride_v, const int64_t* input_lengths, int32_t S, int32_t N, int32_t beam,
+                                       int32_t blank, const simulst_ctc_prefix_desc* desc, int64_t* strings) {
+  if (!h) return SIMULST_E_NULL;
   SL_CHECK_NULL(h, desc);
-  const simulst_ctc_prefix_desc* d = static_cast<const simulst_ctc_prefix_desc*>(desc);
-  SL_CHECK_NULL(h, out); SL_CHECK_NULL(h, log_probs); SL_CHECK_NULL(h, input_lengths);
+  const simulst_ctc_prefix_desc* d = desc;
+  SL_CHECK_NULL(h, strings); SL_CHECK_NULL(h, cand_log_probs); SL_CHECK_NULL(h, input_lengths);
   SL_CHECK_NULL(h, d->cand_ids); SL_CHECK_NULL(h, d->lengths); SL_CHECK_NULL(h, d->p_b); SL_CHECK_NULL(h, d->p_nb);
-  SL_REQUIRE(h, S > 0 && blank >= 0, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (prefix beam): shape");
-  SL_REQUIRE(h, beam >= 1 && beam <= PB_BEAM, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (prefix beam): beam = -max_target_length is 1..16");
-  SL_REQUIRE(h, d->k >= 0 && d->k <= PB_K, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (prefix beam): k is 0..8");
+  SL_REQUIRE(h, S > 0 && blank >= 0, SIMULST_E_SHAPE, "simulst_ctc_prefix_beam: shape");
+  SL_REQUIRE(h, beam >= 1 && beam <= PB_BEAM, SIMULST_E_SHAPE, "simulst_ctc_prefix_beam: beam is 1..16");
+  SL_REQUIRE(h, d->k >= 0 && d->k <= PB_K, SIMULST_E_SHAPE, "simulst_ctc_prefix_beam: k is 0..8");
   SL_REQUIRE(h, d->cap >= 1 && d->cap <= SIMULST_CTC_PREFIX_CAP(beam), SIMULST_E_SHAPE,
-             "simulst_ctc_best_alignment (prefix beam): cap is 1..SIMULST_CTC_PREFIX_CAP(beam)");
+             "simulst_ctc_prefix_beam: cap is 1..SIMULST_CTC_PREFIX_CAP(beam)");
   if (N <= 0) return SIMULST_OK;
   const size_t lds = (size_t)2 * beam * ((d->cap + 3) & ~3) * sizeof(int);
   static_assert(SIMULST_CTC_PREFIX_STRING_BYTES + PB_STATIC_LDS <= 160 * 1024, "LDS of a compute unit");
   static const sl_lds_limit limits[] = {{(const void*)ctc_prefix_kernel, SIMULST_CTC_PREFIX_STRING_BYTES}};
   if (lds + PB_STATIC_LDS > 48 * 1024)
-    if (int rc = sl_raise_lds(h, SL_LDS_CTC_PREFIX, limits, "simulst_ctc_best_alignment (prefix beam)")) return rc;
+    if (int rc = sl_raise_lds(h, SL_LDS_CTC_PREFIX, limits, "simulst_ctc_prefix_beam")) return rc;
   KTimer t(h, SIMULST_K_SCAN);
-  hipLaunchKernelGGL(ctc_prefix_kernel, dim3(N), dim3(64), lds, h->stream, log_probs, (long)lp_stride_t, (long)lp_stride_b,
+  hipLaunchKernelGGL(ctc_prefix_kernel, dim3(N), dim3(64), lds, h->stream, cand_log_probs, (long)lp_stride_t, (long)lp_stride_b,
                      (long)lp_stride_v, d->cand_ids, (long)d->id_stride_b, (long)d->id_stride_t, (const long*)input_lengths, S, beam,
-                     d->k, d->cap, d->pad, (long*)out, (long*)d->lengths, d->p_b, d->p_nb);
-  return sl_launch_status(h, "simulst_ctc_best_alignment (prefix beam)");
+                     d->k, d->cap, d->pad, (long*)strings, (long*)d->lengths, d->p_b, d->p_nb);
+  return sl_launch_status(h, "simulst_ctc_prefix_beam");
 }

@@ -1,6 +1,5 @@
-// CTC prefix scores inside the attention beam search (joint CTC / attention decoding) for gfx950 -- the scoring mode of
-// simulst_ctc_best_alignment (max_target_length < 0 and targets != NULL, include/simulst_hip.h; DESIGN.md "Beam search", "CTC prefix
-// scores inside the beam").
+// CTC prefix scores inside the attention beam search (joint CTC / attention decoding) for gfx950 --
+// simulst_ctc_prefix_score (include/simulst_hip.h; DESIGN.md "Beam search", "CTC prefix scores inside the beam").
 //
 // ctc_prefix_score_kernel, once per beam step: ONE wave per beam row r = s * G + j, ONE lane per candidate (K <= 32).  Lane k extends
 // the row's hypothesis g by its candidate c and runs the prefix-score recursion over the sentence's frames, serially, in fp32:
@@ -24,12 +23,6 @@ constexpr int PS_KMAX = 32;                          // candidates of a row: one
 constexpr int PS_FB = 32;                            // frames staged at a time
 constexpr int PS_PER_LANE = PS_FB * PS_KMAX / 64;
 constexpr float PS_FLOOR = -1.0e4f;                  // the CTC term of an extension no alignment spells
-
-__device__ __forceinline__ float ps_lae(float a, float b) {  // log(e^a + e^b): max + log1p(exp(-|a - b|)), -inf when both are
-  const float m = fmaxf(a, b);
-  if (m == -INFINITY) return -INFINITY;
-  return m + log1pf(expf(-fabsf(a - b)));
-}
 
 struct ps_shared {
   float x[PS_FB * PS_KMAX];                          // [frame][candidate], K floats a frame
@@ -94,15 +87,15 @@ __global__ __launch_bounds__(64) void ctc_prefix_score_kernel(const float* __res
       const int idx = lane + 64 * u;
       if (idx < PS_FB * K) sh.x[idx] = rx[u];
     }
-    if (lane < PS_FB) { sh.gb[lane] = rst.y; sh.tot[lane] = ps_lae(rst.x, rst.y); sh.xb[lane] = rxb; }
+    if (lane < PS_FB) { sh.gb[lane] = rst.y; sh.tot[lane] = lae(rst.x, rst.y); sh.xb[lane] = rxb; }
     __syncthreads();
     if (t0 + PS_FB < T) prefetch(t0 + PS_FB);
     const int t1 = T - t0 < PS_FB ? T - t0 : PS_FB;
     for (int f = 0; f < t1; ++f) {
       const float x = ext ? sh.x[f * K + lane] : -INFINITY;
-      const float gn = ps_lae(pn, phi) + x;
-      const float gb = ps_lae(pn, pb) + sh.xb[f];
-      acc = ps_lae(acc, phi + x);
+      const float gn = lae(pn, phi) + x;
+      const float gb = lae(pn, pb) + sh.xb[f];
+      acc = lae(acc, phi + x);
       if (own) out[(long)(t0 + f) * K + lane] = make_float2(gn, gb);
       phi = same ? sh.gb[f] : sh.tot[f];
       pn = gn;
@@ -115,7 +108,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_score_kernel(const float* __res
   float psi_h = -INFINITY;
   if (ext) psi_h = acc;
   else if (!special && tok == eos) {
-    if (T > 0) { const float2 st = str[T - 1]; psi_h = ps_lae(st.x, st.y); }
+    if (T > 0) { const float2 st = str[T - 1]; psi_h = lae(st.x, st.y); }
     else psi_h = empty ? 0.f : -INFINITY;
   }
   cand_psi[(long)r * K + lane] = psi_h;
@@ -171,37 +164,38 @@ __global__ __launch_bounds__(64) void ctc_prefix_commit_kernel(const float* __re
 
 }  // namespace
 
-int sl_ctc_prefix_score(simulst_handle* h, const float* log_probs, int64_t lp_stride_t, int64_t lp_stride_b, int64_t lp_stride_v,
-                        const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths, int32_t S, int32_t N,
-                        int32_t K, int32_t blank, const void* desc) {
-  const char* who = "simulst_ctc_best_alignment (prefix score)";
+extern "C" int simulst_ctc_prefix_score(simulst_handle* h, const float* cand_log_probs, int64_t lp_stride_t, int64_t lp_stride_b,
+                                        int64_t lp_stride_v, const int64_t* last_labels, const int64_t* input_lengths,
+                                        const int64_t* prefix_lengths, int32_t S, int32_t N, int32_t K, int32_t blank,
+                                        const simulst_ctc_score_desc* desc) {
+  if (!h) return SIMULST_E_NULL;
   SL_CHECK_NULL(h, desc);
-  const simulst_ctc_score_desc* d = static_cast<const simulst_ctc_score_desc*>(desc);
-  SL_CHECK_NULL(h, targets); SL_CHECK_NULL(h, target_lengths); SL_CHECK_NULL(h, input_lengths);
+  const simulst_ctc_score_desc* d = desc;
+  SL_CHECK_NULL(h, prefix_lengths); SL_CHECK_NULL(h, input_lengths);
   SL_CHECK_NULL(h, d->cand_state); SL_CHECK_NULL(h, d->cand_psi); SL_CHECK_NULL(h, d->cand_tok); SL_CHECK_NULL(h, d->cand_slot);
-  SL_REQUIRE(h, d->op == 0 || d->op == 1, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (prefix score): op is 0 (score) or 1 (commit)");
+  SL_REQUIRE(h, d->op == 0 || d->op == 1, SIMULST_E_SHAPE, "simulst_ctc_prefix_score: op is 0 (score) or 1 (commit)");
   if (d->op == 0) {
-    SL_CHECK_NULL(h, log_probs); SL_CHECK_NULL(h, d->blank_lp); SL_CHECK_NULL(h, d->state); SL_CHECK_NULL(h, d->psi);
-    SL_CHECK_NULL(h, d->cand_lp);
+    SL_CHECK_NULL(h, last_labels); SL_CHECK_NULL(h, cand_log_probs); SL_CHECK_NULL(h, d->blank_lp); SL_CHECK_NULL(h, d->state);
+    SL_CHECK_NULL(h, d->psi); SL_CHECK_NULL(h, d->cand_lp);
   } else {
     SL_CHECK_NULL(h, d->next_tok); SL_CHECK_NULL(h, d->reorder); SL_CHECK_NULL(h, d->state_out); SL_CHECK_NULL(h, d->psi_out);
     SL_CHECK_NULL(h, d->last_out); SL_CHECK_NULL(h, d->len_out); SL_CHECK_NULL(h, d->result);
   }
-  SL_REQUIRE(h, K >= 1 && K <= PS_KMAX, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (prefix score): K = -max_target_length is 1..32");
-  SL_REQUIRE(h, d->G >= 1, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (prefix score): G >= 1");
-  SL_REQUIRE(h, S > 0 && blank >= 0, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (prefix score): shape");
+  SL_REQUIRE(h, K >= 1 && K <= PS_KMAX, SIMULST_E_SHAPE, "simulst_ctc_prefix_score: K is 1..32");
+  SL_REQUIRE(h, d->G >= 1, SIMULST_E_SHAPE, "simulst_ctc_prefix_score: G >= 1");
+  SL_REQUIRE(h, S > 0 && blank >= 0, SIMULST_E_SHAPE, "simulst_ctc_prefix_score: shape");
   if (N <= 0) return SIMULST_OK;
-  SL_REQUIRE(h, N % d->G == 0, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (prefix score): N rows a multiple of G");
+  SL_REQUIRE(h, N % d->G == 0, SIMULST_E_SHAPE, "simulst_ctc_prefix_score: N rows a multiple of G");
   KTimer t(h, SIMULST_K_SCAN);
   if (d->op == 0)
-    hipLaunchKernelGGL(ctc_prefix_score_kernel, dim3(N), dim3(64), 0, h->stream, log_probs, (long)lp_stride_t, (long)lp_stride_b,
-                       (long)lp_stride_v, d->blank_lp, (long)d->blank_stride_b, d->state, d->psi, (const long*)targets,
-                       (const long*)target_lengths, (const long*)input_lengths, (const int*)d->finished, S, d->G, K, blank, d->eos,
+    hipLaunchKernelGGL(ctc_prefix_score_kernel, dim3(N), dim3(64), 0, h->stream, cand_log_probs, (long)lp_stride_t, (long)lp_stride_b,
+                       (long)lp_stride_v, d->blank_lp, (long)d->blank_stride_b, d->state, d->psi, (const long*)last_labels,
+                       (const long*)prefix_lengths, (const long*)input_lengths, (const int*)d->finished, S, d->G, K, blank, d->eos,
                        d->pad, d->weight, d->first_only, d->cand_state, d->cand_psi, d->cand_lp, (int*)d->cand_tok, (int*)d->cand_slot);
   else
     hipLaunchKernelGGL(ctc_prefix_commit_kernel, dim3(N), dim3(64), 0, h->stream, d->cand_state, d->cand_psi, (const int*)d->cand_tok,
                        (const int*)d->cand_slot, (const long*)d->next_tok, (const int*)d->reorder, (const int*)d->finished,
-                       (const long*)target_lengths, (const long*)input_lengths, S, N, d->G, K, d->state_out, d->psi_out,
+                       (const long*)prefix_lengths, (const long*)input_lengths, S, N, d->G, K, d->state_out, d->psi_out,
                        (long*)d->last_out, (long*)d->len_out, (int*)d->result);
-  return sl_launch_status(h, who);
+  return sl_launch_status(h, "simulst_ctc_prefix_score");
 }

@@ -1,6 +1,5 @@
-// Batched Levenshtein alignment of int64 label strings for gfx950 -- the edit-distance mode of simulst_ctc_best_alignment
-// (log_probs == NULL with max_target_length >= 0, include/simulst_hip.h; DESIGN.md "CTC head", subsection "Error rates").  The word /
-// token error rate of the reference's ASR stage (tasks/speech_to_text_infer.py:206-215, fairseq's WerScorer over the editdistance
+// Batched Levenshtein alignment of int64 label strings for gfx950 -- simulst_edit_distance (include/simulst_hip.h; DESIGN.md "CTC
+// head", subsection "Error rates").  The word / token error rate of the reference's ASR stage (tasks/speech_to_text_infer.py:206-215, fairseq's WerScorer over the editdistance
 // package) is the sum of these distances over the sum of the reference lengths.
 //
 // One WAVE per pair, pairs by index (one reference row can face 16 hypotheses, a list can face itself), strings read in place.
@@ -22,7 +21,7 @@
 
 namespace {
 
-constexpr int ED_MAX = 1023;            // labels of a string (the limit the other CTC modes have)
+constexpr int ED_MAX = 1023;            // labels of a string (the limit simulst_ctc_best_alignment has)
 constexpr int ED_TILE = 64 * 64;        // staged back-pointers: 64 steps x 64 lanes
 
 // value of lane l - 1 (lane 0 keeps `own`): v_mov_b32_dpp wave_shr:1
@@ -167,33 +166,35 @@ __global__ __launch_bounds__(256) void edit_distance_kernel(const long* __restri
 
 }  // namespace
 
-int sl_edit_distance(simulst_handle* h, const int64_t* refs, int64_t ref_stride_b, const int64_t* hyp_lengths,
-                     const int64_t* ref_lengths, int32_t hyp_cap, int32_t N, int32_t ref_cap, const void* desc, void* ops) {
-  const char* who = "simulst_ctc_best_alignment (edit distance)";
+extern "C" int simulst_edit_distance(simulst_handle* h, const int64_t* refs, int64_t ref_stride_b, const int64_t* ref_lengths,
+                                     const int64_t* hyp_lengths, int32_t ref_cap, int32_t hyp_cap, int32_t N,
+                                     const simulst_edit_desc* desc, void* ops) {
+  if (!h) return SIMULST_E_NULL;
+  const char* who = "simulst_edit_distance";
   SL_CHECK_NULL(h, desc);
-  const simulst_edit_desc* d = static_cast<const simulst_edit_desc*>(desc);
+  const simulst_edit_desc* d = desc;
   SL_CHECK_NULL(h, refs); SL_CHECK_NULL(h, ref_lengths); SL_CHECK_NULL(h, hyp_lengths);
   SL_CHECK_NULL(h, d->hyp); SL_CHECK_NULL(h, d->counts);
   SL_REQUIRE(h, ref_cap <= ED_MAX && hyp_cap <= ED_MAX, SIMULST_E_SHAPE,
-             "simulst_ctc_best_alignment (edit distance): more than 1023 labels in a string");
-  SL_REQUIRE(h, hyp_cap >= 0 && d->n_ref >= 0 && d->n_hyp >= 0, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (edit distance): shape");
+             "simulst_edit_distance: more than 1023 labels in a string");
+  SL_REQUIRE(h, ref_cap >= 0 && hyp_cap >= 0 && d->n_ref >= 0 && d->n_hyp >= 0, SIMULST_E_SHAPE, "simulst_edit_distance: shape");
   // pairs by position name rows 0 .. N-1: known here.  Indices on the device are compared with n_ref / n_hyp by the kernel
-  SL_REQUIRE(h, d->ref_idx || N <= d->n_ref, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (edit distance): pair index past the reference rows");
-  SL_REQUIRE(h, d->hyp_idx || N <= d->n_hyp, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (edit distance): pair index past the hypothesis rows");
+  SL_REQUIRE(h, d->ref_idx || N <= d->n_ref, SIMULST_E_SHAPE, "simulst_edit_distance: pair index past the reference rows");
+  SL_REQUIRE(h, d->hyp_idx || N <= d->n_hyp, SIMULST_E_SHAPE, "simulst_edit_distance: pair index past the hypothesis rows");
   const bool path = ops != nullptr;
   if (path) {
     SL_CHECK_NULL(h, d->n_ops);
-    SL_REQUIRE(h, d->ops_width == 1 || d->ops_width == 4, SIMULST_E_SHAPE, "simulst_ctc_best_alignment (edit distance): ops_width is 1 or 4");
+    SL_REQUIRE(h, d->ops_width == 1 || d->ops_width == 4, SIMULST_E_SHAPE, "simulst_edit_distance: ops_width is 1 or 4");
     SL_REQUIRE(h, d->ops_cap >= ref_cap + hyp_cap, SIMULST_E_SHAPE,
-               "simulst_ctc_best_alignment (edit distance): ops_cap below the two capacities' sum");
+               "simulst_edit_distance: ops_cap below the two capacities' sum");
   }
   if (N <= 0) return SIMULST_OK;
   if (path) {
     SL_CHECK_NULL(h, d->bp);
     SL_REQUIRE(h, (reinterpret_cast<uintptr_t>(d->bp) & 15) == 0, SIMULST_E_ARG,
-               "simulst_ctc_best_alignment (edit distance): back-pointer scratch is not 16-byte aligned");
+               "simulst_edit_distance: back-pointer scratch is not 16-byte aligned");
     SL_REQUIRE(h, d->bp_bytes >= (int64_t)N * ed_bp_pair_bytes(ref_cap, hyp_cap), SIMULST_E_SHAPE,
-               "simulst_ctc_best_alignment (edit distance): back-pointer scratch below SIMULST_EDIT_BP_BYTES");
+               "simulst_edit_distance: back-pointer scratch below SIMULST_EDIT_BP_BYTES");
   }
   // several pairs a workgroup while their LDS fits the default 48 KB; the 1023-label layout runs a wave a workgroup
   const int per_wave = ed_wave_lds(ref_cap, hyp_cap, path);

@@ -13,14 +13,14 @@ hypotheses, and ``CTCTranscriber.score_ctc`` is the model-level call.
 
 ``ctc_topk`` is the head's per-frame candidate list -- the blank and the best k other labels with their log-probabilities, again
 without the logits (Ops.linear_topk: SIMULST_EPI_ROW_TOPK) --, ``ctc_prefix_beam_advance`` the time-synchronous prefix beam search over
-such lists (on the GPU every frame of a call in ONE launch, the search mode of simulst_ctc_best_alignment in csrc/ctc_prefix.hip, with
+such lists (on the GPU every frame of a call in ONE launch, simulst_ctc_prefix_beam in csrc/ctc_prefix.hip, with
 the same recursion as device tensor operations kept as the comparison; the state goes in and comes out, so that chunks of rows continue
 one search), ``ctc_prefix_beam_search`` the two together and ``CTCTranscriber.transcribe_ctc_nbest`` the model-level call,
 whose hypotheses ``ctc_rescore`` gives their exact likelihoods.  No language model is fused in, and no gradient is computed.
 
 ``CTCPrefixScorer`` is the CTC side of joint CTC / attention decoding: inside the attention beam search (beam.BeamSearch, rescore=)
 every candidate of every step is scored by the CTC prefix probability of the extended string -- ``ctc_prefix_score``, one launch a step
-(the scoring mode of simulst_ctc_best_alignment, csrc/ctc_prefix_score.hip) over log-probabilities gathered at the candidates alone --
+(simulst_ctc_prefix_score, csrc/ctc_prefix_score.hip) over log-probabilities gathered at the candidates alone --
 and ``ctc_prefix_commit`` moves the chosen candidates' states behind the selection; both have a torch form (composed=True).
 
 The blank index is a keyword everywhere (default 0, the criterion's fallback, joint_ctc_criterion.py:76).
@@ -265,7 +265,7 @@ def ctc_prefix_beam_advance(ids: torch.Tensor, lprob: torch.Tensor, enc_len: tor
     best of the pool by p_b' (+) p_nb' survive, ties in pool index order (a stable sort).  A frame at or past enc_len[b] leaves row b's
     state as it is.
 
-    On the GPU all T frames run in ONE launch (the search mode of simulst_ctc_best_alignment, csrc/ctc_prefix.hip: one wave per
+    On the GPU all T frames run in ONE launch (simulst_ctc_prefix_beam, csrc/ctc_prefix.hip: one wave per
     utterance, the strings in LDS for the call), with no read-back; `ops` is the Ops whose stream it goes to (default: a new one).  The
     same recursion as torch tensor operations -- about 120 small launches a frame -- is kept as the comparison and is what runs with
     composed=True, for CPU tensors, and where the kernel has no place for the call: strings longer than _lib.ctc_prefix_cap(beam)
@@ -298,9 +298,9 @@ def ctc_prefix_beam_advance(ids: torch.Tensor, lprob: torch.Tensor, enc_len: tor
     d.cand_ids, d.id_stride_b, d.id_stride_t = ids.data_ptr(), ids.stride(0), ids.stride(1)
     d.k, d.pad, d.cap = kp - 1, int(pad), strings.size(2)
     d.lengths, d.p_b, d.p_nb = lengths.data_ptr(), p_b.data_ptr(), p_nb.data_ptr()
-    ops.h.check(ops.lib.simulst_ctc_best_alignment(ops.h.ptr, _p(lprob), lprob.stride(1), lprob.stride(0), lprob.stride(2), _p(None), 0,
-                                                   _p(il), _p(None), T, B, -beam, 0, 0, ctypes.addressof(d), _p(strings), _p(None)),
-                "simulst_ctc_best_alignment (prefix beam)")
+    ops.h.check(ops.lib.simulst_ctc_prefix_beam(ops.h.ptr, _p(lprob), lprob.stride(1), lprob.stride(0), lprob.stride(2), _p(il), T, B,
+                                                beam, 0, ctypes.byref(d), _p(strings)),
+                "simulst_ctc_prefix_beam")
     return strings, lengths, p_b, p_nb
 
 
@@ -391,8 +391,8 @@ SCORE_KMAX = 32
 
 def ctc_prefix_score(ops, x, xb, state, psi, last, plen, in_len, finished, cand_lp, cand_tok, cand_slot, cand_state, cand_psi, *,
                      G: int, blank: int, eos: int, pad: int, weight: float, first_only: bool = False, composed: bool = False):
-    """One step's CTC prefix scores (DESIGN.md "Beam search", "CTC prefix scores inside the beam"; the scoring mode of
-    simulst_ctc_best_alignment, csrc/ctc_prefix_score.hip), for R = Bs * G beam rows of K candidates each:
+    """One step's CTC prefix scores (DESIGN.md "Beam search", "CTC prefix scores inside the beam"; simulst_ctc_prefix_score,
+    csrc/ctc_prefix_score.hip), for R = Bs * G beam rows of K candidates each:
       x [Bs, S, G * K] fp32 (any strides): the candidates' log-probabilities under the head;  xb [Bs, S] fp32: the blank's
       state [R, S, 2] fp32 (gn, gb), psi [R] fp32, last [R] int64, plen [R] int64: the rows' hypotheses;  in_len [R] int64 frames
       finished [Bs] int32 or None;  cand_lp [R, K] fp32 / cand_tok [R, K] int32: simulst_beam_topk's lists, REWRITTEN in place
@@ -417,9 +417,9 @@ def ctc_prefix_score(ops, x, xb, state, psi, last, plen, in_len, finished, cand_
     d.state, d.psi, d.cand_state, d.cand_psi = state.data_ptr(), psi.data_ptr(), cand_state.data_ptr(), cand_psi.data_ptr()
     d.cand_lp, d.cand_tok, d.cand_slot = cand_lp.data_ptr(), cand_tok.data_ptr(), cand_slot.data_ptr()
     d.finished = finished.data_ptr() if finished is not None else None
-    ops.h.check(ops.lib.simulst_ctc_best_alignment(ops.h.ptr, _p(x), x.stride(1), x.stride(0), x.stride(2), _p(last), 0, _p(in_len),
-                                                   _p(plen), S, R, -K, int(blank), 0, ctypes.addressof(d), _p(None), _p(None)),
-                "simulst_ctc_best_alignment (prefix score)")
+    ops.h.check(ops.lib.simulst_ctc_prefix_score(ops.h.ptr, _p(x), x.stride(1), x.stride(0), x.stride(2), _p(last), _p(in_len), _p(plen),
+                                                 S, R, K, int(blank), ctypes.byref(d)),
+                "simulst_ctc_prefix_score")
 
 
 def ctc_prefix_commit(ops, cand_state, cand_psi, cand_tok, cand_slot, next_tok, reorder, finished, last, plen, in_len, state_out,
@@ -427,7 +427,7 @@ def ctc_prefix_commit(ops, cand_state, cand_psi, cand_tok, cand_slot, next_tok, 
     """Behind simulst_beam_select: row r of an unfinished sentence takes the state and psi of candidate next_tok[r] (int64 [R]) of its
     parent row reorder[r] (int32 [R]) into state_out [R, S, 2] / psi_out [R], last_out[r] = next_tok[r], len_out[r] = plen[parent] + 1.
     A token that is not among the parent's candidates (or a parent outside the sentence) adds 1 to result[0] (int32) and leaves the
-    row.  `last` is not read (the entry wants it: it selects the mode)."""
+    row.  `last` is unused."""
     R, K = cand_tok.shape
     S = state_out.size(1)
     if composed or not cand_tok.is_cuda:
@@ -446,9 +446,9 @@ def ctc_prefix_commit(ops, cand_state, cand_psi, cand_tok, cand_slot, next_tok, 
     d.finished = finished.data_ptr() if finished is not None else None
     d.next_tok, d.reorder, d.state_out, d.psi_out = next_tok.data_ptr(), reorder.data_ptr(), state_out.data_ptr(), psi_out.data_ptr()
     d.last_out, d.len_out, d.result = last_out.data_ptr(), len_out.data_ptr(), result.data_ptr()
-    ops.h.check(ops.lib.simulst_ctc_best_alignment(ops.h.ptr, _p(None), 0, 0, 0, _p(last), 0, _p(in_len), _p(plen), S, R, -K, 0, 0,
-                                                   ctypes.addressof(d), _p(None), _p(None)),
-                "simulst_ctc_best_alignment (prefix score, commit)")
+    ops.h.check(ops.lib.simulst_ctc_prefix_score(ops.h.ptr, _p(None), 0, 0, 0, _p(None), _p(in_len), _p(plen), S, R, K, 0,
+                                                 ctypes.byref(d)),
+                "simulst_ctc_prefix_score (commit)")
 
 
 def _score_rows(R, G, finished, first_only, dev):

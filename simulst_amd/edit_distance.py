@@ -2,8 +2,8 @@
 
 The reference's ASR stage is judged by word error rate (exp/infer_asr.yaml eval_wer, tasks/speech_to_text_infer.py:206-215: fairseq's
 WerScorer, the sum of edit distances over the sum of reference lengths, summed over workers at :263-289).  `edit_distance` is that
-distance for N (reference, hypothesis) pairs of int64 label strings in ONE launch (csrc/edit_distance.hip, the edit-distance mode of
-simulst_ctc_best_alignment), with the substitution / deletion / insertion counts of ONE alignment fixed by a tie rule, and optionally
+distance for N (reference, hypothesis) pairs of int64 label strings in ONE launch (csrc/edit_distance.hip,
+simulst_edit_distance), with the substitution / deletion / insertion counts of ONE alignment fixed by a tie rule, and optionally
 that alignment.  Pairs are named by row indices, so the shapes a host loop is bad at cost nothing extra: a 16-best list against its
 reference (`oracle_error`) and an n-best list against itself (`mbr_select`, minimum-Bayes-risk selection).
 

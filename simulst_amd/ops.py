@@ -774,12 +774,11 @@ class Ops:
     # ------------------------------------------------------------------ error rates (csrc/edit_distance.hip)
     def edit_distance(self, ref, ref_len, hyp, hyp_len, *, ref_idx=None, hyp_idx=None, n_pairs=None, path=False, pad=-1,
                       ops_dtype=torch.int8, ref_cap=None, hyp_cap=None):
-        """The edit-distance mode of simulst_ctc_best_alignment: ref [Rr, >= ref_cap] / hyp [Rh, >= hyp_cap] int64 label strings (rows
+        """simulst_edit_distance: ref [Rr, >= ref_cap] / hyp [Rh, >= hyp_cap] int64 label strings (rows
         contiguous, any row stride; the same tensor may be both), ref_len [Rr] / hyp_len [Rh] int64, ref_idx / hyp_idx int32 [N] or
         None (pair p is rows p, p) -> counts int32 [N, 4] = (distance, sub, del, ins); with path also (ops [N, ref_cap + hyp_cap] in
         ops_dtype -- 0 match, 1 substitution, 2 deletion, 3 insertion, `pad` behind --, n_ops int32 [N]).  The capacities default to the
         tensors' widths, at most 1023.  No read-back."""
-        import ctypes
         for t in (ref, hyp, ref_len, hyp_len):
             if t.dtype != torch.int64:
                 raise TypeError("edit_distance: strings and lengths are int64")
@@ -825,9 +824,9 @@ class Ops:
             n_ops = torch.empty(N, device=dev, dtype=torch.int32)
             bp = torch.empty(max(_lib.edit_bp_bytes(N, ref_cap, hyp_cap), 16), device=dev, dtype=torch.uint8)
             d.n_ops, d.bp, d.bp_bytes, d.ops_cap, d.ops_width = n_ops.data_ptr(), bp.data_ptr(), bp.numel(), cap, out.element_size()
-        self.h.check(self.lib.simulst_ctc_best_alignment(self.h.ptr, _p(None), 0, 0, 0, _p(ref), ref.stride(0), _p(hyp_len), _p(ref_len),
-                                                         hyp_cap, N, ref_cap, 0, 0, ctypes.addressof(d), _p(out), _p(None)),
-                     "simulst_ctc_best_alignment (edit distance)")
+        self.h.check(self.lib.simulst_edit_distance(self.h.ptr, _p(ref), ref.stride(0), _p(ref_len), _p(hyp_len), ref_cap, hyp_cap, N,
+                                                    C.byref(d), _p(out)),
+                     "simulst_edit_distance")
         return (counts, out, n_ops) if path else counts
 
     # ------------------------------------------------------------------ beam search (csrc/beam.hip)

@@ -1,9 +1,11 @@
-"""CPU-side checks of the search mode of simulst_ctc_best_alignment (max_target_length < 0: the prefix beam recursion of
-csrc/ctc_prefix.hip).  Every refusal is made before a launch (all pointers below are host memory or null), no utterance is no error, the
-modes with max_target_length >= 0 answer as before, and the mode added no entry point and changed no descriptor."""
+"""CPU-side checks of simulst_ctc_prefix_beam (the prefix beam recursion of csrc/ctc_prefix.hip).  Every refusal is made before a
+launch (all pointers below are host memory or null), no utterance is no error, simulst_ctc_best_alignment answers for a transcript
+alone, and no descriptor changed."""
 import ctypes
 
 import pytest
+
+import abi_pins
 
 E_NULL, E_SHAPE = -1, -2
 
@@ -35,28 +37,28 @@ def test_search_mode_refusals_on_host_buffers(handle):
     p = ctypes.c_void_p(ctypes.addressof(buf))
 
     def call(d, beam=8, N=2, lp=p, il=p, out=p, S=5, blank=0):
-        return lib.simulst_ctc_best_alignment(h, lp, 18, 9, 1, None, 0, il, None, S, N, -beam, blank, 0,
-                                              ctypes.addressof(d) if d is not None else None, out, None)
+        return lib.simulst_ctc_prefix_beam(h, lp, 18, 9, 1, il, S, N, beam, blank, ctypes.byref(d) if d is not None else None, out)
 
     err = lambda: lib.simulst_last_error(h)
     # null pointers: the descriptor, what it points to, and the call's own
-    assert call(None) == E_NULL
     for field in ("cand_ids", "lengths", "p_b", "p_nb"):
         assert call(_desc(p, **{field: None})) == E_NULL and field.encode() in err()
-    assert call(_desc(p), out=None) == E_NULL and b"out" in err()
-    assert call(_desc(p), lp=None) == E_NULL and b"log_probs" in err()
+    assert call(None) == E_NULL and b": desc" in err()
+    assert call(_desc(p), out=None) == E_NULL and b": strings" in err()
+    assert call(_desc(p), lp=None) == E_NULL and b"cand_log_probs" in err()
     assert call(_desc(p), il=None) == E_NULL and b"input_lengths" in err()
-    # shapes; targets and target_lengths are NULL throughout
-    assert call(_desc(p), beam=17) == E_SHAPE and b"beam" in err()
-    assert call(_desc(p), beam=2 ** 31) == E_SHAPE and b"beam" in err()          # INT32_MIN as max_target_length
+    # shapes (the function's own name holds "beam": the phrase names the argument)
+    assert call(_desc(p), beam=17) == E_SHAPE and b"beam is 1..16" in err()
+    assert call(_desc(p), beam=0) == E_SHAPE and b"beam is 1..16" in err()
+    assert call(_desc(p), beam=2 ** 31) == E_SHAPE and b"beam is 1..16" in err()          # INT32_MIN
     assert call(_desc(p, k=9)) == E_SHAPE and b"k is" in err()
     assert call(_desc(p, k=-1)) == E_SHAPE and b"k is" in err()
-    assert call(_desc(p, cap=0)) == E_SHAPE and b"cap" in err()
+    assert call(_desc(p, cap=0)) == E_SHAPE and b"cap is" in err()
     assert call(_desc(p), S=0) == E_SHAPE and call(_desc(p), blank=-1) == E_SHAPE
     for beam in (1, 8, 16):
         limit = _lib.ctc_prefix_cap(beam)
         assert limit % 4 == 0 and 8 * beam * limit <= _lib.CTC_PREFIX_STRING_BYTES < 8 * beam * (limit + 4)
-        assert call(_desc(p, cap=limit + 1), beam=beam, N=0) == E_SHAPE and b"cap" in err()
+        assert call(_desc(p, cap=limit + 1), beam=beam, N=0) == E_SHAPE and b"cap is" in err()
         assert call(_desc(p, cap=limit), beam=beam, N=0) == 0
     assert _lib.ctc_prefix_cap(16) == 1104 >= 1024
     # the refusals hold with no utterance too; a valid call with none launches nothing
@@ -78,17 +80,23 @@ def test_modes_with_a_transcript_answer_as_before(handle):
     assert call(0, None, p, mtl=1024) == E_SHAPE and b"1023" in lib.simulst_last_error(h)
     assert call(0, p, p, targets=None) == E_NULL and b"targets" in lib.simulst_last_error(h)
     assert call(0, p, p, tl=None) == E_NULL and b"target_lengths" in lib.simulst_last_error(h)
+    # no other operation hides behind the arguments: a negative max_target_length is a shape, NULL log_probs a null pointer
+    for mtl in (-1, -8, -2 ** 31):
+        assert call(0, p, p, mtl=mtl) == E_SHAPE and b"shape" in lib.simulst_last_error(h)
+        assert call(0, p, p, mtl=mtl, targets=None) == E_NULL and b"targets" in lib.simulst_last_error(h)
+    assert lib.simulst_ctc_best_alignment(h, None, 8, 4, 1, p, 3, p, p, 5, 2, 3, 0, 0, p, p, None) == E_NULL
+    assert b"log_probs" in lib.simulst_last_error(h)
 
 
 def test_descriptor_layout_and_pinned_counts():
     from simulst_amd import _lib
     d = _lib.CtcPrefixDesc
-    assert ctypes.sizeof(d) == 64
+    assert ctypes.sizeof(d) == abi_pins.CTC_PREFIX_DESC_BYTES
     assert [getattr(d, n).offset for n in ("cand_ids", "id_stride_b", "id_stride_t", "k", "pad", "cap", "lengths", "p_b", "p_nb")] == \
         [0, 8, 16, 24, 28, 32, 40, 48, 56]
-    assert len(_lib.SIGNATURES) == 81
-    assert _lib.load().simulst_version() == 108 == _lib.ABI_VERSION
-    assert ctypes.sizeof(_lib.LinearDesc) == 152
+    assert len(_lib.SIGNATURES) == abi_pins.N_SIGNATURES
+    assert _lib.load().simulst_version() == abi_pins.VERSION == _lib.ABI_VERSION
+    assert ctypes.sizeof(_lib.LinearDesc) == abi_pins.LINEAR_DESC_BYTES
 
 
 def test_python_surface_takes_ops_and_composed():

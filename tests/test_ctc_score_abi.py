@@ -6,6 +6,8 @@ import ctypes
 
 import pytest
 
+import abi_pins
+
 E_NULL, E_SHAPE, E_ARG = -1, -2, -4
 ROW_GATHER = 9
 
@@ -94,6 +96,6 @@ def test_sum_mode_of_ctc_best_alignment_on_host_buffers(handle):
 
 def test_no_new_entry_point_and_no_descriptor_change():
     from simulst_amd import _lib
-    assert len(_lib.SIGNATURES) == 81
-    assert _lib.load().simulst_version() == 108 == _lib.ABI_VERSION
-    assert ctypes.sizeof(_lib.LinearDesc) == 152
+    assert len(_lib.SIGNATURES) == abi_pins.N_SIGNATURES
+    assert _lib.load().simulst_version() == abi_pins.VERSION == _lib.ABI_VERSION
+    assert ctypes.sizeof(_lib.LinearDesc) == abi_pins.LINEAR_DESC_BYTES

@@ -1,7 +1,6 @@
 """CPU-side checks of the error-rate work: the reference of tests/edit_distance_ref.py against exhaustive enumeration, known answers
-and identities; the composed (host) form of simulst_amd.edit_distance against it; harness.WerScorer / corpus_wer / corpus_scores; the
-edit-distance mode of simulst_ctc_best_alignment at the ABI (declared, no new entry point, refusals made before any launch on host
-buffers); sharding.reduce_error_counts under two gloo ranks.  Everything compared is an integer: every assertion is equality."""
+and identities; the composed (host) form of simulst_amd.edit_distance against it; harness.WerScorer / corpus_wer / corpus_scores;
+simulst_edit_distance at the ABI (declared, refusals made before any launch on host buffers); sharding.reduce_error_counts under two gloo ranks.  Everything compared is an integer: every assertion is equality."""
 import ctypes
 import os
 import random
@@ -12,6 +11,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import abi_pins
 import edit_distance_ref as er
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -224,9 +224,10 @@ def test_descriptor_is_declared_and_nothing_else_moved():
     header = open(os.path.join(ROOT, "include", "simulst_hip.h")).read()
     assert "} simulst_edit_desc;" in header and "SIMULST_EDIT_BP_BYTES" in header
     assert _lib.edit_bp_bytes(3, 1023, 1023) == 3 * 16 * 1086 * 64 and _lib.edit_bp_bytes(1, 10, 64) == 73 * 64
-    assert len(_lib.SIGNATURES) == 81
-    assert _lib.load().simulst_version() == 108 == _lib.ABI_VERSION
-    assert ctypes.sizeof(_lib.LinearDesc) == 152 and ctypes.sizeof(_lib.CtcPrefixDesc) == 64
+    assert len(_lib.SIGNATURES) == abi_pins.N_SIGNATURES
+    assert _lib.load().simulst_version() == abi_pins.VERSION == _lib.ABI_VERSION
+    assert ctypes.sizeof(_lib.LinearDesc) == abi_pins.LINEAR_DESC_BYTES
+    assert ctypes.sizeof(_lib.CtcPrefixDesc) == abi_pins.CTC_PREFIX_DESC_BYTES
 
 
 def test_mode_refusals_on_host_buffers(handle):
@@ -244,20 +245,22 @@ def test_mode_refusals_on_host_buffers(handle):
             setattr(d, k, v)
         return d
 
-    def call(d, N=0, refs=p, il=p, tl=p, S=8, cap=8, out=None):
-        return lib.simulst_ctc_best_alignment(h, None, 0, 0, 0, refs, 8, il, tl, S, N, cap, 0, 0,
-                                              ctypes.addressof(d) if d is not None else None, out, None)
+    def call(d, N=0, refs=p, il=p, tl=p, S=8, cap=8, out=None):          # il: the hypothesis lengths, tl: the reference lengths
+        return lib.simulst_edit_distance(h, refs, 8, tl, il, cap, S, N, ctypes.byref(d) if d is not None else None, out)
 
     err = lambda: lib.simulst_last_error(h)   # noqa: E731
-    assert call(None) == E_NULL and call(None, N=2) == E_NULL
+    assert call(None) == E_NULL and call(None, N=2) == E_NULL and b": desc" in err()
     assert call(desc(counts=None), N=2) == E_NULL and b"counts" in err()
-    assert call(desc(hyp=None), N=2) == E_NULL and b"hyp" in err()
-    assert call(desc(), N=2, refs=None) == E_NULL and call(desc(), N=2, il=None) == E_NULL and call(desc(), N=2, tl=None) == E_NULL
+    assert call(desc(hyp=None), N=2) == E_NULL and b"d->hyp" in err()
+    assert call(desc(), N=2, refs=None) == E_NULL and b": refs" in err()
+    assert call(desc(), N=2, il=None) == E_NULL and b"hyp_lengths" in err()
+    assert call(desc(), N=2, tl=None) == E_NULL and b"ref_lengths" in err()
     # the capacities: 1023 labels at the most, on either side
     assert call(desc(), cap=1024) == E_SHAPE and b"1023" in err()
     assert call(desc(), S=1024) == E_SHAPE and b"1023" in err()
     assert call(desc(), N=2, cap=1024) == E_SHAPE and b"1023" in err()
     assert call(desc(), cap=1023, S=1023) == 0
+    assert call(desc(), cap=-1) == E_SHAPE and call(desc(), S=-1) == E_SHAPE and b"shape" in err()
     # pairs by position name rows 0 .. N-1: the host knows them
     assert call(desc(), N=5) == E_SHAPE and b"index" in err()
     # the path's own arguments
@@ -270,13 +273,16 @@ def test_mode_refusals_on_host_buffers(handle):
     assert call(desc()) == 0 and call(desc(), N=-3) == 0 and call(desc(), out=p) == 0 and call(desc(bp=None), out=p) == 0
 
 
-def test_the_other_modes_still_come_first(handle):
-    """max_target_length < 0 with a NULL log_probs is the search / scoring mode's refusal, as before"""
+def test_best_alignment_compares_no_strings(handle):
+    """what was the edit-distance call through simulst_ctc_best_alignment (NULL log_probs) is a null pointer, whatever the rest says"""
     lib, h = handle
     buf = (ctypes.c_int64 * 64)()
     p = ctypes.c_void_p(ctypes.addressof(buf))
-    assert lib.simulst_ctc_best_alignment(h, None, 0, 0, 0, None, 0, p, None, 5, 2, -8, 0, 0, None, p, None) == E_NULL
-    assert b"desc" in lib.simulst_last_error(h)
+    for mtl in (8, -8):
+        assert lib.simulst_ctc_best_alignment(h, None, 0, 0, 0, p, 8, p, p, 8, 2, mtl, 0, 0, p, p, None) == E_NULL
+        assert b"log_probs" in lib.simulst_last_error(h)
+    assert lib.simulst_ctc_best_alignment(h, p, 8, 4, 1, p, 3, p, p, 5, 2, -8, 0, 0, None, p, None) == E_SHAPE
+    assert b"shape" in lib.simulst_last_error(h)
     assert lib.simulst_ctc_best_alignment(h, p, 8, 4, 1, None, 3, p, p, 5, 0, 3, 0, 0, None, p, p) == E_NULL
     assert b"targets" in lib.simulst_last_error(h)
 

@@ -5,6 +5,8 @@ import ctypes
 
 import pytest
 
+import abi_pins
+
 E_SHAPE, E_ARG = -2, -4
 F32, BF16 = 0, 1
 
@@ -56,4 +58,4 @@ def test_other_refusals_keep_status_and_message(handle):
 
 def test_version_unchanged():
     from simulst_amd import _lib
-    assert _lib.load().simulst_version() == 108 == _lib.ABI_VERSION
+    assert _lib.load().simulst_version() == abi_pins.VERSION == _lib.ABI_VERSION

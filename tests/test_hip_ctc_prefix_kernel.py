@@ -1,5 +1,5 @@
-"""The prefix beam recursion in one launch (csrc/ctc_prefix.hip: the search mode of simulst_ctc_best_alignment, max_target_length < 0,
-behind ctc.ctc_prefix_beam_advance) on the MI355X, fed with the hand-made candidate lists of tests/ctc_prefix_ref.py -- no projection
+"""The prefix beam recursion in one launch (csrc/ctc_prefix.hip: simulst_ctc_prefix_beam, behind
+ctc.ctc_prefix_beam_advance) on the MI355X, fed with the hand-made candidate lists of tests/ctc_prefix_ref.py -- no projection
 is involved -- against the fp64 reference of tests/ctc_beam_ref.py on the same lists and against the torch form (composed=True).
 
 The rule is tests/test_hip_ctc_beam.py's: a score lies within beam_bound(n, score) = (n + 1) 2^-22 max(1, |score|) of the reference; an
@@ -246,9 +246,9 @@ def test_capacity_limit_and_fallback(ops, monkeypatch):
     d.cand_ids, d.id_stride_b, d.id_stride_t, d.k, d.pad, d.cap = ids.data_ptr(), ids.stride(0), ids.stride(1), 8, PAD, limit + 1
     d.lengths, d.p_b, d.p_nb = lengths.data_ptr(), p_b.data_ptr(), p_nb.data_ptr()
     vp = ctypes.c_void_p
-    rc = ops.lib.simulst_ctc_best_alignment(ops.h.ptr, vp(lp.data_ptr()), lp.stride(1), lp.stride(0), lp.stride(2), None, 0,
-                                            vp(il.data_ptr()), None, T, 3, -beam, 0, 0, ctypes.addressof(d), vp(strings.data_ptr()), None)
-    assert rc == -2 and b"cap" in ops.lib.simulst_last_error(ops.h.ptr)
+    rc = ops.lib.simulst_ctc_prefix_beam(ops.h.ptr, vp(lp.data_ptr()), lp.stride(1), lp.stride(0), lp.stride(2), vp(il.data_ptr()), T, 3,
+                                         beam, 0, ctypes.byref(d), vp(strings.data_ptr()))
+    assert rc == -2 and b"cap is" in ops.lib.simulst_last_error(ops.h.ptr)
     torch.cuda.synchronize()
     assert bool((strings == PAD).all())
 

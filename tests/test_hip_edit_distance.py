@@ -1,5 +1,5 @@
-"""The batched edit distance on the MI355X (csrc/edit_distance.hip: the edit-distance mode of simulst_ctc_best_alignment, log_probs NULL
-with max_target_length >= 0, behind simulst_amd.edit_distance) against tests/edit_distance_ref.py.  Everything is an integer, so every
+"""The batched edit distance on the MI355X (csrc/edit_distance.hip: simulst_edit_distance, behind
+simulst_amd.edit_distance) against tests/edit_distance_ref.py.  Everything is an integer, so every
 comparison is equality: the four counts of every pair, and the alignment operation by operation.
 
 The length grid {0, 1, 2, 63, 64, 65, 127, 128, 129, 1022, 1023} sits on the kernel's edges: a hypothesis is laid over the 64 lanes of a
@@ -222,8 +222,8 @@ def test_counts_only_runs_with_a_null_scratch(ops):
     d = _lib.EditDesc()
     d.hyp, d.hyp_stride_b, d.n_ref, d.n_hyp, d.counts = h.data_ptr(), h.stride(0), 2, 2, counts.data_ptr()
     vp = ctypes.c_void_p
-    rc = ops.lib.simulst_ctc_best_alignment(ops.h.ptr, None, 0, 0, 0, vp(r.data_ptr()), r.stride(0), vp(hl.data_ptr()), vp(rl.data_ptr()),
-                                            h.size(1), 2, r.size(1), 0, 0, ctypes.addressof(d), None, None)
+    rc = ops.lib.simulst_edit_distance(ops.h.ptr, vp(r.data_ptr()), r.stride(0), vp(rl.data_ptr()), vp(hl.data_ptr()), r.size(1), h.size(1),
+                                       2, ctypes.byref(d), None)
     assert rc == 0
     torch.cuda.synchronize()
     assert counts.cpu().tolist() == [[3, 2, 0, 1], [2, 0, 1, 1], [-99] * 4]

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import abi_pins
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G23 = os.path.join(ROOT, "tests", "golden", "g23_s2t_emformer.npz")
 E_ARG = -4
@@ -100,7 +102,7 @@ def test_full_declared_and_bound():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "simulst_hip.h")).read(), flags=re.S)
     assert re.search(r"SIMULST_ATTN_FULL\s*=\s*4", src)
     assert _lib.ATTN_FULL == 4 and _lib.ATTN_ENUM["full"] == 4
-    assert _lib.load().simulst_version() == 108
+    assert _lib.load().simulst_version() == abi_pins.VERSION
 
 
 @pytest.fixture

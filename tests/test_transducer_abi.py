@@ -7,6 +7,8 @@ import subprocess
 
 import pytest
 
+import abi_pins
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("simulst_transducer_pool", "simulst_joiner_scan", "simulst_joiner_emit", "simulst_joiner_mask_blank")
 E_NULL, E_ARG = -1, -4
@@ -23,7 +25,7 @@ def test_declared_exported_and_bound():
         assert re.search(r"\b" + n + r"$", exported, flags=re.M), n
         assert n in _lib.SIGNATURES and hasattr(lib, n)
     assert re.search(r"global:\s*simulst_\*;", open(os.path.join(ROOT, "simulst_amd", "csrc", "exports.map")).read())
-    assert lib.simulst_version() == 108 == _lib.ABI_VERSION
+    assert lib.simulst_version() == abi_pins.VERSION == _lib.ABI_VERSION
 
 
 @pytest.fixture

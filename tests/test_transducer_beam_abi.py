@@ -7,6 +7,8 @@ import subprocess
 
 import pytest
 
+import abi_pins
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"simulst_joiner_scan_beam": 18, "simulst_joiner_emit_beam": 20, "simulst_transducer_beam_reorder": 11}
 E_NULL, E_ARG = -1, -4
@@ -23,9 +25,9 @@ def test_declared_exported_and_bound():
         assert m and len(m.group(1).split(",")) == n_args, n
         assert re.search(r"\b" + n + r"$", exported, flags=re.M), n
         assert n in _lib.SIGNATURES and len(_lib.SIGNATURES[n]) == n_args and hasattr(lib, n)
-    assert lib.simulst_version() == 108 == _lib.ABI_VERSION           # no descriptor structure changed
+    assert lib.simulst_version() == abi_pins.VERSION == _lib.ABI_VERSION           # no descriptor structure changed
     # the library's entry points: 76 before these three
-    assert len(_lib.SIGNATURES) == 81 == len(re.findall(r"^\S+ T simulst_\w+$", exported, flags=re.M))
+    assert len(_lib.SIGNATURES) == abi_pins.N_SIGNATURES == len(re.findall(r"^\S+ T simulst_\w+$", exported, flags=re.M))
 
 
 @pytest.fixture
